@@ -16,7 +16,7 @@ The same JSON line carries
                 this box's host cores on a bounded sample of the same workload,
   bitset        BASELINE's second metric (BinnedBitSet Gbp/s) on configs[2].
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -35,6 +35,37 @@ for p in (ROOT, os.path.join(ROOT, "bx-python_amd")):
 import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s peak
+DUMP_SAMPLE = 4 << 20  # --dump-outputs: a per-query output longer than this is written as a fixed, seeded sample of this many entries
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_index(n):
+    """Positions of an n-long per-query output that --dump-outputs keeps: all of them, or DUMP_SAMPLE of them drawn with a
+    fixed seed (the same n gives the same positions in every run and every build)."""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(20250).choice(n, DUMP_SAMPLE, replace=False))
+
+
+def dump_counts(counts, idx):
+    """Per-query counts (int32 device tensor) at the positions idx, as float32 when that is exact, else float64."""
+    import torch
+
+    got = counts[torch.from_numpy(idx).to(counts.device)].cpu().numpy()
+    exact32 = got.size == 0 or int(np.abs(got).max()) < (1 << 24)
+    return got.astype(np.float32 if exact32 else np.float64)
+
+
+def write_dump(dirpath, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy (float32 or float64), at most DUMP_CAP_BYTES in all."""
+    nbytes = sum(a.nbytes for a in arrays.values())
+    if nbytes > DUMP_CAP_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes, more than %d" % (nbytes, DUMP_CAP_BYTES))
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    log("bench.py: wrote %s (%d bytes) to %s" % (", ".join(sorted(arrays)), nbytes, dirpath))
 
 
 def log(*a):
@@ -403,11 +434,12 @@ def genome_golden_check(chrom, counts_np, golden):
     return hashlib.sha256(sub.tobytes()).hexdigest() == pt["counts_sha256"] and int(sub.sum(dtype=np.int64)) == pt["total"]
 
 
-def bench_genome(torch, dist, rank, world, steps, warmup, n_targets, n_queries, single_gpu_reference=True):
+def bench_genome(torch, dist, rank, world, steps, warmup, n_targets, n_queries, single_gpu_reference=True, dump=None):
     """BASELINE configs[3]: the 24 hg19 chromosomes (synth.cfg4: 10M targets x 100M queries spread by length), one
     interval index per chromosome, chromosomes dealt to the ranks by LPT (bxmi.shard), every rank counts its own
     chromosomes, the 24 per-chromosome totals are all-reduced (int64, RCCL).  STRONG scaling: the whole job is the
-    same genome whatever the number of GPUs; the time of a step is the slowest rank's.  Returns a dict (rank 0) or None."""
+    same genome whatever the number of GPUs; the time of a step is the slowest rank's.  Returns a dict (rank 0) or None.
+    `dump` (a dict) receives what the last timed step computed: the per-chromosome totals and a sample of the counts."""
     from bxmi import shard, synth
     from bxmi.intervals import IntervalIndex
 
@@ -486,6 +518,15 @@ def bench_genome(torch, dist, rank, world, steps, warmup, n_targets, n_queries, 
     build_s = time.perf_counter() - t0
     collective = world > 1
     elapsed, kernel_ms, rows = timed(mine, steps, warmup, collective)
+    if dump is not None and rank == 0:
+        # (before the side legs below reuse the count buffers; the rank's chromosomes in genome order, their counts end to end)
+        owned = [c for c in chroms if c in mine.owned]
+        allc = torch.cat([mine.counts[c] for c in owned])
+        idx = dump_index(allc.numel())
+        dump["chrom_totals"] = rows[-1].cpu().numpy().astype(np.float64)
+        dump["counts"] = dump_counts(allc, idx)
+        dump["counts_index"] = idx.astype(np.float64)
+        del allc
     if collective:
         t = torch.tensor([elapsed, kernel_ms], dtype=torch.float64, device="cuda")
         all_reduce(dist, t, op=dist.ReduceOp.MAX)
@@ -659,6 +700,9 @@ def main():
                          "by LPT, strong scaling) rides the same line as the `genome` object.  genome = that leg alone as the top-level line.")
     ap.add_argument("--weak", action="store_true", help="(accepted for compatibility: --workload count is weak scaling at every N)")
     ap.add_argument("--no-genome", action="store_true", help="skip the configs[3] leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy: "
+                    "total (the step's overlap total), counts (the per-query counts at the positions in counts_index: all of them, or "
+                    "a fixed seeded sample of %d when there are more); --workload genome: chrom_totals instead of total" % DUMP_SAMPLE)
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -704,8 +748,11 @@ def main():
     # The top-level line is configs[1] at every N (a 1 -> 8 curve must compare one workload with itself).
     workload = "count" if args.workload == "auto" else args.workload
     if workload == "genome":
-        g = bench_genome(torch, dist, rank, world, args.steps, args.warmup, args.targets, args.queries)
+        dump = {} if args.dump_outputs else None
+        g = bench_genome(torch, dist, rank, world, args.steps, args.warmup, args.targets, args.queries, dump=dump)
         if rank == 0:
+            if dump:
+                write_dump(args.dump_outputs, dump)
             name = _ffi.C.create_string_buffer(128)
             _ffi.call("bxmi_device_info", local_rank, name, 128, None, None)
             total_q = sum(synth.cfg4_sizes(args.queries).values())
@@ -802,6 +849,11 @@ def main():
         all_reduce(dist, t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in events]))
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs, before the self-check below reuses `counts` (rank 0's queries with --gpus N)
+        idx = dump_index(nq)
+        write_dump(args.dump_outputs, dict(total=totals[args.warmup + args.steps - 1:args.warmup + args.steps].cpu().numpy().astype(np.float64),
+                                           counts=dump_counts(counts, idx), counts_index=idx.astype(np.float64)))
 
     # ---- self-check of what was just measured --------------------------------
     total.zero_()

@@ -672,6 +672,9 @@ static int bits_need(bxmi_bits *h, int64_t upto_bits /* exclusive; BITS_ALL = th
     if (h->cap_words) e = hipDeviceSynchronize();
     if (e == hipSuccess && h->cap_words) e = hipMemcpy(np, h->words.p, (size_t)h->cap_words * 8, hipMemcpyDeviceToDevice);
     if (e == hipSuccess) e = hipMemset(static_cast<char *>(np) + (size_t)h->cap_words * 8, 0, bytes - (size_t)h->cap_words * 8);
+    // hipMemset may return before the fill has landed, and the null stream does not order the set's non-blocking stream:
+    // without this wait a kernel queued right after (bits_point) can write its bit before the zeros overwrite it
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) {
         (void)hipFree(np);
         return fail(BXMI_EHIP, "bits_need: %s", hipGetErrorString(e));
@@ -712,6 +715,7 @@ extern "C" int bxmi_bits_create(int64_t size, int64_t granularity, bxmi_bits_t *
     h->nwords = (div_up(h->total_bits, 64) + 1) & ~1ll;
     int rc = h->tags.reserve((size_t)tag_count + 64);  // the words come with the first bit (bits_need)
     if (rc == BXMI_OK && hipMemset(h->tags.p, 0, h->tags.cap) != hipSuccess) rc = fail(BXMI_EHIP, "hipMemset failed");
+    if (rc == BXMI_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(BXMI_EHIP, "hipStreamSynchronize failed");  // (see bits_need)
     if (rc != BXMI_OK) {
         delete h;
         return rc;

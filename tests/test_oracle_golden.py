@@ -4,8 +4,8 @@ Pins the CPU oracle (oracle/*.c) to the reference:
   * the known answers of the reference's own tests
     (lib/bx/intervals/intersection_tests.py, lib/bx/bitset_tests.py,
      doctests intersection.pyx:335-376),
-  * op-for-op equality with oracle/_ref (the reference's C compiled in place),
-    when that library is present.
+  * op-for-op equality with the reference's C compiled in place (oracle/_ref),
+    through the observations it recorded (tests/golden/ref_c.json).
 CPU only.
 """
 import hashlib
@@ -270,40 +270,25 @@ def test_reference_known_answers_bitset():
     assert z.unpack().tolist() == [0 if 20 <= i < 60 else 1 for i in range(100)]
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
+def _ref_c_golden():
+    import json
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_c.json")) as f:
+        return json.load(f)
+
+
 def test_restatement_equals_compiled_reference_c():
-    """Random differential run: our binbits.c vs the reference's C files compiled in place."""
-    rng = np.random.default_rng(77)
-    for size, gran in ((100, 1), (997, 7), (5000, 64), (70000, 1024), (1 << 20, 1024), (12345, 10)):
-        mine = [O.OracleBinnedBitSet(size, gran) for _ in range(2)]
-        ref = [O.RefBinnedBitSet(size, gran) for _ in range(2)]
-        assert (mine[0].bin_size, mine[0].nbins) == (ref[0].bin_size, ref[0].nbins)
-        for step in range(400):
-            w = int(rng.integers(0, 2))
-            op = int(rng.integers(0, 10))
-            s = int(rng.integers(0, size))
-            n = int(rng.integers(0, min(size - s, max(2, size // 4)) + 1))
-            if op <= 2:
-                mine[w].set_range(s, n), ref[w].set_range(s, n)
-            elif op == 3:
-                assert mine[w].count_range(s, n) == ref[w].count_range(s, n), (size, gran, step)
-            elif op == 4:
-                assert mine[w].next_set(s) == ref[w].next_set(s), (size, gran, step)
-                assert mine[w].next_clear(s) == ref[w].next_clear(s), (size, gran, step)
-            elif op == 5:
-                mine[w].set(s), ref[w].set(s)
-                mine[1 - w].clear(s), ref[1 - w].clear(s)
-            elif op == 6 and rng.random() < 0.4:
-                mine[w].invert(), ref[w].invert()
-            elif op == 7:
-                mine[w].iand(mine[1 - w]), ref[w].iand(ref[1 - w])
-            elif op == 8:
-                mine[w].ior(mine[1 - w]), ref[w].ior(ref[1 - w])
-            else:
-                assert mine[w][s] == ref[w][s]
-        for w in range(2):
-            assert mine[w].count_range(0, size) == ref[w].count_range(0, size)
-            assert all(mine[w][p] == ref[w][p] for p in range(0, size, max(1, size // 997)))
+    """Random differential run: our binbits.c against what the reference's C files, compiled in place, observed on the same
+    seeded run (tests/golden/ref_c.json, oracle/gen_golden_ref_c.py)."""
+    from oracle.gen_golden_ref_c import bitset_run
+
+    want = _ref_c_golden()["bitsets"]
+    got = bitset_run(O.OracleBinnedBitSet)
+    assert len(got) == len(want) == 6
+    for g, w in zip(got, want):
+        assert (g["size"], g["gran"]) == (w["size"], w["gran"])
+        first = next((k for k, (a, b) in enumerate(zip(g["obs"], w["obs"])) if a != b), None)
+        assert first is None and len(g["obs"]) == len(w["obs"]), (g["size"], g["gran"], first)
 
 
 # ------------------------------------------------------------------ ClusterTree (SURVEY 8f rank 4) --
@@ -344,21 +329,15 @@ def test_reference_known_answers_cluster():
     assert regions(pairs) == [(0, upto * 3, list(range(upto + 1)))]
 
 
-@pytest.mark.skipif(not O.have_ref_cluster(), reason="oracle/_ref/libcluster_ref.so is built only where /root/reference exists")
 def test_cluster_restatement_equals_compiled_reference_c():
-    """oracle/cluster.c vs the reference's own src/cluster.c compiled in place, inserted in random orders."""
-    rng = np.random.default_rng(9)
-    for trial in range(400):
-        n = int(rng.integers(1, 80))
-        md, mn = int(rng.integers(0, 25)), int(rng.integers(0, 4))
-        span = int(rng.choice([40, 300, 10**6]))
-        s = rng.integers(-span, span, size=n)
-        e = s + rng.integers(0, 30, size=n)
-        ids = rng.integers(-50, 5000, size=n)
-        order = rng.permutation(n)
-        want = O.ref_cluster_regions([(int(s[i]), int(e[i]), int(ids[i])) for i in order], md, mn)
-        got = O.cluster_regions(s, e, ids, md, mn)
-        assert got == want, (trial, md, mn, n)
+    """oracle/cluster.c vs the reference's own src/cluster.c compiled in place, inserted in random orders (its regions
+    recorded in tests/golden/ref_c.json by oracle/gen_golden_ref_c.py)."""
+    from oracle.gen_golden_ref_c import as_lists, cluster_trials
+
+    want = _ref_c_golden()["clusters"]
+    assert len(want) == 400
+    for trial, ((s, e, ids, order, md, mn), w) in enumerate(zip(cluster_trials(), want)):
+        assert as_lists(O.cluster_regions(s, e, ids, md, mn)) == w, (trial, md, mn, len(s))
 
 
 def test_restatement_is_clean_under_asan_and_ubsan():
@@ -402,15 +381,13 @@ def test_cluster_distance_minus_one_vectors():
         O.cluster_regions([0, 5], [3, 5], None, -1)  # a zero-length interval
     with pytest.raises(ValueError):
         O.cluster_regions([0, 5], [3, 9], None, -2)
-    if O.have_ref_cluster():  # the restatement against the reference's C, random insertion orders
-        rng = np.random.default_rng(77)
-        for _ in range(40):
-            n = int(rng.integers(2, 150))
-            s = rng.integers(0, 400, size=n)
-            e = s + rng.integers(1, 40, size=n)
-            tri = [(int(a), int(b), i) for i, (a, b) in enumerate(zip(s, e))]
-            ref = sorted([a, b, sorted(m)] for a, b, m in O.ref_cluster_regions([tri[i] for i in rng.permutation(n)], -1, 0))
-            assert sorted([a, b, sorted(m)] for a, b, m in O.cluster_regions(s, e, None, -1, 0)) == ref
+    # the restatement against the reference's C, random insertion orders (tests/golden/ref_c.json)
+    from oracle.gen_golden_ref_c import as_lists, minus_one_trials
+
+    want = _ref_c_golden()["cluster_minus_one"]
+    assert len(want) == 40
+    for k, ((s, e, _), ref) in enumerate(zip(minus_one_trials(), want)):
+        assert sorted([a, b, sorted(m)] for a, b, m in as_lists(O.cluster_regions(s, e, None, -1, 0))) == ref, k
 
 
 def test_negative_cluster_distance_has_no_answer_to_reproduce():
@@ -424,12 +401,17 @@ def test_negative_cluster_distance_has_no_answer_to_reproduce():
 
     from oracle import oracle as O
 
-    if not O.have_ref_cluster():
-        pytest.skip("oracle/_ref/libcluster_ref.so not built")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "oracle", "cluster_negative_distance.py")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "negative distances depend on order / priorities: True" in r.stdout
-    row = [l for l in r.stdout.splitlines() if l.split()[:1] == ["-1"]][0]
+    with open(os.path.join(root, "tests", "golden", "cluster_negative_distance.txt")) as f:
+        table = f.read()
+    if O.have_ref_cluster():  # the experiment itself, where the reference's C is built: it must print the committed table
+        r = subprocess.run([sys.executable, os.path.join(root, "oracle", "cluster_negative_distance.py")], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert r.stdout == table
+    assert "negative distances depend on order / priorities: True" in table
+    row = [l for l in table.splitlines() if l.split()[:1] == ["-1"]][0]
     assert "| 0 of 50 / 0 of 50 / 50 of 50" in row, row  # positive lengths: one answer; with zero-length intervals: none
-    assert all("0 of 50 / 0 of 50 / 0 of 50" not in l for l in r.stdout.splitlines() if l.split()[:1] in (["-2"], ["-3"], ["-4"]))
+    assert all("0 of 50 / 0 of 50 / 0 of 50" not in l for l in table.splitlines() if l.split()[:1] in (["-2"], ["-3"], ["-4"]))
+    for md in (-2, -3, -20):
+        with pytest.raises(ValueError):
+            O.cluster_regions([0, 5], [3, 9], None, md)

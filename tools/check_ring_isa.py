@@ -13,6 +13,7 @@ allocator that a destination register is still being written.  For every such ke
 usage: python tools/check_ring_isa.py [file.s]   (without a file: compiles intervals.hip to assembly first, ~40 s)"""
 import os
 import re
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -139,10 +140,12 @@ def check_kernel(name, lines):
 
 
 def main():
+    tmp = None
     if len(sys.argv) > 1:
         path = sys.argv[1]
     else:
-        path = os.path.join(tempfile.gettempdir(), "bxmi_intervals.s")
+        tmp = tempfile.mkdtemp(prefix="bxmi_isa_")  # (private: several users or runs may share the temp dir)
+        path = os.path.join(tmp, "intervals.s")
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
                                "-I" + os.path.join(ROOT, "include"), os.path.join(CSRC, "intervals.hip"), "-o", path], stderr=subprocess.DEVNULL)
     kernels, cur = {}, None
@@ -155,6 +158,8 @@ def main():
             cur = None
         elif cur:
             kernels[cur].append((no, line.rstrip("\n")))
+    if tmp:
+        shutil.rmtree(tmp)
     failed = 0
     for name, lines in kernels.items():
         if "bw_search_kernel" in name:  # the persistent walk: bw_search_kernel<W8, DEPTH>
