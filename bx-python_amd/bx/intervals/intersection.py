@@ -347,6 +347,61 @@ class IntervalTree:
         self._core._flush()
         return self._core.index.find(starts, ends)
 
+    def _neighbors_many(self, positions, num_intervals, max_dist, direction):
+        """before (direction < 0) / after (direction > 0) for every position: one batched call.  Positions are C ints whose
+        position -/+ 1 is one too (the per-call methods raise the same OverflowError); the "sort, keep n" rule orders by
+        the stored start / end, which are the payloads' own for Interval objects."""
+        n, max_dist = _cint(num_intervals), _cint(max_dist)
+        pos = _ffi_as_i32(positions)
+        if pos.ndim != 1:
+            raise ValueError("positions must be a 1-d sequence")
+        if self._core is None:
+            return [[] for _ in range(len(pos))]
+        edge = -(2**31) if direction < 0 else 2**31 - 1
+        if len(pos) and np.any(pos == edge):
+            raise OverflowError("value too large to convert to int")
+        core = self._core
+        if not 1 <= n <= IntervalIndex.NEIGHBORS_MAX_K:  # the per-call path serves any n
+            one = core.left if direction < 0 else core.right
+            return [one(int(p), n, max_dist) for p in pos.tolist()]
+        core._flush()
+        if direction < 0:
+            hits, cnt = core.index.before_batch(pos, n, max_dist)
+        else:
+            hits, cnt = core.index.after_batch(pos, n, max_dist)
+        vals = core.values
+        return [[vals[i] for i in row[:c]] for row, c in zip(hits.tolist(), cnt.tolist())]
+
+    def before_many(self, positions, num_intervals=1, max_dist=2500):
+        """[before(p, num_intervals, max_dist) for p in positions], answered by one batched device call."""
+        return self._neighbors_many(positions, num_intervals, max_dist, -1)
+
+    def after_many(self, positions, num_intervals=1, max_dist=2500):
+        """[after(p, num_intervals, max_dist) for p in positions], answered by one batched device call."""
+        return self._neighbors_many(positions, num_intervals, max_dist, +1)
+
+    def _stranded_many(self, intervals, num_intervals, max_dist, upstream):
+        intervals = list(intervals)
+        minus = np.array([iv.strand == -1 or iv.strand == "-" for iv in intervals], dtype=bool)
+        use_after = minus if upstream else ~minus
+        out = [None] * len(intervals)
+        ia, ib = np.flatnonzero(use_after), np.flatnonzero(~use_after)
+        res_a = self.after_many([intervals[i].end for i in ia], num_intervals, max_dist)
+        res_b = self.before_many([intervals[i].start for i in ib], num_intervals, max_dist)
+        for i, r in zip(ia.tolist(), res_a):
+            out[i] = r
+        for i, r in zip(ib.tolist(), res_b):
+            out[i] = r
+        return out
+
+    def upstream_many(self, intervals, num_intervals=1, max_dist=2500):
+        """[upstream_of_interval(iv, num_intervals, max_dist) for iv in intervals]: two batched calls, one per strand rule."""
+        return self._stranded_many(intervals, num_intervals, max_dist, True)
+
+    def downstream_many(self, intervals, num_intervals=1, max_dist=2500):
+        """[downstream_of_interval(iv, num_intervals, max_dist) for iv in intervals]: two batched calls."""
+        return self._stranded_many(intervals, num_intervals, max_dist, False)
+
     @property
     def values(self):
         return self._c().values

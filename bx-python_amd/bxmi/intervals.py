@@ -228,6 +228,36 @@ class IntervalIndex:
             cap = n_out.value
         raise _ffi.BxmiError(_ffi.ERANGE, "neighbors: buffer still too small")
 
+    NEIGHBORS_MAX_K = 64  # the cap of bxmi_ivl_neighbors_batch on k
+
+    def _neighbors_batch(self, positions, k, max_dist, direction):
+        self._ready()
+        pos = as_i32(positions)
+        if pos.ndim != 1:
+            raise ValueError("positions must be a 1-d array")
+        nq = len(pos)
+        hits = np.empty((nq, max(int(k), 0)), dtype=np.int32)  # (k outside 1..64: the library says BXMI_EINVAL)
+        n = np.empty(nq, dtype=np.int32)
+        call("bxmi_ivl_neighbors_batch", self._h, ptr(pos), nq, int(k), int(max_dist), int(direction), ptr(hits), ptr(n), None)
+        return hits, n
+
+    def before_batch(self, positions, k=1, max_dist=2500):
+        """IntervalNode.left(p, k, max_dist) for every position at once (intersection.pyx:232-245): -> (hits int32[nq, k],
+        n int32[nq]); row i holds n[i] insertion indices in the reference's order, then -1.  1 <= k <= 64."""
+        return self._neighbors_batch(positions, k, max_dist, -1)
+
+    def after_batch(self, positions, k=1, max_dist=2500):
+        """IntervalNode.right(p, k, max_dist) for every position at once (intersection.pyx:247-260); same layout as
+        before_batch."""
+        return self._neighbors_batch(positions, k, max_dist, +1)
+
+    def neighbors_batch_dev(self, pos_ptr, nq, k, max_dist, direction, hits_ptr, n_ptr, n_cand_ptr=None, stream=None):
+        """Device-pointer form of before_batch (direction < 0) / after_batch (direction > 0): int32 positions[nq] in,
+        int32 hits[nq, k], int32 n[nq] and optionally int64 candidate counts[nq] out; stream-ordered, no host sync."""
+        self._ready()
+        call("bxmi_ivl_neighbors_batch_dev", self._h, pos_ptr, int(nq), int(k), int(max_dist), int(direction), hits_ptr, n_ptr,
+             n_cand_ptr, stream)
+
     def clusters(self, max_dist, ids=None):
         """ClusterTree's grouping (cluster.pyx:57-121): intervals chained by gaps <= max_dist.
         -> (starts int32[c], ends int32[c], offsets int64[c+1], members int32[n]); members of a cluster are ids in

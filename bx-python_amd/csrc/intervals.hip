@@ -47,6 +47,7 @@
 #include "count_dense.hpp"
 #include "find_sorted.hpp"
 #include "find_direct.hpp"
+#include "find_neighbors.hpp"
 #include "cluster.hpp"
 
 namespace bxmi {
@@ -2200,5 +2201,87 @@ extern "C" int bxmi_ivl_neighbors(bxmi_ivl_t *h, int32_t position, int32_t max_d
     *n_out = (int64_t)cnt;
     int64_t ncopy = (int64_t)cnt < cap ? (int64_t)cnt : cap;
     if (ncopy > 0) BXMI_HIP(hipMemcpy(out, h->q_hits.p, (size_t)ncopy * 4, hipMemcpyDeviceToHost));
+    return BXMI_OK;
+}
+
+// ---- batched before()/after() (find_neighbors.hpp) ----
+extern "C" int bxmi_ivl_neighbors_batch_dev(bxmi_ivl_t *h, const int32_t *pos, int64_t nq, int32_t k, int32_t max_dist, int dir,
+                                            int32_t *out, int32_t *n_out, int64_t *n_cand, void *stream)
+{
+    BXMI_TRY(need_sealed(h, "bxmi_ivl_neighbors_batch_dev"));
+    if (nq < 0 || dir == 0 || (nq > 0 && (!pos || !out || !n_out)))
+        return fail(BXMI_EINVAL, "bxmi_ivl_neighbors_batch_dev: bad arguments");
+    if (k < 1 || k > NB_MAX_K)
+        return fail(BXMI_EINVAL, "bxmi_ivl_neighbors_batch_dev: k=%d outside 1..%d (larger k: bxmi_ivl_neighbors per position)", (int)k,
+                    NB_MAX_K);
+    if (nq > INT_MAX) return fail(BXMI_EINVAL, "bxmi_ivl_neighbors_batch_dev: nq=%lld above 2^31-1", (long long)nq);
+    if (nq == 0) return BXMI_OK;
+    hipStream_t st = as_stream(stream);
+    if (h->n == 0) {  // no candidates anywhere
+        BXMI_HIP(hipMemsetAsync(out, 0xff, (size_t)nq * k * 4, st));
+        BXMI_HIP(hipMemsetAsync(n_out, 0, (size_t)nq * 4, st));
+        if (n_cand) BXMI_HIP(hipMemsetAsync(n_cand, 0, (size_t)nq * 8, st));
+        return BXMI_OK;
+    }
+    IndexDev ix = index_dev(h);
+    TreeDev S = h->treeS.dev;
+    int grid = device_props().cus * 2;
+    int64_t need = div_up(nq, (int64_t)(FIND_THREADS / 8) * FIND_Q);
+    if (need < grid) grid = (int)need;
+    if (dir > 0) {
+        size_t lds_bytes = (size_t)S.lds_ints * 4;
+        BXMI_TRY(allow_big_lds(nb_after_kernel<true>, lds_bytes));
+        hipLaunchKernelGGL(nb_after_kernel<true>, dim3(grid), dim3(FIND_THREADS), lds_bytes, st, S, ix, pos, nq, (int)k, (int)max_dist, out,
+                           n_out, n_cand);
+        BXMI_LAUNCH_CHECK();
+        return BXMI_OK;
+    }
+    TreeDev P = h->treeP.dev;
+    BXMI_TRY(h->q_lo.reserve((size_t)nq * 8));
+    BXMI_TRY(h->q_hi.reserve((size_t)(nq + 1) * 4));
+    int2 *win = h->q_lo.as<int2>();
+    int32_t *big = h->q_hi.as<int32_t>();
+    BXMI_HIP(hipMemsetAsync(big, 0, 4, st));
+    size_t lds_bytes = (size_t)(S.lds_ints + P.lds_ints) * 4;
+    BXMI_TRY(allow_big_lds(nb_before_window_kernel<true>, lds_bytes));
+    hipLaunchKernelGGL(nb_before_window_kernel<true>, dim3(grid), dim3(FIND_THREADS), lds_bytes, st, S, P, ix, pos, nq, (int)max_dist, win,
+                       big);
+    BXMI_LAUNCH_CHECK();
+    int wgrid = device_props().cus * 8;
+    int64_t wneed = div_up(nq, (int64_t)(NB_WAVE_THREADS / 64));
+    if (wneed < wgrid) wgrid = (int)wneed;
+    hipLaunchKernelGGL(nb_before_wave_kernel, dim3(wgrid), dim3(NB_WAVE_THREADS), 0, st, ix, pos, nq, (int)k, (int)max_dist, win, out,
+                       n_out, n_cand);
+    BXMI_LAUNCH_CHECK();
+    // the long windows: a fixed grid that loops over however many pass 1 listed (no host round trip)
+    hipLaunchKernelGGL(nb_before_block_kernel, dim3(device_props().cus * 2), dim3(NB_BLOCK_THREADS), 0, st, ix, pos, (int)k, (int)max_dist,
+                       win, big, out, n_out, n_cand);
+    BXMI_LAUNCH_CHECK();
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_ivl_neighbors_batch(bxmi_ivl_t *h, const int32_t *pos, int64_t nq, int32_t k, int32_t max_dist, int dir, int32_t *out,
+                                        int32_t *n_out, int64_t *n_cand)
+{
+    BXMI_TRY(need_sealed(h, "bxmi_ivl_neighbors_batch"));
+    if (nq < 0 || dir == 0 || (nq > 0 && (!pos || !out || !n_out))) return fail(BXMI_EINVAL, "bxmi_ivl_neighbors_batch: bad arguments");
+    if (k < 1 || k > NB_MAX_K)
+        return fail(BXMI_EINVAL, "bxmi_ivl_neighbors_batch: k=%d outside 1..%d (larger k: bxmi_ivl_neighbors per position)", (int)k, NB_MAX_K);
+    if (nq > INT_MAX) return fail(BXMI_EINVAL, "bxmi_ivl_neighbors_batch: nq=%lld above 2^31-1", (long long)nq);
+    if (nq == 0) return BXMI_OK;
+    BXMI_TRY(ivl_stream(h));
+    hipStream_t st = h->stream;
+    BXMI_TRY(h->q_s.reserve((size_t)nq * 4));
+    BXMI_TRY(h->q_hits.reserve((size_t)nq * k * 4));
+    BXMI_TRY(h->q_cnt.reserve((size_t)nq * 4));
+    if (n_cand) BXMI_TRY(h->q_off.reserve((size_t)nq * 8));
+    int32_t *d_pos = h->q_s.as<int32_t>(), *d_out = h->q_hits.as<int32_t>(), *d_n = h->q_cnt.as<int32_t>();
+    int64_t *d_cand = n_cand ? h->q_off.as<int64_t>() : nullptr;
+    BXMI_HIP(hipMemcpyAsync(d_pos, pos, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    BXMI_TRY(bxmi_ivl_neighbors_batch_dev(h, d_pos, nq, k, max_dist, dir, d_out, d_n, d_cand, st));
+    BXMI_HIP(hipMemcpyAsync(out, d_out, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+    BXMI_HIP(hipMemcpyAsync(n_out, d_n, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    if (n_cand) BXMI_HIP(hipMemcpyAsync(n_cand, d_cand, (size_t)nq * 8, hipMemcpyDeviceToHost, st));
+    BXMI_HIP(hipStreamSynchronize(st));
     return BXMI_OK;
 }

@@ -205,6 +205,26 @@ int bxmi_ivl_find_one(bxmi_ivl_t *h, int32_t qs, int32_t qe, int32_t *hits, int6
 int bxmi_ivl_neighbors(bxmi_ivl_t *h, int32_t position, int32_t max_dist, int dir, int32_t *out, int64_t cap,
                        int64_t *n_out);
 
+/* before()/after() for a whole array of positions: for each i < nq, IntervalNode.left(pos[i], k, max_dist) (dir < 0) or
+ * right(pos[i], k, max_dist) (dir > 0) as insertion indices, the reference's "sort, keep n" rule included:
+ *   dir > 0: candidates 0 <= start - (pos+1) < max_dist, in in-order; their first min(k, count) (sorted by start already).
+ *   dir < 0: candidates 0 <= (pos-1) - end < max_dist, in REVERSE in-order; exactly k of them: that list as it stands
+ *            (intersection.pyx:242-245), otherwise the first min(k, count) by end descending, the later in in-order first
+ *            among equal ends (a stable sort of the reversed list).
+ * pos +/- 1 and the distance window are computed in 64 bits, as bxmi_ivl_neighbors does.  Indexes with reversed intervals
+ * take the superset rule of bxmi_ivl_neighbors for dir < 0 (same results, slower).
+ * out is an [nq, k] slab: out[i*k .. i*k + n_out[i]) holds the answer, the rest of the row is -1; n_out[i] <= k.
+ * n_cand (optional, NULL = not wanted) receives the candidate count before the cut.
+ * k outside 1..64 -> BXMI_EINVAL (larger k: bxmi_ivl_neighbors per position); nq above 2^31-1 -> BXMI_EINVAL.
+ * Host arrays, natural alignment; BLOCKS until every output is written.
+ *                                                  intersection.pyx:192-260 */
+int bxmi_ivl_neighbors_batch(bxmi_ivl_t *h, const int32_t *pos, int64_t nq, int32_t k, int32_t max_dist, int dir, int32_t *out,
+                             int32_t *n_out, int64_t *n_cand);
+/* Device variant: device pointers of natural alignment (4 bytes, 8 for n_cand).  Stream-ordered on `stream`, no host
+ * synchronisation; the handle's query scratch is in use until the work completes (one batch per handle at a time). */
+int bxmi_ivl_neighbors_batch_dev(bxmi_ivl_t *h, const int32_t *pos, int64_t nq, int32_t k, int32_t max_dist, int dir, int32_t *out,
+                                 int32_t *n_out, int64_t *n_cand, void *stream);
+
 /* ClusterTree (lib/bx/intervals/cluster.pyx:57-121, src/cluster.c:112-260): groups of intervals chained by gaps of at
  * most max_dist (>= 0).  All clusters in ascending start order: starts[c], ends[c], and members[offsets[c] ..
  * offsets[c+1]) = the member ids in ascending order, where an interval's id is ids[insertion index] (or the insertion
