@@ -1760,6 +1760,7 @@ extern "C" int bxmi_ivl_count_dev(bxmi_ivl_t *h, const int32_t *qs, const int32_
     if (nq == 0) return BXMI_OK;
     if (((uintptr_t)qs | (uintptr_t)qe | (uintptr_t)counts) & 15)
         return fail(BXMI_EINVAL, "bxmi_ivl_count_dev: query/count arrays must be 16-byte aligned");
+    if (!counts && !total_dev) return BXMI_OK;  // nothing asked for: no launch, so no path has to cope with two NULL outputs
     hipStream_t st = as_stream(stream);
     const bool partition = !h->has_reversed && h->n > 0 &&
                            (g_opt_partition == 1 || (g_opt_partition < 0 && nq >= g_opt_partition_min && h->n >= 4096));

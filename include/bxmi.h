@@ -130,13 +130,18 @@ int bxmi_ivl_count(bxmi_ivl_t *h, const int32_t *qs, const int32_t *qe, int64_t 
 /* Device variant: *total_dev (device int64) is ACCUMULATED into (zero it first).  counts = NULL: the total only -- nothing is
  * stored per query.  Stream-ordered, with ONE exception: a handle's FIRST large batch (>= ivl.bitmap_min queries) builds the
  * index's unit images and answers the order probe synchronously -- it waits for `stream` once (and cannot be captured into a
- * hipGraph); every later call only enqueues. */
+ * hipGraph); every later call only enqueues.  qs, qe and counts must be 16-byte aligned (every allocator's boundary; the passes
+ * read and write them 16 bytes per lane): a pointer that is not -- a slice of a device array at an odd offset -- returns
+ * BXMI_EINVAL before anything is written (nq == 0 returns BXMI_OK first).  counts = NULL and total_dev = NULL: BXMI_OK, nothing
+ * launched. */
 int bxmi_ivl_count_dev(bxmi_ivl_t *h, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t *counts,
                        int64_t *total_dev, void *stream);
 /* A dict of per-chromosome trees queried in one go (scripts/interval_join.py:21-28 keeps {chrom: Intersecter}; a genome-wide
  * batch asks every tree with its own chromosome's queries): exactly n calls of bxmi_ivl_count_dev -- hs[i] with
  * qs[i][0..nq[i]), counts[i] and totals_dev[i] (each optional / accumulated as there) -- but the indexes that qualify for
- * the bitmap-cell pass share ONE pass: a fixed handful of launches for the whole genome instead of one set per chromosome. */
+ * the bitmap-cell pass share ONE pass: a fixed handful of launches for the whole genome instead of one set per chromosome.
+ * The same 16-byte alignment of qs[i], qe[i] and counts[i]: one array that is not aligned refuses the whole call with
+ * BXMI_EINVAL before anything is launched. */
 int bxmi_ivl_count_multi_dev(bxmi_ivl_t *const *hs, int n, const int32_t *const *qs, const int32_t *const *qe, const int64_t *nq,
                              int32_t *const *counts, int64_t *const *totals_dev, void *stream);
 /* Which search stage of the large-batch count pass can serve this sealed index -- the slice search stage (count_slices.hpp: sorted keys staged per unit of 2^f buckets; serves sparse

@@ -8,6 +8,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+# the _dev entry point this file drives (through IntervalIndex.neighbors_batch_dev; tests/test_device_entry_points_abi.py)
+DEV_ENTRY_POINTS = ("bxmi_ivl_neighbors_batch_dev",)
+
 I32_MIN, I32_MAX = -(2**31), 2**31 - 1
 
 
