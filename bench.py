@@ -9,14 +9,21 @@ region starts.  One "step" = one pass of the count kernel over the rank's
 index and its own 100M queries (weak scaling, no data-path collective); the only
 collective is the optional int64 all-reduce of the overlap total (RCCL).
 
-The same JSON line carries
-  roofline      algorithmic bytes (12 B/query + 8 B/target per launch) / measured
-                kernel time (HIP events on the launch stream) against 8 TB/s,
+A plain run does what the headline needs and nothing else: it sets up, warms up,
+times the steps, writes --dump-outputs and prints the line, whose roofline is
+algorithmic bytes (12 B/query + 8 B/target per launch) / measured kernel time
+(HIP events around the timed steps) against 8 TB/s.  --full adds the rest to the
+same line:
+  parity        a pass after the timed steps checked against its counts, the
+                timed steps' totals and the reference treap's golden hashes,
   cpu_baseline  the oracle treap (a C port of the reference's algorithm) timed on
-                this box's host cores on a bounded sample of the same workload,
-  bitset        BASELINE's second metric (BinnedBitSet Gbp/s) on configs[2].
+                the host's cores on a bounded sample of the same workload,
+  bitset        BASELINE's second metric (BinnedBitSet Gbp/s) on configs[2],
+  and the index build, cold passes, sorted / total-only / host-pointer passes,
+  configs[3] and [4], the clustered index, per-call latency and the HBM traffic
+  quoted from profiles/pmc_latest.json; the --no-* options leave legs out of it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -434,12 +441,13 @@ def genome_golden_check(chrom, counts_np, golden):
     return hashlib.sha256(sub.tobytes()).hexdigest() == pt["counts_sha256"] and int(sub.sum(dtype=np.int64)) == pt["total"]
 
 
-def bench_genome(torch, dist, rank, world, steps, warmup, n_targets, n_queries, single_gpu_reference=True, dump=None):
+def bench_genome(torch, dist, rank, world, steps, warmup, n_targets, n_queries, single_gpu_reference=True, dump=None, full=True):
     """BASELINE configs[3]: the 24 hg19 chromosomes (synth.cfg4: 10M targets x 100M queries spread by length), one
     interval index per chromosome, chromosomes dealt to the ranks by LPT (bxmi.shard), every rank counts its own
     chromosomes, the 24 per-chromosome totals are all-reduced (int64, RCCL).  STRONG scaling: the whole job is the
     same genome whatever the number of GPUs; the time of a step is the slowest rank's.  Returns a dict (rank 0) or None.
-    `dump` (a dict) receives what the last timed step computed: the per-chromosome totals and a sample of the counts."""
+    `dump` (a dict) receives what the last timed step computed: the per-chromosome totals and a sample of the counts.
+    full=False leaves out the parity checks, the one-GPU side legs and the one-GPU reference of a multi-rank job."""
     from bxmi import shard, synth
     from bxmi.intervals import IntervalIndex
 
@@ -531,25 +539,30 @@ def bench_genome(torch, dist, rank, world, steps, warmup, n_targets, n_queries, 
         t = torch.tensor([elapsed, kernel_ms], dtype=torch.float64, device="cuda")
         all_reduce(dist, t, op=dist.ReduceOp.MAX)
         elapsed, kernel_ms = float(t[0].item()), float(t[1].item())
-    # parity on what was just measured: owner-side golden hashes, and the reduced totals against the owners' counts
-    ok_hash, ok_sum = [], []
-    own_tot = torch.zeros(len(chroms), dtype=torch.int64, device="cuda")
-    for c in mine.owned:
-        cn = mine.counts[c].cpu().numpy()
-        g = genome_golden_check(c, cn, golden)
-        if g is not None:
-            ok_hash.append(bool(g))
-        own_tot[chroms.index(c)] = int(cn.sum(dtype=np.int64))
-    if collective:
-        all_reduce(dist, own_tot)
-    same_every_step = bool((rows == own_tot.unsqueeze(0)).all().item())
-    flags = torch.tensor([int(all(ok_hash)) if ok_hash else 1, int(same_every_step), len(ok_hash)], dtype=torch.int64, device="cuda")
-    if collective:
-        red = flags.clone()
-        all_reduce(dist, red, op=dist.ReduceOp.MIN)
-        cnt = flags[2:].clone()
-        all_reduce(dist, cnt)
-        flags = torch.tensor([int(red[0]), int(red[1]), int(cnt[0])], device="cuda")
+    parity = None
+    if full:
+        # parity on what was just measured: owner-side golden hashes, and the reduced totals against the owners' counts
+        ok_hash, ok_sum = [], []
+        own_tot = torch.zeros(len(chroms), dtype=torch.int64, device="cuda")
+        for c in mine.owned:
+            cn = mine.counts[c].cpu().numpy()
+            g = genome_golden_check(c, cn, golden)
+            if g is not None:
+                ok_hash.append(bool(g))
+            own_tot[chroms.index(c)] = int(cn.sum(dtype=np.int64))
+        if collective:
+            all_reduce(dist, own_tot)
+        same_every_step = bool((rows == own_tot.unsqueeze(0)).all().item())
+        flags = torch.tensor([int(all(ok_hash)) if ok_hash else 1, int(same_every_step), len(ok_hash)], dtype=torch.int64, device="cuda")
+        if collective:
+            red = flags.clone()
+            all_reduce(dist, red, op=dist.ReduceOp.MIN)
+            cnt = flags[2:].clone()
+            all_reduce(dist, cnt)
+            flags = torch.tensor([int(red[0]), int(red[1]), int(cnt[0])], device="cuda")
+        parity = dict(golden_subsample_hashes_ok=bool(flags[0].item()), chromosomes_hashed=int(flags[2].item()),
+                      reduced_totals_equal_sum_of_owner_counts_every_step=bool(flags[1].item()),
+                      overlaps_per_step=int(own_tot.sum().item()))
     total_q = sum(qsz.values())
     value = total_q * steps / elapsed / 1e6
     out = None
@@ -564,11 +577,9 @@ def bench_genome(torch, dist, rank, world, steps, warmup, n_targets, n_queries, 
             lpt=dict(balance_max_over_mean=round(shard.balance(weights, assign), 4), speedup_bound=round(world / shard.balance(weights, assign), 3),
                      heaviest_rank_intervals=max(loads), chromosomes_per_rank=[len(p) for p in assign]),
             collective=("all_reduce(int64[24]) per step, backend %s" % dist.get_backend()) if collective else "none (one rank)",
-            parity=dict(golden_subsample_hashes_ok=bool(flags[0].item()), chromosomes_hashed=int(flags[2].item()),
-                        reduced_totals_equal_sum_of_owner_counts_every_step=bool(flags[1].item()),
-                        overlaps_per_step=int(own_tot.sum().item())),
+            parity=parity,
             build_s=round(mine.index_s, 4), data_generation_and_build_s=round(build_s, 2))
-    if not collective and rank == 0 and not os.environ.get("BENCH_PER_CHROM"):
+    if full and not collective and rank == 0 and not os.environ.get("BENCH_PER_CHROM"):
         # side legs on one GPU (never `value`): (1) the caller wants the per-chromosome TOTALS only (configs[3]'s "all-reduce on counts"
         # shape, scripts/bed_count_overlapping.py consumes len(find()) only): no count is stored per query; (2) every chromosome's
         # queries sorted by start, as a sorted BED file brings them: the walk on cell images answers them as they lie
@@ -602,7 +613,7 @@ def bench_genome(torch, dist, rank, world, steps, warmup, n_targets, n_queries, 
                                      totals_equal_shuffled_pass=bool((rows3 == own_tot.unsqueeze(0)).all().item()) and sorted_counts_ok,
                                      note="every chromosome's queries sorted by start; one bxmi_ivl_count_multi_dev call per step, answered by the sorted walk over segments")
     # the same genome on ONE GPU, in the same run (rank 0 alone; the others wait): what the speed-up is measured against
-    if collective and single_gpu_reference:
+    if full and collective and single_gpu_reference:
         if rank == 0:
             rest = Shard([c for c in chroms if c not in assign[0]])
             rest.owned = chroms
@@ -700,6 +711,9 @@ def main():
                          "by LPT, strong scaling) rides the same line as the `genome` object.  genome = that leg alone as the top-level line.")
     ap.add_argument("--weak", action="store_true", help="(accepted for compatibility: --workload count is weak scaling at every N)")
     ap.add_argument("--no-genome", action="store_true", help="skip the configs[3] leg")
+    ap.add_argument("--full", action="store_true", help="also run every side measurement and check (parity, CPU baseline, index build, "
+                    "cold passes, sorted / total-only / host-pointer passes, bitsets, find, genome, clustered, per-call latency, quoted HBM "
+                    "traffic) into the same line; without it the run does the headline steps alone")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy: "
                     "total (the step's overlap total), counts (the per-query counts at the positions in counts_index: all of them, or "
                     "a fixed seeded sample of %d when there are more); --workload genome: chrom_totals instead of total" % DUMP_SAMPLE)
@@ -749,7 +763,7 @@ def main():
     workload = "count" if args.workload == "auto" else args.workload
     if workload == "genome":
         dump = {} if args.dump_outputs else None
-        g = bench_genome(torch, dist, rank, world, args.steps, args.warmup, args.targets, args.queries, dump=dump)
+        g = bench_genome(torch, dist, rank, world, args.steps, args.warmup, args.targets, args.queries, dump=dump, full=args.full)
         if rank == 0:
             if dump:
                 write_dump(args.dump_outputs, dump)
@@ -786,7 +800,7 @@ def main():
 
     (ts, te), _ = synth.cfg2(args.targets, 1)
     baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         baseline = CpuBaseline(ts, te)
         baseline.start()
 
@@ -797,18 +811,20 @@ def main():
     ix.seal()
     torch.cuda.synchronize()
     first_build_s = time.perf_counter() - t0  # the process's first index: library load, code objects, nothing warm
-    # a second index over the same targets, timed in its parts: the 80 MB host copy + upload, and the seal itself (two
-    # radix sorts, prefix max, three search trees)
-    t0 = time.perf_counter()
-    ix2 = IntervalIndex()
-    ix2.append(ts, te)
-    t1 = time.perf_counter()
-    ix2.seal()
-    _ffi.call("bxmi_synchronize", None)
-    build_s = time.perf_counter() - t0
-    build_parts = dict(first_index_of_the_process_s=round(first_build_s, 4), append_from_host_arrays_s=round(t1 - t0, 4),
-                       seal_s=round(build_s - (t1 - t0), 4))
-    ix2.close()
+    build_s = build_parts = None
+    if args.full:
+        # a second index over the same targets, timed in its parts: the 80 MB host copy + upload, and the seal itself (two
+        # radix sorts, prefix max, three search trees)
+        t0 = time.perf_counter()
+        ix2 = IntervalIndex()
+        ix2.append(ts, te)
+        t1 = time.perf_counter()
+        ix2.seal()
+        _ffi.call("bxmi_synchronize", None)
+        build_s = time.perf_counter() - t0
+        build_parts = dict(first_index_of_the_process_s=round(first_build_s, 4), append_from_host_arrays_s=round(t1 - t0, 4),
+                           seal_s=round(build_s - (t1 - t0), 4))
+        ix2.close()
     qs_h, qe_h = synth.uniform_intervals(args.queries, 202 + 1000 * rank)
     qs = torch.from_numpy(qs_h).cuda()
     qe = torch.from_numpy(qe_h).cuda()
@@ -856,36 +872,38 @@ def main():
                                            counts=dump_counts(counts, idx), counts_index=idx.astype(np.float64)))
 
     # ---- self-check of what was just measured --------------------------------
-    total.zero_()
-    ix.count_dev(qs.data_ptr(), qe.data_ptr(), nq, counts.data_ptr(), total.data_ptr(), stream)
-    torch.cuda.synchronize()
-    local_total = int(total.item())
-    sum_ok = local_total == int(counts.sum(dtype=torch.int64).item())
-    parity = "sum-of-counts == total: %s" % sum_ok
-    if world == 1:
-        parity += "; every timed step produced that total: %s" % bool((totals[: args.steps + args.warmup] == local_total).all().item())
-    job_total = local_total
-    if world > 1:
-        # every rank's own total, summed by the collective: what each timed step's all-reduced slot must hold
-        lt = torch.tensor([local_total], dtype=torch.int64, device="cuda")
-        all_reduce(dist, lt)
-        job_total = int(lt.item())
-        if args.allreduce_total:
-            parity += "; every timed step's all-reduced total == sum of the ranks' totals: %s" % bool(
-                (totals[: args.steps + args.warmup] == job_total).all().item())
     golden_path = os.path.join(ROOT, "tests", "golden", "scale.json")
-    if rank == 0 and args.queries == 100_000_000 and args.targets == 10_000_000 and os.path.exists(golden_path):
-        pt = json.load(open(golden_path))["points"].get("10M x 1M (cfg2 subsample)")
-        if pt:
-            sub = counts[:: pt["stride"]].contiguous().cpu().numpy()
-            ok = hashlib.sha256(sub.tobytes()).hexdigest() == pt["counts_sha256"] and int(sub.sum(dtype=np.int64)) == pt["total"]
-            parity += "; sha256 of the 1M-query subsample == reference treap's: %s" % ok
+    parity = local_total = job_total = None
+    if args.full:
+        total.zero_()
+        ix.count_dev(qs.data_ptr(), qe.data_ptr(), nq, counts.data_ptr(), total.data_ptr(), stream)
+        torch.cuda.synchronize()
+        local_total = int(total.item())
+        sum_ok = local_total == int(counts.sum(dtype=torch.int64).item())
+        parity = "sum-of-counts == total: %s" % sum_ok
+        if world == 1:
+            parity += "; every timed step produced that total: %s" % bool((totals[: args.steps + args.warmup] == local_total).all().item())
+        job_total = local_total
+        if world > 1:
+            # every rank's own total, summed by the collective: what each timed step's all-reduced slot must hold
+            lt = torch.tensor([local_total], dtype=torch.int64, device="cuda")
+            all_reduce(dist, lt)
+            job_total = int(lt.item())
+            if args.allreduce_total:
+                parity += "; every timed step's all-reduced total == sum of the ranks' totals: %s" % bool(
+                    (totals[: args.steps + args.warmup] == job_total).all().item())
+        if rank == 0 and args.queries == 100_000_000 and args.targets == 10_000_000 and os.path.exists(golden_path):
+            pt = json.load(open(golden_path))["points"].get("10M x 1M (cfg2 subsample)")
+            if pt:
+                sub = counts[:: pt["stride"]].contiguous().cpu().numpy()
+                ok = hashlib.sha256(sub.tobytes()).hexdigest() == pt["counts_sha256"] and int(sub.sum(dtype=np.int64)) == pt["total"]
+                parity += "; sha256 of the 1M-query subsample == reference treap's: %s" % ok
 
     # what a caller's FIRST passes cost (the headline is a steady-state number).  A fresh handle over the same
     # targets: pass 1 builds the index's unit images, allocates the pass's scratch and asks the order probe synchronously
     # (all once per handle); pass 2 is what every later pass costs unless the batch looks sorted.
     cold = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         ixc = IntervalIndex()
         ixc.append(ts, te)
         ixc.seal()
@@ -906,7 +924,7 @@ def main():
     # the caller wants the TOTAL only (counts = NULL; scripts/bed_count_overlapping.py consumes len(find()) only): the same pass, its
     # un-permute kernel sums without storing a count per query.  Reported beside the headline, never `value`.
     total_only = None
-    if rank == 0 and world == 1 and not args.no_sorted:  # (a side leg like `sorted_queries`: tools/profile.sh leaves both out)
+    if args.full and rank == 0 and world == 1 and not args.no_sorted:  # (a side leg like `sorted_queries`: tools/profile.sh leaves both out)
         tt = torch.zeros(8, dtype=torch.int64, device="cuda")
         ix.count_dev(qs.data_ptr(), qe.data_ptr(), nq, None, tt[0:].data_ptr(), stream)
         torch.cuda.synchronize()
@@ -920,7 +938,7 @@ def main():
 
     # the same batch through the HOST-pointer entry point (pageable numpy buffers over PCIe): reported, never `value`
     pcie = None
-    if rank == 0 and world == 1 and not args.no_pcie:
+    if args.full and rank == 0 and world == 1 and not args.no_pcie:
         ix.count(qs_h[:1 << 20], qe_h[:1 << 20])
         t1 = time.perf_counter()
         hc, ht = ix.count(qs_h, qe_h)  # the handle's first batch of this size: its 1.2 GB of device staging are allocated here
@@ -938,7 +956,7 @@ def main():
     # the same queries sorted by start (how BED files usually arrive): libbxmi notices on the device and answers in one
     # pass without bucketing.  Reported beside the headline, never `value` (BASELINE.json asks for generated order).
     sorted_q = None
-    if rank == 0 and world == 1 and not args.no_sorted:
+    if args.full and rank == 0 and world == 1 and not args.no_sorted:
         order = torch.argsort(qs, stable=True)
         sqs, sqe = qs[order].contiguous(), qe[order].contiguous()
         del order
@@ -979,7 +997,7 @@ def main():
     # configs[3] on all the ranks of this job (strong scaling, chromosomes dealt by LPT, totals all-reduced): a collective
     # leg, so every rank walks through it; rank 0 keeps the result for the line
     genome_leg = None
-    if world > 1 and not args.no_genome:
+    if args.full and world > 1 and not args.no_genome:
         del qs, qe, counts
         torch.cuda.empty_cache()
         # (no try / except here: a rank that fails would hang the others in the collective -- let it surface)
@@ -1032,7 +1050,7 @@ def main():
             "kernel_ms": round(kernel_ms, 4), "algorithmic_bytes_per_launch": alg_bytes,
             "timed_with": "HIP events on the launch stream around every bxmi_ivl_count_dev call of the timed region",
         },
-        "index_build_s": round(build_s, 4),
+        "index_build_s": round(build_s, 4) if build_s is not None else None,
         "index_build_parts": build_parts,
         "pcie_inclusive": pcie,
         "sorted_queries": sorted_q,
@@ -1044,22 +1062,24 @@ def main():
     }
     # HBM bytes per launch from the PMC counters: taken in their own rocprofv3 runs (tools/profile.sh), so this run can only
     # quote them -- and only if they were taken on THIS code (the file carries the hashes of bench.py and the kernel sources)
-    pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
-    line["roofline"]["traffic_source"] = "none: profiles/pmc_latest.json missing"
-    if os.path.exists(pmc):
-        try:
-            doc = json.load(open(pmc))
-            have, want = doc.get("stamps", {}), source_stamps()
-            if all(have.get(k) == want[k] for k in want):
-                line["roofline"]["traffic"] = doc.get("count_pass", {}).get("hbm_bytes_per_launch")
-                line["roofline"]["traffic_source"] = ("profiles/pmc_latest.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `%s` on %s, "
-                                                      "bench_sha16=%s kernel_sha16=%s head=%s" % (have.get("command"), have.get("date"), have.get("bench_sha16"),
-                                                                                                  have.get("kernel_sha16"), have.get("head")))
-            else:
-                line["roofline"]["traffic_source"] = "stale: profiles/pmc_latest.json was taken on other code (%s), not quoted" % ", ".join(
-                    "%s %s != %s" % (k, have.get(k), want[k]) for k in want if have.get(k) != want[k])
-        except Exception as ex:
-            line["roofline"]["traffic_source"] = "unreadable: %r" % ex
+    line["roofline"]["traffic_source"] = "not quoted: --full quotes profiles/pmc_latest.json"
+    if args.full:
+        pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
+        line["roofline"]["traffic_source"] = "none: profiles/pmc_latest.json missing"
+        if os.path.exists(pmc):
+            try:
+                doc = json.load(open(pmc))
+                have, want = doc.get("stamps", {}), source_stamps()
+                if all(have.get(k) == want[k] for k in want):
+                    line["roofline"]["traffic"] = doc.get("count_pass", {}).get("hbm_bytes_per_launch")
+                    line["roofline"]["traffic_source"] = ("profiles/pmc_latest.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `%s` on %s, "
+                                                          "bench_sha16=%s kernel_sha16=%s head=%s" % (have.get("command"), have.get("date"), have.get("bench_sha16"),
+                                                                                                      have.get("kernel_sha16"), have.get("head")))
+                else:
+                    line["roofline"]["traffic_source"] = "stale: profiles/pmc_latest.json was taken on other code (%s), not quoted" % ", ".join(
+                        "%s %s != %s" % (k, have.get(k), want[k]) for k in want if have.get(k) != want[k])
+            except Exception as ex:
+                line["roofline"]["traffic_source"] = "unreadable: %r" % ex
     if baseline is not None:
         res = baseline.measure(qs_h, qe_h, args.cpu_sample)
         if res is None:
@@ -1082,20 +1102,20 @@ def main():
             except Exception as ex:
                 cb["calibration_error"] = repr(ex)
             line["cpu_baseline"] = cb
-    if world == 1 and not args.no_bitset:
+    if args.full and world == 1 and not args.no_bitset:
         try:
             del qs, qe, counts
             torch.cuda.empty_cache()
             line["bitset"] = bench_bitsets(torch, max(5, args.steps), args.warmup)
         except Exception as ex:
             line["bitset"] = {"error": repr(ex)}
-    if world == 1 and not args.no_find:
+    if args.full and world == 1 and not args.no_find:
         try:
             torch.cuda.empty_cache()
             line["find_csr"] = bench_find(torch)
         except Exception as ex:
             line["find_csr"] = {"error": repr(ex)}
-    if world == 1 and not args.no_genome:
+    if args.full and world == 1 and not args.no_genome:
         try:
             torch.cuda.empty_cache()
             line["genome"] = bench_genome(torch, dist, 0, 1, max(5, args.steps), args.warmup, args.targets, args.queries)
@@ -1108,7 +1128,7 @@ def main():
     line["collective"] = coll
     if dry:
         line["dry_run"] = "BENCH_DRY_MULTI=1: every rank on cuda:0, gloo instead of RCCL -- a rehearsal of the code path, not a measurement"
-    if world == 1 and not args.no_find:
+    if args.full and world == 1 and not args.no_find:
         try:
             torch.cuda.empty_cache()
             line["clustered"] = bench_clustered(torch)
@@ -1116,7 +1136,7 @@ def main():
             line["clustered"]["generated_order"]["x_uniform_time"] = round(line["clustered"]["generated_order"]["ms"] / u, 2)
         except Exception as ex:
             line["clustered"] = {"error": repr(ex)}
-    if world == 1 and not args.no_find:
+    if args.full and world == 1 and not args.no_find:
         try:
             line["per_call_latency"] = bench_per_call()
         except Exception as ex:

@@ -35,7 +35,7 @@ def _line(stdout):
 def test_bench_launches_its_own_ranks_dry_two():
     nq, nt = 4_000_000, 400_000
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--queries", str(nq),
-                        "--targets", str(nt), "--no-cpu-baseline"], capture_output=True, text=True, timeout=1500, env=_env(BENCH_DRY_MULTI="1"))
+                        "--targets", str(nt), "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=1500, env=_env(BENCH_DRY_MULTI="1"))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = _line(p.stdout)
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and "dry_run" in line

@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 for r in $(seq 1 ${ROUNDS:-2}); do
   for lib in ${LIBS:-libbxmi_base.so libbxmi.so}; do
-    BXMI_LIB=$PWD/bx-python_amd/bxmi/$lib timeout 900 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-pcie ${BENCH_ARGS:-} 2>/dev/null | tail -1 | python -c "
+    BXMI_LIB=$PWD/bx-python_amd/bxmi/$lib timeout 900 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-pcie ${BENCH_ARGS:-} 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 g=lambda *k: (lambda x: x)(__import__('functools').reduce(lambda a,b: (a or {}).get(b) if isinstance(a,dict) else None, k, d))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One GPU iteration (via gpurun): [TESTS=1] the interval parity tests, a short bench line, the count pass's kernel list
 # (rocprofv3 --kernel-trace --stats), [SHARE=1] the projected rank shares and the kernel list of the 8-GPU share.
-# Everything lands in gpurun_out/.
+# The bench line is summarised on stdout; everything else is written to the output folder.
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 REPO=$PWD
@@ -12,16 +12,19 @@ if [ "${TESTS:-1}" = "1" ]; then
   echo "intervals rc=$?"; tail -4 gpurun_out/test_intervals.log
 fi
 if [ "${COUNT:-1}" = "1" ]; then
-timeout 600 python bench.py --steps 20 --warmup 3 ${BENCH_ARGS:---no-cpu-baseline --no-bitset --no-find --no-genome} > gpurun_out/bench_short.json 2> gpurun_out/bench_short.err
-echo "bench rc=$?"; python - <<'PY'
-import json
+BENCH_LINE=$(mktemp)
+timeout 600 python bench.py --full --steps 20 --warmup 3 ${BENCH_ARGS:---no-cpu-baseline --no-bitset --no-find --no-genome} > "$BENCH_LINE" 2> "$BENCH_LINE.err"
+rc=$?; echo "bench rc=$rc"; [ $rc = 0 ] || tail -5 "$BENCH_LINE.err"
+python - "$BENCH_LINE" <<'PY'
+import json, sys
 try:
-    d = json.loads(open("gpurun_out/bench_short.json").read().strip().splitlines()[-1])
+    d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
     print("ms_per_step", d["ms_per_step"], "kernel_ms", d["roofline"]["kernel_ms"], "frac", d["roofline"]["frac"], "| sorted", (d.get("sorted_queries") or {}).get("ms_per_pass"),
           "| total_only", (d.get("total_only") or {}).get("ms_per_pass"), "|", d["parity"][:160])
 except Exception as ex:
     print("no bench line:", ex)
 PY
+rm -f "$BENCH_LINE" "$BENCH_LINE.err"
 fi
 stats() {  # $1 = output dir, rest = command
   local out=$1; shift
