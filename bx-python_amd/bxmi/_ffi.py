@@ -66,6 +66,11 @@ _SIGNATURES = {
     "bxmi_ivl_neighbors_batch": [vp, vp, i64, i32, i32, C.c_int, vp, vp, vp],
     "bxmi_ivl_neighbors_batch_dev": [vp, vp, i64, i32, i32, C.c_int, vp, vp, vp, vp],
     "bxmi_ivl_clusters": [vp, vp, i32, _p(i64), vp, vp, vp, vp],
+    "bxmi_chainmap_create": [_p(vp), i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "bxmi_chainmap_destroy": [vp],
+    "bxmi_chainmap_info": [vp, _p(i64), _p(i64), _p(i64)],
+    "bxmi_chainmap_map": [vp, vp, vp, i64, i32, C.c_int, C.c_double, vp, vp, vp, vp, vp, i64, _p(i64)],
+    "bxmi_chainmap_map_dev": [vp, vp, vp, i64, i32, C.c_int, C.c_double, vp, vp, vp, vp, vp, i64, _p(i64), vp],
     "bxmi_bits_create": [i64, i64, _p(vp)],
     "bxmi_bits_destroy": [vp],
     "bxmi_bits_info": [vp, _p(i32), _p(i32), _p(i32)],

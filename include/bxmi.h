@@ -18,6 +18,7 @@
  *   lib/bx/bitset.pyx:198-241    BinnedBitSet methods        -> call bxmi_bits_*
  *   lib/bx/intervals/intersection.pyx:388-406,428-435
  *                                IntervalTree.insert/find    -> bxmi_ivl_*
+ *   scripts/bnMapper.py:83-193   transform, the choice between chains, union_elements -> bxmi_chainmap_*
  *   (intersection.pyx has no C ABI of its own: its cdef classes are the
  *    interface, so the entry points below are what a Cython/ctypes shim of
  *    those classes binds; see INTEGRATION.md.)
@@ -239,6 +240,55 @@ int bxmi_ivl_neighbors_batch_dev(bxmi_ivl_t *h, const int32_t *pos, int64_t nq, 
  * -> BXMI_EINVAL (the reference's result then depends on the insertion order and on unseeded rand() priorities). */
 int bxmi_ivl_clusters(bxmi_ivl_t *h, const int32_t *ids, int32_t max_dist, int64_t *n_clusters, int32_t *starts, int32_t *ends,
                       int64_t *offsets, int32_t *members);
+
+/* ---- liftover through chain alignments  (scripts/bnMapper.py) ---------------
+ * One bxmi_chainmap_t holds the chains of ONE source chromosome, resident on the device: an interval index over their
+ * spans [t_start, t_end) in the order given (bnMapper.py:417-420 inserts them in file order) and their block tables.
+ * All coordinates are forward-strand (bnMapper.py:299-305 converts a '-' side in the header); block tables are relative
+ * to their chain's start and cumulative (lib/bx/align/epo.py:19-43): chain c owns blocks block_off[c] .. block_off[c+1],
+ * block j aligns target [blk_t_start[j], blk_t_end[j]) + t_start[c] with query [blk_q_start[j], blk_q_start[j] + its length),
+ * the latter relative to q_start[c] before the strand flip.  q_span[c] = qEnd - qStart (the Sz of bnMapper.py:121),
+ * q_minus[c] != 0 = query strand '-'.
+ * Empty blocks are legal (chains made from EPO alignments have them).  Refused with BXMI_EINVAL: a chain without blocks,
+ * a block of negative length, a block that starts before the one before it ends on either side (a negative gap) or
+ * reaches outside its chain's span, t_end - t_start or q_start + q_span beyond 2^31-1, more than 2^31-1 blocks.  (The
+ * reference takes such tables and answers by whole-table scans; no chain file has them.) */
+typedef struct bxmi_chainmap bxmi_chainmap_t;
+int bxmi_chainmap_create(bxmi_chainmap_t **out, int64_t n_chains, const int32_t *t_start, const int32_t *t_end, const int32_t *q_start,
+                         const int32_t *q_span, const uint8_t *q_minus, const int64_t *block_off, const int32_t *blk_t_start,
+                         const int32_t *blk_t_end, const int32_t *blk_q_start);
+int bxmi_chainmap_destroy(bxmi_chainmap_t *m);
+/* Each optional (NULL): number of chains, number of blocks, blocks of the longest chain. */
+int bxmi_chainmap_info(const bxmi_chainmap_t *m, int64_t *n_chains, int64_t *n_blocks, int64_t *max_chain_blocks);
+
+#define BXMI_LIFT_MAPPED 0  /* rows offsets[i] .. offsets[i+1] hold the result */
+#define BXMI_LIFT_NOCHAIN 1 /* no chain met, or every chain met yields nothing (gap region, gap rule)  bnMapper.py:169 */
+#define BXMI_LIFT_SPLIT 2   /* more than one chain yields something and select == 0                    bnMapper.py:180 */
+#define BXMI_LIFT_BELOW 3   /* (fe - fs) * threshold > mapped bases                                    bnMapper.py:187 */
+#define BXMI_LIFT_EMPTY 4   /* the union left nothing                                                  bnMapper.py:193 */
+/* transform_by_chrom (bnMapper.py:153-193) for nf features [fs[i], fe[i]) of this chromosome:
+ *   max_gap    -g: < 0 = no gap rule; the rule looks at the junctions si .. ei-2 only, as bnMapper.py:102-107 does
+ *   select     what to do when several chains yield something: 0 = drop the feature (the default of the script),
+ *              1 = the first chain with the strictly largest (last slice's end - first slice's end), the first chain if none
+ *                  is positive (-k, bnMapper.py:172-179), 2 = the first chain in find order (the summit lookup, :222-242)
+ *   threshold  -t, compared in double arithmetic as the reference does
+ * A chain whose span reaches beyond its blocks yields nothing for a feature that meets only that part (the reference
+ * raises IndexError there, bnMapper.py:95-96).
+ * Out, per feature: chain[i] = the chosen chain (its position in the arrays given to create) or -1, status[i] = BXMI_LIFT_*;
+ * offsets[nf + 1] and, for feature i, rows offsets[i] .. offsets[i+1] of out_start / out_end: the unioned slices in query
+ * coordinates, ascending (union_elements + sorted, :126-142,192).  *total = offsets[nf].  More rows than `cap`: BXMI_ERANGE
+ * with chain, status, offsets and *total valid and out_start / out_end untouched.  Some fs[i] > fe[i]: BXMI_EINVAL, nothing
+ * written.  Host arrays; BLOCKS until everything is written. */
+int bxmi_chainmap_map(bxmi_chainmap_t *m, const int32_t *fs, const int32_t *fe, int64_t nf, int32_t max_gap, int select, double threshold,
+                      int32_t *chain, int32_t *status, int64_t *offsets, int32_t *out_start, int32_t *out_end, int64_t cap,
+                      int64_t *total);
+/* Device variant: device pointers of natural alignment (4 bytes, 8 for offsets); total_host is a HOST pointer.  Everything is
+ * enqueued on `stream`; the call waits for it twice -- inside bxmi_ivl_find_dev for the number of (feature, chain) pairs, and
+ * at its end for the row total that decides between BXMI_OK and BXMI_ERANGE (the rows are written by then).  One batch per
+ * handle at a time (the handle owns the scratch between the passes). */
+int bxmi_chainmap_map_dev(bxmi_chainmap_t *m, const int32_t *fs, const int32_t *fe, int64_t nf, int32_t max_gap, int select,
+                          double threshold, int32_t *chain, int32_t *status, int64_t *offsets, int32_t *out_start, int32_t *out_end,
+                          int64_t cap, int64_t *total_host, void *stream);
 
 /* ---- binned bitset  (binBits.h:15-26, bitset.pyx:198-241) ----------------- */
 /* binBitsAlloc(size, granularity): bin_size and nbins use the reference's
