@@ -461,6 +461,7 @@ static int ivl_find_partitioned(bxmi_ivl *h, const int32_t *qs, const int32_t *q
 static int bp_prepare_index(bxmi_ivl *h, hipStream_t st)
 {
     h->bp_state = -1;
+    h->bp_hard_cells = 0;  // (an index that is refused before its images are built has none to report)
     const int shift = h->geom.shift;
     // (units of at least two buckets: the 1024-thread tile sorts can then start every unit's run on a whole 16-byte slot)
     if (h->has_reversed || h->n < 4096 || shift > BP_UNIT_LOG2 - 1 || shift < BM_MIN_SHIFT) return BXMI_OK;
@@ -505,6 +506,7 @@ static int bp_prepare_index(bxmi_ivl *h, hipStream_t st)
 static int bo_prepare_index(bxmi_ivl *h, hipStream_t st, bool clumped = false)
 {
     h->bo_state = -1;
+    h->bo_hard_cells = 0;
     const int shift = h->geom.shift;
     int64_t span = (int64_t)h->cmax - (int64_t)h->geom.cmin + 1;
     const int k = g_opt_bo_cell_log2 ? (int)g_opt_bo_cell_log2 : (clumped ? BO_MIN_K : bo_cell_log2_for(span, h->n));
@@ -555,6 +557,7 @@ static int bo_prepare_index(bxmi_ivl *h, hipStream_t st, bool clumped = false)
 static int bd_prepare_index(bxmi_ivl *h, hipStream_t st)
 {
     h->bd_state = -1;
+    h->bd_worst[0] = h->bd_worst[1] = 0;
     const int shift = h->geom.shift;
     if (h->has_reversed || h->n < 4096 || shift > BD_MAX_SHIFT || shift < BM_MIN_SHIFT) return BXMI_OK;
     // Units of 2^19 coordinates first (runs twice as long, 12 KiB of LDS for duplicated coordinates: enough for an index
@@ -609,6 +612,7 @@ static int bd_prepare_index(bxmi_ivl *h, hipStream_t st)
 static int sl_prepare_index(bxmi_ivl *h, hipStream_t st)
 {
     h->sl_state = -1;
+    for (unsigned &need : h->sl_need) need = 0;
     if (h->has_reversed || h->n < 1) return BXMI_OK;
     BXMI_TRY(h->sl_meta.reserve((size_t)(BM_NB + 1) * sizeof(int4)));
     BXMI_TRY(h->sl_stats.reserve(64));
@@ -1619,11 +1623,14 @@ extern "C" int bxmi_ivl_seal(bxmi_ivl_t *h, void *stream)
         h->geom.cmin = cmin;
         h->geom.shift = shift;
         h->cmax = cmax;
+        // (what the stages reported about the index that was goes with their states: a resealed handle answers the *_state
+        // calls as a fresh one does)
         h->sl_state = 0;
-        h->fx_state = 0, h->fx_pieces_f = -1;
-        h->bd_state = 0;
-        h->bp_state = 0;
-        h->bo_state = 0, h->bo_tried_clumped = false;
+        for (unsigned &need : h->sl_need) need = 0;
+        h->fx_state = 0, h->fx_pieces_f = -1, h->fx_hits_per_q = -1.0;
+        h->bd_state = 0, h->bd_worst[0] = h->bd_worst[1] = 0, h->bd_blocks = false;
+        h->bp_state = 0, h->bp_hard_cells = 0;
+        h->bo_state = 0, h->bo_tried_clumped = false, h->bo_hard_cells = 0;
         h->w8_off = false, h->w8_queries = 0;  // (the feedback of the 8-bit counts belongs to the index that was)
         if (h->bd_fb_host) {
             BXMI_HIP(hipMemsetAsync(h->bd_fb.p, 0, 64, st));
