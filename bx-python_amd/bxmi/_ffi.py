@@ -71,6 +71,15 @@ _SIGNATURES = {
     "bxmi_chainmap_info": [vp, _p(i64), _p(i64), _p(i64)],
     "bxmi_chainmap_map": [vp, vp, vp, i64, i32, C.c_int, C.c_double, vp, vp, vp, vp, vp, i64, _p(i64)],
     "bxmi_chainmap_map_dev": [vp, vp, vp, i64, i32, C.c_int, C.c_double, vp, vp, vp, vp, vp, i64, _p(i64), vp],
+    "bxmi_scores_create": [i64, _p(vp)],
+    "bxmi_scores_destroy": [vp],
+    "bxmi_scores_info": [vp, _p(i64)],
+    "bxmi_scores_values_dev": [vp, _p(vp), vp],
+    "bxmi_scores_write": [vp, i64, vp, i64],
+    "bxmi_scores_read": [vp, i64, vp, i64],
+    "bxmi_scores_set_spans": [vp, vp, vp, vp, i64],
+    "bxmi_scores_aggregate": [vp, vp, vp, vp, i64, vp, vp, vp, vp],
+    "bxmi_scores_aggregate_dev": [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp],
     "bxmi_bits_create": [i64, i64, _p(vp)],
     "bxmi_bits_destroy": [vp],
     "bxmi_bits_info": [vp, _p(i32), _p(i32), _p(i32)],

@@ -1,0 +1,129 @@
+"""
+Per-base score tracks on the MI355X: the average, minimum and maximum of a score track (phastCons and the like) over a
+whole array of intervals per call -- the engine under ``bxmi.cli.aggregate_scores_in_intervals`` (reference:
+scripts/aggregate_scores_in_intervals.py:107-134 over lib/bx/binned_array.py).
+
+``ScoreTrack`` is one chromosome's scores as a dense float32 array in HBM (``bxmi_scores_*`` of include/bxmi.h), NaN = no
+score.  ``aggregate`` answers from host arrays, ``aggregate_dev`` from device arrays.  The sums are the reference's bit for
+bit: float32, added in position order.
+"""
+import collections
+import ctypes as C
+
+import numpy as np
+
+from . import _ffi
+from ._ffi import as_i32, call, ptr
+
+# per interval: valid bases, their ordered float32 sum, their smallest and largest score (+inf / -inf where count == 0)
+Aggregate = collections.namedtuple("Aggregate", "count total minimum maximum")
+
+MIN_SENTINEL, MAX_SENTINEL = 100000000, -100000000  # aggregate_scores_in_intervals.py:112-113
+
+
+def _mask_handle(mask):
+    """The bxmi_bits_t behind a mask: None, a bxmi.bitset.DeviceBitSet, or a drop-in bx.bitset set (its queue is flushed)."""
+    if mask is None:
+        return None
+    if hasattr(mask, "_flush"):
+        mask._flush()
+        mask = mask._d
+    return mask._h
+
+
+class ScoreTrack:
+    """float32 scores of positions [0, size) resident on the device; every position starts without a score (NaN)."""
+
+    def __init__(self, size):
+        _ffi.require_gpu()
+        h = C.c_void_p()
+        call("bxmi_scores_create", int(size), C.byref(h))
+        self._h = h
+        self.size = int(size)
+
+    def close(self):
+        if self._h is not None:
+            _ffi.load().bxmi_scores_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def values_dev(self):
+        """(device pointer, n) of the float32 array."""
+        p, n = C.c_void_p(), C.c_int64(0)
+        call("bxmi_scores_values_dev", self._h, C.byref(p), C.byref(n))
+        return p.value, n.value
+
+    def write(self, offset, values):
+        """values -> track[offset : offset + len(values)]"""
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        call("bxmi_scores_write", self._h, int(offset), ptr(v), len(v))
+
+    def read(self, offset=0, n=None):
+        """track[offset : offset + n] as a numpy float32 array (to the end when n is None)"""
+        n = self.size - int(offset) if n is None else int(n)
+        out = np.empty(max(n, 0), dtype=np.float32)
+        call("bxmi_scores_read", self._h, int(offset), ptr(out), n)
+        return out
+
+    def set_spans(self, starts, ends, values):
+        """track[starts[i]:ends[i]] = values[i], in order: where spans overlap the later one wins.  Spans are clipped to the track."""
+        s, e = as_i32(starts), as_i32(ends)
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        if not (s.shape == e.shape == v.shape) or s.ndim != 1:
+            raise ValueError("starts, ends and values must be 1-d arrays of equal length")
+        call("bxmi_scores_set_spans", self._h, ptr(s), ptr(e), ptr(v), len(s))
+
+    def aggregate(self, starts, ends, mask=None):
+        """count, ordered float32 sum, minimum and maximum of the valid scores of every [starts[i], ends[i]) -> Aggregate of numpy
+        arrays.  Valid: not NaN, not +-0, and not set in `mask` (a DeviceBitSet or a bx.bitset set; None = nothing is masked)."""
+        s, e = as_i32(starts), as_i32(ends)
+        if s.shape != e.shape or s.ndim != 1:
+            raise ValueError("starts and ends must be 1-d arrays of equal length")
+        n = len(s)
+        count = np.empty(n, dtype=np.int32)
+        total, mn, mx = (np.empty(n, dtype=np.float32) for _ in range(3))
+        call("bxmi_scores_aggregate", self._h, _mask_handle(mask), ptr(s), ptr(e), n, ptr(count), ptr(total), ptr(mn), ptr(mx))
+        return Aggregate(count, total, mn, mx)
+
+    def aggregate_ptrs(self, mask, start_ptr, end_ptr, n, count_ptr, total_ptr, min_ptr, max_ptr, stream=None):
+        """bxmi_scores_aggregate_dev as it stands: device pointers in, nothing waited for."""
+        call("bxmi_scores_aggregate_dev", self._h, _mask_handle(mask), start_ptr, end_ptr, int(n), count_ptr, total_ptr, min_ptr, max_ptr, stream)
+
+    def aggregate_dev(self, starts, ends, mask=None, stream=None):
+        """`aggregate` on device arrays: int32 torch tensors on the GPU in, an Aggregate of torch tensors out, queued on torch's
+        current stream (or `stream`); nothing is waited for."""
+        import torch
+
+        if starts.dtype != torch.int32 or ends.dtype != torch.int32 or starts.shape != ends.shape or starts.dim() != 1:
+            raise ValueError("starts and ends must be 1-d int32 tensors of equal length")
+        if not (starts.is_cuda and ends.is_cuda):
+            raise ValueError("aggregate_dev takes device tensors (host arrays: aggregate)")
+        starts, ends = starts.contiguous(), ends.contiguous()
+        n, dev = starts.numel(), starts.device
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        total, mn, mx = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
+        self.aggregate_ptrs(mask, starts.data_ptr(), ends.data_ptr(), n, count.data_ptr(), total.data_ptr(), mn.data_ptr(), mx.data_ptr(),
+                            stream=stream)
+        return Aggregate(count, total, mn, mx)
+
+
+def format_row(chrom, start, stop, count, total, minimum, maximum):
+    """One output line (without the newline) as aggregate_scores_in_intervals.py:127-134 prints it.  The average is the
+    float32 quotient total / count; the reference's minimum starts as the int 100000000 and is replaced by a score only
+    through min(score, minimum), so it survives -- and prints without a fraction -- when every valid score is above 1e8;
+    likewise the maximum and -100000000."""
+    if count > 0:
+        avg = np.float32(total) / int(count)
+        mn, mx = np.float32(minimum), np.float32(maximum)
+        mn = mn if mn <= MIN_SENTINEL else MIN_SENTINEL
+        mx = mx if mx >= MAX_SENTINEL else MAX_SENTINEL
+    else:
+        avg = mn = mx = "nan"
+    return "\t".join(map(str, [chrom, start, stop, avg, mn, mx]))

@@ -46,6 +46,8 @@ int ivl_option_count();
 int ivl_option_at(int i, const char **key, int64_t *value);
 int bits_set_option(const char *key, int64_t value);
 int64_t bits_get_grid();
+int scores_set_option(const char *key, int64_t value);
+int64_t scores_get_wave_min_len();
 
 }  // namespace bxmi
 
@@ -165,11 +167,11 @@ extern "C" int bxmi_set_option(const char *key, int64_t value)
         bxmi::g_opt_poll = value != 0;
         return BXMI_OK;
     }
-    if (ivl_set_option(key, value) || bits_set_option(key, value)) return BXMI_OK;
+    if (ivl_set_option(key, value) || bits_set_option(key, value) || scores_set_option(key, value)) return BXMI_OK;
     return fail(BXMI_EINVAL, "bxmi_set_option: unknown key '%s'", key);
 }
 
-// every option in turn: i = 0, 1, ... until BXMI_EINVAL (the interval path's table, then bits.grid and core.poll)
+// every option in turn: i = 0, 1, ... until BXMI_EINVAL (the interval path's table, then bits.grid, core.poll and scores.wave_min_len)
 extern "C" int bxmi_option_at(int i, const char **key, int64_t *value)
 {
     if (!key || !value) return fail(BXMI_EINVAL, "bxmi_option_at: NULL output");
@@ -183,6 +185,10 @@ extern "C" int bxmi_option_at(int i, const char **key, int64_t *value)
         *key = "core.poll", *value = bxmi::g_opt_poll ? 1 : 0;
         return BXMI_OK;
     }
+    if (i == n + 2) {
+        *key = "scores.wave_min_len", *value = scores_get_wave_min_len();
+        return BXMI_OK;
+    }
     return fail(BXMI_EINVAL, "bxmi_option_at: no option %d", i);
 }
 
@@ -191,7 +197,7 @@ extern "C" int bxmi_get_option(const char *key, int64_t *value)
     if (!key || !value) return fail(BXMI_EINVAL, "bxmi_get_option: NULL argument");
     // (a local: an unknown key must leave *value alone; the loop is bounded by the table, so no failing call overwrites
     // the thread's error text before the real message is set)
-    const int n = ivl_option_count() + 2;
+    const int n = ivl_option_count() + 3;
     for (int i = 0; i < n; i++) {
         const char *k = nullptr;
         int64_t v = 0;

@@ -1,0 +1,224 @@
+// scores.hip -- per-base score tracks (bxmi_scores_*): dense float32 arrays in HBM, filled from spans, aggregated over
+// batches of intervals.  Kernels and the exactness argument: scores.hpp.
+#include <new>
+#include <vector>
+
+#include "common.hpp"
+#include "scores.hpp"
+
+namespace bxmi {
+
+static int64_t g_opt_wave_min_len = 8192;  // scores.wave_min_len: intervals of at least this many bases take a wave each
+
+int scores_set_option(const char *key, int64_t value)
+{
+    if (!strcmp(key, "scores.wave_min_len")) {
+        g_opt_wave_min_len = value < 0 ? 0 : value;
+        return 1;
+    }
+    return 0;
+}
+
+int64_t scores_get_wave_min_len() { return g_opt_wave_min_len; }
+
+}  // namespace bxmi
+
+using namespace bxmi;
+
+struct bxmi_scores {
+    int64_t size = 0;
+    DevBuf values;
+    DevBuf long_list;                            // int32[1 + n]: the intervals of the current batch left to the wave kernel
+    DevBuf order, work;                          // int32[n]: the others ordered by length; the ordering's counters (scores.hpp)
+    DevBuf q_start, q_end, q_value;              // staging of the host forms
+    DevBuf r_count, r_sum, r_min, r_max;
+    hipStream_t stream = nullptr;
+};
+
+static int scores_stream(bxmi_scores *h)
+{
+    if (!h->stream) BXMI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_scores_create(int64_t size, bxmi_scores_t **out)
+{
+    if (!out) return fail(BXMI_EINVAL, "bxmi_scores_create: out is NULL");
+    *out = nullptr;
+    if (size < 0 || size > 2147483647LL) return fail(BXMI_EINVAL, "bxmi_scores_create: size %lld outside [0, 2^31-1]", (long long)size);
+    bxmi_scores *h = new (std::nothrow) bxmi_scores();
+    if (!h) return fail(BXMI_ENOMEM, "bxmi_scores_create: host allocation failed");
+    h->size = size;
+    int rc = scores_stream(h);
+    if (rc == BXMI_OK) rc = h->values.reserve((size_t)(size > 0 ? size : 1) * sizeof(float));
+    if (rc == BXMI_OK && size > 0) {
+        hipLaunchKernelGGL(sc_nan_kernel, dim3(stream_grid(size, SC_FILL_THREADS * 8)), dim3(SC_FILL_THREADS), 0, h->stream, h->values.as<float>(), size);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = fail(BXMI_EHIP, "bxmi_scores_create: %s", hipGetErrorString(e));
+    }
+    if (rc != BXMI_OK) {
+        if (h->stream) (void)hipStreamDestroy(h->stream);
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_scores_destroy(bxmi_scores_t *h)
+{
+    if (!h) return BXMI_OK;
+    if (h->stream) {
+        (void)hipStreamSynchronize(h->stream);
+        (void)hipStreamDestroy(h->stream);
+    }
+    delete h;
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_scores_info(const bxmi_scores_t *h, int64_t *size)
+{
+    if (!h) return fail(BXMI_EINVAL, "bxmi_scores_info: NULL handle");
+    if (size) *size = h->size;
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_scores_values_dev(bxmi_scores_t *h, float **values_dev, int64_t *n)
+{
+    if (!h) return fail(BXMI_EINVAL, "bxmi_scores_values_dev: NULL handle");
+    if (values_dev) *values_dev = h->values.as<float>();
+    if (n) *n = h->size;
+    return BXMI_OK;
+}
+
+static int scores_check_window(const bxmi_scores *h, int64_t offset, const void *p, int64_t n, const char *who)
+{
+    if (!h) return fail(BXMI_EINVAL, "%s: NULL handle", who);
+    if (n < 0 || offset < 0 || offset > h->size || n > h->size - offset)
+        return fail(BXMI_EINVAL, "%s: [%lld, %lld + %lld) outside the track [0, %lld)", who, (long long)offset, (long long)offset, (long long)n,
+                    (long long)h->size);
+    if (n > 0 && !p) return fail(BXMI_EINVAL, "%s: NULL array", who);
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_scores_write(bxmi_scores_t *h, int64_t offset, const float *values, int64_t n)
+{
+    BXMI_TRY(scores_check_window(h, offset, values, n, "bxmi_scores_write"));
+    if (n) BXMI_HIP(hipMemcpy(h->values.as<float>() + offset, values, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_scores_read(bxmi_scores_t *h, int64_t offset, float *out, int64_t n)
+{
+    BXMI_TRY(scores_check_window(h, offset, out, n, "bxmi_scores_read"));
+    if (n) BXMI_HIP(hipMemcpy(out, h->values.as<float>() + offset, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return BXMI_OK;
+}
+
+// "As if applied in order": the list is cut into maximal runs of ascending, disjoint spans (after clipping; spans clipped to
+// nothing belong to any run), each run is one launch, the launches follow each other on one stream.  A wiggle file in
+// position order is a single run; a list in descending order costs a launch per span.
+extern "C" int bxmi_scores_set_spans(bxmi_scores_t *h, const int32_t *start, const int32_t *end, const float *value, int64_t n)
+{
+    if (!h) return fail(BXMI_EINVAL, "bxmi_scores_set_spans: NULL handle");
+    if (n < 0 || (n > 0 && (!start || !end || !value))) return fail(BXMI_EINVAL, "bxmi_scores_set_spans: bad arguments");
+    if (n == 0 || h->size == 0) return BXMI_OK;
+    std::vector<int64_t> cuts;  // first span of every run
+    cuts.push_back(0);
+    int64_t reach = 0;          // end of the last non-empty span of the current run
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t s = start[i] > 0 ? start[i] : 0, e = end[i] < h->size ? end[i] : h->size;
+        if (s >= e) continue;
+        if (s < reach) cuts.push_back(i);
+        reach = e;
+    }
+    cuts.push_back(n);
+    BXMI_TRY(scores_stream(h));
+    BXMI_TRY(h->q_start.reserve((size_t)n * 4));
+    BXMI_TRY(h->q_end.reserve((size_t)n * 4));
+    BXMI_TRY(h->q_value.reserve((size_t)n * 4));
+    BXMI_HIP(hipMemcpyAsync(h->q_start.p, start, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    BXMI_HIP(hipMemcpyAsync(h->q_end.p, end, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    BXMI_HIP(hipMemcpyAsync(h->q_value.p, value, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    for (size_t r = 0; r + 1 < cuts.size(); r++) {
+        const int64_t a = cuts[r], m = cuts[r + 1] - a;
+        if (m <= 0) continue;
+        hipLaunchKernelGGL(sc_fill_kernel, dim3(stream_grid(m, SC_FILL_THREADS)), dim3(SC_FILL_THREADS), 0, h->stream, h->values.as<float>(), h->size,
+                           h->q_start.as<int32_t>() + a, h->q_end.as<int32_t>() + a, h->q_value.as<float>() + a, m);
+        BXMI_LAUNCH_CHECK();
+    }
+    BXMI_HIP(hipStreamSynchronize(h->stream));
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_scores_aggregate_dev(bxmi_scores_t *h, const bxmi_bits_t *mask_or_null, const int32_t *start, const int32_t *end, int64_t n,
+                                         int32_t *count, float *sum, float *min, float *max, void *stream)
+{
+    if (!h) return fail(BXMI_EINVAL, "bxmi_scores_aggregate_dev: NULL handle");
+    if (n < 0 || n > 2147483647LL) return fail(BXMI_EINVAL, "bxmi_scores_aggregate_dev: n = %lld outside [0, 2^31-1]", (long long)n);
+    if (n == 0) return BXMI_OK;
+    if (!start || !end || !count || !sum || !min || !max) return fail(BXMI_EINVAL, "bxmi_scores_aggregate_dev: NULL array");
+    ScMask M{nullptr, 0, 0};
+    if (mask_or_null) {
+        uint64_t *words = nullptr;
+        int32_t msize = 0;
+        // (the view makes the mask allocate the bins it has not touched yet; its bits do not change)
+        BXMI_TRY(bxmi_bits_words_dev(const_cast<bxmi_bits_t *>(mask_or_null), &words, &M.nwords));
+        BXMI_TRY(bxmi_bits_info(mask_or_null, &msize, nullptr, nullptr));
+        M.words = reinterpret_cast<const unsigned long long *>(words);
+        M.size = msize;
+    }
+    hipStream_t st = as_stream(stream);
+    BXMI_TRY(h->long_list.reserve((size_t)(n + 1) * sizeof(int32_t)));
+    int32_t *long_list = h->long_list.as<int32_t>();
+    BXMI_TRY(h->order.reserve((size_t)n * sizeof(int32_t)));
+    BXMI_TRY(h->work.reserve(SC_WORK_INTS * sizeof(int32_t)));
+    int32_t *order = h->order.as<int32_t>(), *work = h->work.as<int32_t>();
+    BXMI_HIP(hipMemsetAsync(long_list, 0, sizeof(int32_t), st));
+    BXMI_HIP(hipMemsetAsync(work, 0, SC_WORK_INTS * sizeof(int32_t), st));
+    const float *values = h->values.as<float>();
+    const int64_t wave_min_len = g_opt_wave_min_len;
+    hipLaunchKernelGGL(sc_bucket_count_kernel, dim3(stream_grid(n, SC_ORD_THREADS * 4)), dim3(SC_ORD_THREADS), 0, st, start, end, n, h->size,
+                       wave_min_len, work, long_list);
+    BXMI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sc_bucket_scan_kernel, dim3(1), dim3(SC_BUCKETS), 0, st, work);
+    BXMI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sc_bucket_scatter_kernel, dim3((unsigned)div_up(n, SC_ORD_THREADS * SC_ORD_ITEMS)), dim3(SC_ORD_THREADS), 0, st, start, end, n,
+                       h->size, wave_min_len, work, order);
+    BXMI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sc_rows_kernel, dim3((unsigned)div_up(n, SC_ROWS)), dim3(SC_ROWS), 0, st, values, h->size, M, start, end, work, order, count, sum,
+                       min, max);
+    BXMI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sc_wave_kernel, dim3(stream_grid(n, SC_WAVE_THREADS / 64)), dim3(SC_WAVE_THREADS), 0, st, values, h->size, M, start, end, count,
+                       sum, min, max, long_list);
+    BXMI_LAUNCH_CHECK();
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_scores_aggregate(bxmi_scores_t *h, const bxmi_bits_t *mask_or_null, const int32_t *start, const int32_t *end, int64_t n, int32_t *count,
+                                     float *sum, float *min, float *max)
+{
+    if (!h) return fail(BXMI_EINVAL, "bxmi_scores_aggregate: NULL handle");
+    if (n < 0 || n > 2147483647LL) return fail(BXMI_EINVAL, "bxmi_scores_aggregate: n = %lld outside [0, 2^31-1]", (long long)n);
+    if (n == 0) return BXMI_OK;
+    if (!start || !end || !count || !sum || !min || !max) return fail(BXMI_EINVAL, "bxmi_scores_aggregate: NULL array");
+    BXMI_TRY(scores_stream(h));
+    const size_t bytes = (size_t)n * 4;
+    BXMI_TRY(h->q_start.reserve(bytes));
+    BXMI_TRY(h->q_end.reserve(bytes));
+    BXMI_TRY(h->r_count.reserve(bytes));
+    BXMI_TRY(h->r_sum.reserve(bytes));
+    BXMI_TRY(h->r_min.reserve(bytes));
+    BXMI_TRY(h->r_max.reserve(bytes));
+    BXMI_HIP(hipMemcpyAsync(h->q_start.p, start, bytes, hipMemcpyHostToDevice, h->stream));
+    BXMI_HIP(hipMemcpyAsync(h->q_end.p, end, bytes, hipMemcpyHostToDevice, h->stream));
+    BXMI_TRY(bxmi_scores_aggregate_dev(h, mask_or_null, h->q_start.as<int32_t>(), h->q_end.as<int32_t>(), n, h->r_count.as<int32_t>(),
+                                       h->r_sum.as<float>(), h->r_min.as<float>(), h->r_max.as<float>(), h->stream));
+    BXMI_HIP(hipMemcpyAsync(count, h->r_count.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    BXMI_HIP(hipMemcpyAsync(sum, h->r_sum.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    BXMI_HIP(hipMemcpyAsync(min, h->r_min.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    BXMI_HIP(hipMemcpyAsync(max, h->r_max.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    BXMI_HIP(hipStreamSynchronize(h->stream));
+    return BXMI_OK;
+}

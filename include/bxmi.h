@@ -19,6 +19,8 @@
  *   lib/bx/intervals/intersection.pyx:388-406,428-435
  *                                IntervalTree.insert/find    -> bxmi_ivl_*
  *   scripts/bnMapper.py:83-193   transform, the choice between chains, union_elements -> bxmi_chainmap_*
+ *   scripts/aggregate_scores_in_intervals.py:107-134, lib/bx/binned_array.py:72-100
+ *                                the per-base loop over a BinnedArray of scores      -> bxmi_scores_*
  *   (intersection.pyx has no C ABI of its own: its cdef classes are the
  *    interface, so the entry points below are what a Cython/ctypes shim of
  *    those classes binds; see INTEGRATION.md.)
@@ -89,6 +91,8 @@ int bxmi_memset(void *dst_dev, int value, size_t bytes);
  *   bits.grid          grid of the per-bitset kernels
  *   core.poll          1 (default): the one-call paths (bxmi_ivl_find_one, short bxmi_bits_count_range) poll a completion
  *                      word their kernel writes to host memory; 0: they wait for the stream
+ *   scores.wave_min_len  bxmi_scores_aggregate: intervals with at least this many bases inside the track get a wave each
+ *                      (default 8192; 0 = all of them), shorter ones share a wave 64 at a time
  * Unknown keys return BXMI_EINVAL. */
 int bxmi_set_option(const char *key, int64_t value);
 /* The current value of an option, and every option in turn (i = 0, 1, ... until BXMI_EINVAL): what the tests and A/B tools
@@ -344,6 +348,42 @@ int bxmi_bits_group_popcount_dev(bxmi_bits_group_t *g, int64_t *counts_dev, void
  * start=next_set(end); end=next_clear(start) of bed_intersect_basewise.py:32-38
  * produces.  Writes up to cap pairs; *n_runs = number of runs (BXMI_ERANGE if > cap). */
 int bxmi_bits_runs(bxmi_bits_t *h, int32_t from, int32_t *run_start, int32_t *run_end, int64_t cap, int64_t *n_runs);
+
+/* ---- per-base score tracks  (scripts/aggregate_scores_in_intervals.py, lib/bx/binned_array.py) ----------
+ * One bxmi_scores_t is the BinnedArray of ONE chromosome as a dense float32 array [0, size) in HBM, size <= 2^31-1; NaN = no
+ * score (BinnedArray's default), positions outside [0, size) have none. */
+typedef struct bxmi_scores bxmi_scores_t;
+int bxmi_scores_create(int64_t size, bxmi_scores_t **out); /* every position NaN */
+int bxmi_scores_destroy(bxmi_scores_t *h);
+int bxmi_scores_info(const bxmi_scores_t *h, int64_t *size);
+/* Device view: float32[*n], *n = size. */
+int bxmi_scores_values_dev(bxmi_scores_t *h, float **values_dev, int64_t *n);
+/* values[offset .. offset + n) from / into a host array; a window that leaves [0, size) -> BXMI_EINVAL. */
+int bxmi_scores_write(bxmi_scores_t *h, int64_t offset, const float *values, int64_t n);
+int bxmi_scores_read(bxmi_scores_t *h, int64_t offset, float *out, int64_t n);
+/* values[start[i] .. end[i]) = value[i] for i = 0 .. n-1, as if applied in that order: where spans overlap the later one wins
+ * (load_scores_wiggle, :61-71, assigns position by position in file order).  Spans are clipped to the track; one that is clipped
+ * to nothing, empty or inverted is legal and does nothing.  Spans in ascending order without overlaps -- a wiggle file -- are
+ * one launch; every descent or overlap starts another.  Host arrays; BLOCKS until the track is written. */
+int bxmi_scores_set_spans(bxmi_scores_t *h, const int32_t *start, const int32_t *end, const float *value, int64_t n);
+/* The loop of aggregate_scores_in_intervals.py:110-126 for n intervals [start[i], end[i]).  A base is VALID when its score
+ * is not NaN, not +-0 (:115 skips falsy scores) and its bit in `mask_or_null` is clear (as bxmi_bits_get answers; positions at or
+ * beyond the mask's size are not masked).  Per interval:
+ *   count[i]  the valid bases
+ *   sum[i]    their float32 sum IN POSITION ORDER, one rounding per add: bit for bit the reference's `total` (numpy.float32 from
+ *             the first add on); +0.0 when count[i] == 0
+ *   min[i], max[i]  the smallest / largest valid score; +inf / -inf when count[i] == 0.  (The reference's sentinels -- its
+ *             minimum starts as the int 100000000 -- are the caller's: bxmi.scores.format_row.)
+ * start >= end gives count 0; negative starts and ends beyond the track are legal.  Because the sum of one interval is a
+ * serial chain of adds, an interval costs its length times the add latency however many CUs there are.
+ * Host arrays; BLOCKS until the four outputs are written. */
+int bxmi_scores_aggregate(bxmi_scores_t *h, const bxmi_bits_t *mask_or_null, const int32_t *start, const int32_t *end, int64_t n,
+                          int32_t *count, float *sum, float *min, float *max);
+/* Device variant: device pointers of natural alignment (4 bytes).  Stream-ordered on `stream`, no host synchronisation; the
+ * handle's list of long intervals is in use until the work completes (one batch per handle at a time).  The mask's words must
+ * be complete before the work on `stream` starts (the host forms of bxmi_bits_* return with them written). */
+int bxmi_scores_aggregate_dev(bxmi_scores_t *h, const bxmi_bits_t *mask_or_null, const int32_t *start, const int32_t *end, int64_t n,
+                              int32_t *count, float *sum, float *min, float *max, void *stream);
 
 /* ---- BED text -> SoA columns on the host (the step before the hot path) ------
  * Strict single-pass parser for what lib/bx/bitset_builders.py:33-46 and
