@@ -36,8 +36,10 @@
 #include <condition_variable>
 #include <mutex>
 #include <thread>
+#include <utility>
 
 #include "primitives.hpp"
+#include "count_plan.hpp"
 
 #include "count_direct.hpp"
 #include "count_parts.hpp"
@@ -48,7 +50,6 @@
 #include "find_sorted.hpp"
 #include "find_direct.hpp"
 #include "find_neighbors.hpp"
-#include "liftover.hpp"
 #include "cluster.hpp"
 
 namespace bxmi {
@@ -226,7 +227,21 @@ struct bxmi_ivl {
 
 static IndexDev index_dev(const bxmi_ivl *h);
 template <typename Kern>
-static int allow_big_lds(Kern k, size_t bytes);
+static int allow_big_lds(Kern k, size_t bytes)
+{
+    BXMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return BXMI_OK;
+}
+
+// Launch a kernel that takes dynamic LDS: its limit is raised to `lds` first (on every call), and the launch is checked.
+template <typename... Params, typename... Args>
+static int launch_lds(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Args &&...args)
+{
+    BXMI_TRY(allow_big_lds(kern, lds));
+    hipLaunchKernelGGL(kern, grid, block, lds, st, std::forward<Args>(args)...);
+    BXMI_LAUNCH_CHECK();
+    return BXMI_OK;
+}
 
 // Everything a bucketed pass needs to know about one (sub-)batch.
 struct PartPlan {
@@ -261,10 +276,7 @@ static int part_prepare(bxmi_ivl *h, int sub, int64_t q0, const int32_t *qs, con
     hipLaunchKernelGGL(part_colscan_kernel, dim3(nrb), dim3(PT_THREADS), 0, st, pp->table, pp->ntiles, rows_per_block, partial, gate);
     BXMI_LAUNCH_CHECK();
     const size_t scat_lds = (size_t)PT_TILE * 8 + PT_NB * sizeof(unsigned);
-    hipLaunchKernelGGL(part_scatter_kernel, dim3(pp->tgrid), dim3(PT_THREADS), scat_lds, st, qs, qe, nq, h->geom, pp->table, pp->ntiles, pp->bq,
-                       pp->lpos, gate);
-    BXMI_LAUNCH_CHECK();
-    return BXMI_OK;
+    return launch_lds(part_scatter_kernel, dim3(pp->tgrid), dim3(PT_THREADS), scat_lds, st, qs, qe, nq, h->geom, pp->table, pp->ntiles, pp->bq, pp->lpos, gate);
 }
 
 // Scratch for bucketing a batch of nq queries (grow-only).
@@ -277,7 +289,6 @@ static int part_reserve(bxmi_ivl *h, int64_t nq, bool want_lpos)
     BXMI_TRY(h->p_hist.reserve((size_t)PT_MAX_SUB * 80 * PT_NB * sizeof(unsigned)));
     BXMI_TRY(h->p_dest.reserve((size_t)(nq + 8) * 2));
     if (want_lpos) BXMI_TRY(h->p_cnt.reserve((size_t)(nq + 4) * 4));
-    BXMI_TRY(allow_big_lds(part_scatter_kernel, (size_t)PT_TILE * 8 + PT_NB * sizeof(unsigned)));
     return BXMI_OK;
 }
 
@@ -300,10 +311,9 @@ static int ivl_count_part_sub(bxmi_ivl *h, int sub, int64_t q0, const int32_t *q
     }
     const unsigned grid = (unsigned)(div_up(nq, PT_CHUNK) + PT_NB);
     unsigned short *cnt16 = counts ? h->p_cnt.as<unsigned short>() + q0 : nullptr;  // counts in bucket order, 16 bits + escape
-    hipLaunchKernelGGL(part_count_cells_kernel<unsigned short>, dim3(grid), dim3(PT_THREADS), (size_t)PT_LDS_INTS * 4, st, index_dev(h),
-                       h->e_sorted.as<int32_t>(), h->slice_bounds.as<SliceBound>(), h->cell_images.as<int32_t>(),
-                       h->cell_meta.as<CellsMeta>(), pp.plan, pp.table, pp.bq, nq, h->geom, cnt16, total_dev ? slots : nullptr, unsorted);
-    BXMI_LAUNCH_CHECK();
+    BXMI_TRY(launch_lds(part_count_cells_kernel<unsigned short>, dim3(grid), dim3(PT_THREADS), (size_t)PT_LDS_INTS * 4, st, index_dev(h),
+                        h->e_sorted.as<int32_t>(), h->slice_bounds.as<SliceBound>(), h->cell_images.as<int32_t>(), h->cell_meta.as<CellsMeta>(), pp.plan,
+                        pp.table, pp.bq, nq, h->geom, cnt16, total_dev ? slots : nullptr, unsorted));
     if (counts) {
         hipLaunchKernelGGL(part_gather_kernel<unsigned short>, dim3(pp.tgrid), dim3(PT_THREADS), 0, st, cnt16, pp.lpos, pp.table, pp.ntiles, nq,
                            counts, unsorted, index_dev(h), h->e_sorted.as<int32_t>(), qs, qe);
@@ -324,17 +334,14 @@ static int ivl_count_partitioned(bxmi_ivl *h, const int32_t *qs, const int32_t *
 {
     if (nq >= ((int64_t)1 << 31)) return fail(BXMI_EINVAL, "bxmi_ivl_count: more than 2^31 queries in one batch");
     BXMI_TRY(part_reserve(h, nq, counts != nullptr));
-    BXMI_TRY(allow_big_lds(part_count_cells_kernel<unsigned short>, (size_t)PT_LDS_INTS * 4));
     if (!h->images_ready) {
         // LDS images of every bucket for the search (159 MB, a property of the sealed index): built by the first large
         // batch, so the many small per-chromosome trees of the drop-in classes never pay for them
         BXMI_TRY(h->cell_images.reserve((size_t)PT_NB * PT_LDS_INTS * sizeof(int32_t)));
         BXMI_TRY(h->cell_meta.reserve(PT_NB * sizeof(CellsMeta)));
-        BXMI_TRY(allow_big_lds(part_cells_image_kernel, (size_t)PT_LDS_INTS * 4));
-        hipLaunchKernelGGL(part_cells_image_kernel, dim3(PT_NB), dim3(PT_THREADS), (size_t)PT_LDS_INTS * 4, st, index_dev(h),
+        BXMI_TRY(launch_lds(part_cells_image_kernel, dim3(PT_NB), dim3(PT_THREADS), (size_t)PT_LDS_INTS * 4, st, index_dev(h),
                            h->e_sorted.as<int32_t>(), h->slice_bounds.as<SliceBound>(), h->geom, h->cell_images.as<int32_t>(),
-                           h->cell_meta.as<CellsMeta>());
-        BXMI_LAUNCH_CHECK();
+                           h->cell_meta.as<CellsMeta>()));
         h->images_ready = true;
     }
     return ivl_count_part_sub(h, 0, 0, qs, qe, nq, counts, total_dev, st);
@@ -428,10 +435,9 @@ static int ivl_find_partitioned(bxmi_ivl *h, const int32_t *qs, const int32_t *q
     unsigned *table = pp.table;
     unsigned short *lpos = pp.lpos;
     const size_t lds_bytes = (size_t)PT_LDS_INTS * 4;
-    BXMI_TRY(allow_big_lds(part_window_kernel, lds_bytes));
     const unsigned grid = (unsigned)(div_up(nq, PT_CHUNK) + PT_NB);
-    hipLaunchKernelGGL(part_window_kernel, dim3(grid), dim3(PT_THREADS), lds_bytes, st, index_dev(h), h->slice_bounds.as<SliceBound>(), pp.plan,
-                       table, pp.bq, nq, h->p_lo.as<int32_t>(), h->p_hi.as<int32_t>(), h->p_cnt.as<int32_t>());
+    BXMI_TRY(launch_lds(part_window_kernel, dim3(grid), dim3(PT_THREADS), lds_bytes, st, index_dev(h), h->slice_bounds.as<SliceBound>(), pp.plan, table, pp.bq,
+                        nq, h->p_lo.as<int32_t>(), h->p_hi.as<int32_t>(), h->p_cnt.as<int32_t>()));
     hipLaunchKernelGGL(part_gather_kernel<int32_t>, dim3(tgrid), dim3(PT_THREADS), 0, st, h->p_cnt.as<int32_t>(), lpos, table, ntiles, nq,
                        h->q_cnt.as<int32_t>(), (const unsigned *)nullptr, index_dev(h), (const int32_t *)nullptr, (const int32_t *)nullptr,
                        (const int32_t *)nullptr);
@@ -445,9 +451,8 @@ static int ivl_find_partitioned(bxmi_ivl *h, const int32_t *qs, const int32_t *q
     if (total > cap) return fail(BXMI_ERANGE, "bxmi_ivl_find: %lld hits need a larger buffer than cap=%lld", (long long)total, (long long)cap);
     if (total == 0) return BXMI_OK;
     const size_t perm_lds = (size_t)PT_TILE * 8 + (PT_NB + 2) * 2 + PT_NB * 4 + 64;
-    BXMI_TRY(allow_big_lds(part_permute_i64_kernel, perm_lds));
-    hipLaunchKernelGGL(part_permute_i64_kernel, dim3(tgrid), dim3(PT_THREADS), perm_lds, st, reinterpret_cast<const long long *>(offsets), lpos,
-                       table, ntiles, nq, h->p_boffs.as<long long>());
+    BXMI_TRY(launch_lds(part_permute_i64_kernel, dim3(tgrid), dim3(PT_THREADS), perm_lds, st, reinterpret_cast<const long long *>(offsets), lpos,
+                       table, ntiles, nq, h->p_boffs.as<long long>()));
     int fgrid = device_props().cus * 8;
     hipLaunchKernelGGL(part_fill_kernel, dim3(fgrid), dim3(FIND_THREADS), 0, st, index_dev(h), reinterpret_cast<const int32_t *>(pp.bq), 2, nq,
                        h->p_lo.as<int32_t>(),
@@ -481,10 +486,8 @@ static int bp_prepare_index(bxmi_ivl *h, hipStream_t st)
     BXMI_TRY(h->bp_stats.reserve(64));
     BXMI_HIP(hipMemsetAsync(h->bp_stats.p, 0, 64, st));
     const size_t lds = (size_t)4 * L.ncs * sizeof(int32_t);
-    BXMI_TRY(allow_big_lds(bp_image_kernel, lds));
-    hipLaunchKernelGGL(bp_image_kernel, dim3((unsigned)units), dim3(BD_THREADS), lds, st, h->s_ord.as<int32_t>(), h->e_sorted.as<int32_t>(), (int)h->n, g,
-                       h->bp_images.as<unsigned char>(), h->bp_stats.as<unsigned>());
-    BXMI_LAUNCH_CHECK();
+    BXMI_TRY(launch_lds(bp_image_kernel, dim3((unsigned)units), dim3(BD_THREADS), lds, st, h->s_ord.as<int32_t>(), h->e_sorted.as<int32_t>(), (int)h->n, g,
+                       h->bp_images.as<unsigned char>(), h->bp_stats.as<unsigned>()));
     unsigned stats[2] = {0, 0};
     BXMI_HIP(hipMemcpyAsync(stats, h->bp_stats.p, sizeof(stats), hipMemcpyDeviceToHost, st));
     BXMI_HIP(hipStreamSynchronize(st));
@@ -530,16 +533,8 @@ static int bo_prepare_index(bxmi_ivl *h, hipStream_t st, bool clumped = false)
     BXMI_TRY(h->bp_stats.reserve(64));
     BXMI_HIP(hipMemsetAsync(h->bp_stats.p, 0, 64, st));
     const size_t lds = (size_t)L.ncs * sizeof(int32_t);
-    if (clumped) {
-        BXMI_TRY(allow_big_lds(bo_image_kernel<true>, lds));
-        hipLaunchKernelGGL(bo_image_kernel<true>, dim3((unsigned)units), dim3(BD_THREADS), lds, st, h->s_ord.as<int32_t>(), h->e_sorted.as<int32_t>(), (int)h->n, g,
-                           h->bo_images.as<unsigned char>(), h->bp_stats.as<unsigned>());
-    } else {
-        BXMI_TRY(allow_big_lds(bo_image_kernel<false>, lds));
-        hipLaunchKernelGGL(bo_image_kernel<false>, dim3((unsigned)units), dim3(BD_THREADS), lds, st, h->s_ord.as<int32_t>(), h->e_sorted.as<int32_t>(), (int)h->n, g,
-                           h->bo_images.as<unsigned char>(), h->bp_stats.as<unsigned>());
-    }
-    BXMI_LAUNCH_CHECK();
+    BXMI_TRY(launch_lds(clumped ? bo_image_kernel<true> : bo_image_kernel<false>, dim3((unsigned)units), dim3(BD_THREADS), lds, st, h->s_ord.as<int32_t>(),
+                        h->e_sorted.as<int32_t>(), (int)h->n, g, h->bo_images.as<unsigned char>(), h->bp_stats.as<unsigned>()));
     unsigned stats[3] = {0, 0, 0};
     BXMI_HIP(hipMemcpyAsync(stats, h->bp_stats.p, sizeof(stats), hipMemcpyDeviceToHost, st));
     BXMI_HIP(hipStreamSynchronize(st));
@@ -581,7 +576,6 @@ static int bd_prepare_index(bxmi_ivl *h, hipStream_t st)
         BXMI_TRY(h->bd_images.reserve((size_t)units * L.bytes));
         BXMI_TRY(h->bd_stats.reserve(64));
         const size_t lds = (size_t)8 * L.ncs * sizeof(int32_t);
-        BXMI_TRY(allow_big_lds(bd_image_kernel, lds));
         h->bd_geom = g;
         // ranks relative to the whole unit when every slice holds fewer than 2^15 keys (no table read per lookup), else
         // relative to blocks of 1024 cells
@@ -591,9 +585,8 @@ static int bd_prepare_index(bxmi_ivl *h, hipStream_t st)
         for (int table_from = tf_first; table_from <= tf_last; table_from += BD_TABLE_FROM_LAST - BD_TABLE_FROM_FIRST)
         for (int bshift = g_opt_bd_blocks ? 10 : 13; bshift >= 10; bshift -= 3) {
             BXMI_HIP(hipMemsetAsync(h->bd_stats.p, 0, 64, st));
-            hipLaunchKernelGGL(bd_image_kernel, dim3((unsigned)units), dim3(BD_THREADS), lds, st, h->s_ord.as<int32_t>(), h->e_sorted.as<int32_t>(),
-                               (int)h->n, g, bshift, h->bd_images.as<unsigned char>(), h->bd_stats.as<unsigned>(), table_from);
-            BXMI_LAUNCH_CHECK();
+            BXMI_TRY(launch_lds(bd_image_kernel, dim3((unsigned)units), dim3(BD_THREADS), lds, st, h->s_ord.as<int32_t>(), h->e_sorted.as<int32_t>(), (int)h->n, g,
+                                bshift, h->bd_images.as<unsigned char>(), h->bd_stats.as<unsigned>(), table_from));
             BXMI_HIP(hipMemcpyAsync(h->bd_worst, h->bd_stats.p, sizeof(h->bd_worst), hipMemcpyDeviceToHost, st));
             BXMI_HIP(hipStreamSynchronize(st));
             h->bd_blocks = bshift == 10;
@@ -686,6 +679,8 @@ struct BmLaunch {
     int npar = 0;
     BmParOut par_out;
     int n_segs = 1;
+    BmGeom g0;                         // the first segment's geometry (the sorted walk of a single index cuts its units by it)
+    unsigned long long order_seq = 0;  // the number of this pass among the handle's order-aware ones (0 = it is none)
 };
 
 template <int THREADS, int ITEMS>
@@ -693,39 +688,21 @@ static int bm_launch_tiles(const BmLaunch &L, hipStream_t st, bool sub = false)
 {
     constexpr int TILE = THREADS * ITEMS;
     bxmi_ivl *h = L.owner;
+    auto sort = [&](auto kern, int threads, size_t lds, unsigned *tend, unsigned short *tbl2, unsigned *tesc) {
+        return launch_lds(kern, dim3((unsigned)L.ntp), dim3(threads), lds, st, L.segs, L.tile_seg, h->bm_recs.as<unsigned>(), h->bm_slots.as<unsigned short>(),
+                          h->bm_tbl.as<unsigned short>(), L.gate, tend, tbl2, L.par, L.npar, L.par_out, tesc);
+    };
     if (sub) {  // find(): ordered by half buckets, both tables (find_exchange.hpp)
         if (THREADS != 1024 || L.pad) return fail(BXMI_ESTATE, "bm_launch_tiles: half buckets need a 1024-thread shape on packed runs");
         constexpr int T2 = THREADS == 1024 ? THREADS : 1024;  // (only the 1024-thread shapes instantiate the kernel)
         constexpr int I2 = TILE / T2;
-        const size_t lds = (size_t)TILE * 4 + FX_NBK * 4 + FX_NBK * 2 + 64;
-        BXMI_TRY(allow_big_lds((bm_tile_sort_kernel<T2, I2, false, 2>), lds));
-        hipLaunchKernelGGL((bm_tile_sort_kernel<T2, I2, false, 2>), dim3((unsigned)L.ntp), dim3(T2), lds, st, L.segs, L.tile_seg,
-                           h->bm_recs.as<unsigned>(), h->bm_slots.as<unsigned short>(), h->bm_tbl.as<unsigned short>(), L.gate, (unsigned *)nullptr,
-                           h->fx_tbl2.as<unsigned short>(), L.par, L.npar, L.par_out);
-        BXMI_LAUNCH_CHECK();
-        return BXMI_OK;
+        return sort(bm_tile_sort_kernel<T2, I2, false, 2>, T2, (size_t)TILE * 4 + FX_NBK * 4 + FX_NBK * 2 + 64, nullptr, h->fx_tbl2.as<unsigned short>(), nullptr);
     }
-    if (L.pad && L.tot) {
-        const size_t lds = (size_t)(TILE + 3 * THREADS) * 4 + BM_NB * 4 + BM_NB * 2 + 64;
-        BXMI_TRY(allow_big_lds((bm_tile_sort_kernel<THREADS, ITEMS, true, 1, true>), lds));
-        hipLaunchKernelGGL((bm_tile_sort_kernel<THREADS, ITEMS, true, 1, true>), dim3((unsigned)L.ntp), dim3(THREADS), lds, st, L.segs, L.tile_seg,
-                           h->bm_recs.as<unsigned>(), h->bm_slots.as<unsigned short>(), h->bm_tbl.as<unsigned short>(), L.gate, h->bd_tend.as<unsigned>(),
-                           (unsigned short *)nullptr, L.par, L.npar, L.par_out, h->bm_tesc.as<unsigned>());
-    } else if (L.pad) {
-        const size_t lds = (size_t)(TILE + 3 * THREADS) * 4 + BM_NB * 4 + BM_NB * 2 + 64;
-        BXMI_TRY(allow_big_lds((bm_tile_sort_kernel<THREADS, ITEMS, true>), lds));
-        hipLaunchKernelGGL((bm_tile_sort_kernel<THREADS, ITEMS, true>), dim3((unsigned)L.ntp), dim3(THREADS), lds, st, L.segs, L.tile_seg,
-                           h->bm_recs.as<unsigned>(), h->bm_slots.as<unsigned short>(), h->bm_tbl.as<unsigned short>(), L.gate, h->bd_tend.as<unsigned>(),
-                           (unsigned short *)nullptr, L.par, L.npar, L.par_out);
-    } else {
-        const size_t lds = (size_t)TILE * 4 + BM_NB * 4 + BM_NB * 2 + 64;
-        BXMI_TRY(allow_big_lds((bm_tile_sort_kernel<THREADS, ITEMS, false>), lds));
-        hipLaunchKernelGGL((bm_tile_sort_kernel<THREADS, ITEMS, false>), dim3((unsigned)L.ntp), dim3(THREADS), lds, st, L.segs, L.tile_seg,
-                           h->bm_recs.as<unsigned>(), h->bm_slots.as<unsigned short>(), h->bm_tbl.as<unsigned short>(), L.gate, (unsigned *)nullptr,
-                           (unsigned short *)nullptr, L.par, L.npar, L.par_out);
-    }
-    BXMI_LAUNCH_CHECK();
-    return BXMI_OK;
+    // (padded runs: three more slots per thread)
+    const size_t lds = (size_t)(TILE + (L.pad ? 3 * THREADS : 0)) * 4 + BM_NB * 4 + BM_NB * 2 + 64;
+    if (L.pad && L.tot) return sort(bm_tile_sort_kernel<THREADS, ITEMS, true, 1, true>, THREADS, lds, h->bd_tend.as<unsigned>(), nullptr, h->bm_tesc.as<unsigned>());
+    if (L.pad) return sort(bm_tile_sort_kernel<THREADS, ITEMS, true>, THREADS, lds, h->bd_tend.as<unsigned>(), nullptr, nullptr);
+    return sort(bm_tile_sort_kernel<THREADS, ITEMS, false>, THREADS, lds, nullptr, nullptr, nullptr);
 }
 
 template <int THREADS, int ITEMS>
@@ -733,32 +710,18 @@ static int bm_launch_unpermute(const BmLaunch &L, unsigned long long *slots, hip
                                int fx = 0 /* 0, or FIND = 2 / 3 */)
 {
     bxmi_ivl *h = L.owner;
-    const size_t lds = (size_t)THREADS * ITEMS * sizeof(unsigned);
     if (!cnt) cnt = h->bm_recs.as<unsigned>();
-    if (loff && fx == 3) {
-        BXMI_TRY(allow_big_lds((bm_unpermute_kernel<THREADS, ITEMS, 3>), lds));
-        hipLaunchKernelGGL((bm_unpermute_kernel<THREADS, ITEMS, 3>), dim3((unsigned)L.ntp), dim3(THREADS), lds, st, cnt,
-                           h->bm_slots.as<unsigned short>(), L.segs, L.tile_seg, slots, L.gate, loff, h->fx_svq.as<unsigned>(),
-                           h->fx_parts.as<unsigned long long>(), h->fx_tile_tot.as<unsigned long long>());
-    } else if (loff && fx) {
-        BXMI_TRY(allow_big_lds((bm_unpermute_kernel<THREADS, ITEMS, 2>), lds));
-        hipLaunchKernelGGL((bm_unpermute_kernel<THREADS, ITEMS, 2>), dim3((unsigned)L.ntp), dim3(THREADS), lds, st, cnt,
-                           h->bm_slots.as<unsigned short>(), L.segs, L.tile_seg, slots, L.gate, loff, h->fx_svq.as<unsigned>(),
-                           h->fx_parts.as<unsigned long long>(), h->fx_tile_tot.as<unsigned long long>());
-    } else {
-        BXMI_TRY(allow_big_lds((bm_unpermute_kernel<THREADS, ITEMS>), lds));
-        hipLaunchKernelGGL((bm_unpermute_kernel<THREADS, ITEMS>), dim3((unsigned)L.ntp), dim3(THREADS), lds, st, cnt,
-                           h->bm_slots.as<unsigned short>(), L.segs, L.tile_seg, slots, L.gate, (unsigned *)nullptr);
-    }
-    BXMI_LAUNCH_CHECK();
-    return BXMI_OK;
+    const bool find = loff && fx;  // (the plain form leaves no offsets and none of what find_exchange.hpp reads)
+    auto unpermute = [&](auto kern) {
+        return launch_lds(kern, dim3((unsigned)L.ntp), dim3(THREADS), (size_t)THREADS * ITEMS * sizeof(unsigned), st, cnt, h->bm_slots.as<unsigned short>(), L.segs,
+                          L.tile_seg, slots, L.gate, find ? loff : nullptr, find ? h->fx_svq.as<unsigned>() : nullptr,
+                          find ? h->fx_parts.as<unsigned long long>() : nullptr, find ? h->fx_tile_tot.as<unsigned long long>() : nullptr);
+    };
+    if (find && fx == 3) return unpermute(bm_unpermute_kernel<THREADS, ITEMS, 3>);
+    if (find) return unpermute(bm_unpermute_kernel<THREADS, ITEMS, 2>);
+    return unpermute(bm_unpermute_kernel<THREADS, ITEMS>);
 }
 
-// The bitmap-cell pass over a batch of n segments (n sealed, qualifying indexes with their queries): [order check ->]
-// tile sort (with the batch's parameter block) -> run table -> plan -> search -> un-permute -> totals, all on `st`, six launches
-// for up to 16 segments (five when nobody asks for totals); with the order check in front or more segments the parameter kernel
-// is a launch of its own.
-// counts[i] may be NULL (total only: nothing is stored per query); totals_dev[i] may be.  The scratch of hs[0] serves the whole batch.
 #ifndef SL_FIND_U
 #define SL_FIND_U 2  // runs per lane group and round of find()'s count half
 #endif
@@ -766,17 +729,12 @@ template <int LANES>
 static int sl_launch_search(const BmLaunch &L, unsigned grid, hipStream_t st, unsigned *out, unsigned *hc = nullptr)
 {
     bxmi_ivl *h = L.owner;
-    if (out != h->bm_recs.as<unsigned>()) {
-        BXMI_TRY(allow_big_lds((sl_search_pipe_kernel<LANES, SL_FIND_U, true>), L.search_lds));
-        hipLaunchKernelGGL((sl_search_pipe_kernel<LANES, SL_FIND_U, true>), dim3(grid), dim3(SL_THREADS), L.search_lds, st, L.segs, h->bm_items.as<int4>() + 1,
-                           h->bm_items.as<int>(), h->bm_runT.as<unsigned>(), L.ntp, h->bm_recs.as<unsigned>(), out, L.tile_log2, L.gate, hc);
-    } else {
-        BXMI_TRY(allow_big_lds((sl_search_pipe_kernel<LANES, 2, false>), L.search_lds));
-        hipLaunchKernelGGL((sl_search_pipe_kernel<LANES, 2, false>), dim3(grid), dim3(SL_THREADS), L.search_lds, st, L.segs, h->bm_items.as<int4>() + 1,
-                           h->bm_items.as<int>(), h->bm_runT.as<unsigned>(), L.ntp, h->bm_recs.as<unsigned>(), (unsigned *)nullptr, L.tile_log2, L.gate);
-    }
-    BXMI_LAUNCH_CHECK();
-    return BXMI_OK;
+    const bool apart = out != h->bm_recs.as<unsigned>();  // find(): the counts apart from the records
+    auto search = [&](auto kern) {
+        return launch_lds(kern, dim3(grid), dim3(SL_THREADS), L.search_lds, st, L.segs, h->bm_items.as<int4>() + 1, h->bm_items.as<int>(), h->bm_runT.as<unsigned>(),
+                          L.ntp, h->bm_recs.as<unsigned>(), apart ? out : nullptr, L.tile_log2, L.gate, apart ? hc : nullptr);
+    };
+    return apart ? search(sl_search_pipe_kernel<LANES, SL_FIND_U, true>) : search(sl_search_pipe_kernel<LANES, 2, false>);
 }
 
 // find() through the exchange (count_slices.hpp): what the count half leaves behind for the fill half.
@@ -794,23 +752,17 @@ struct BmFindCtx {
 static int sl_launch_search_flat(const BmLaunch &L, unsigned grid, hipStream_t st)
 {
     bxmi_ivl *h = L.owner;
-    BXMI_TRY(allow_big_lds((sl_search_flat_kernel<4>), L.search_lds));
-    hipLaunchKernelGGL((sl_search_flat_kernel<4>), dim3(grid), dim3(SL_THREADS), L.search_lds, st, L.segs, h->bm_items.as<int4>() + 1,
-                       h->bm_items.as<int>(), h->bm_runT.as<unsigned>(), L.ntp, h->bm_recs.as<unsigned>(), L.tile_log2, L.gate);
-    BXMI_LAUNCH_CHECK();
-    return BXMI_OK;
+    return launch_lds(sl_search_flat_kernel<4>, dim3(grid), dim3(SL_THREADS), L.search_lds, st, L.segs, h->bm_items.as<int4>() + 1, h->bm_items.as<int>(),
+                      h->bm_runT.as<unsigned>(), L.ntp, h->bm_recs.as<unsigned>(), L.tile_log2, L.gate);
 }
 
 template <int FMT, bool QB, int EXP, int DEPTH, bool PIPE, bool PAD = false, bool W8 = false>
 static int bd_launch_search_t(const BmLaunch &L, unsigned grid, hipStream_t st)
 {
     bxmi_ivl *h = L.owner;
-    BXMI_TRY(allow_big_lds((bd_search_kernel<FMT, QB, EXP, DEPTH, PIPE, PAD, W8>), L.search_lds));
-    hipLaunchKernelGGL((bd_search_kernel<FMT, QB, EXP, DEPTH, PIPE, PAD, W8>), dim3(grid), dim3(BD_THREADS), L.search_lds, st, L.segs,
-                       h->bm_items.as<int4>() + 1, h->bm_items.as<int>(), h->bd_unitT.as<unsigned short>(), L.ntp, h->bm_recs.as<unsigned>(),
-                       h->bd_cnt16.as<unsigned short>(), L.tile_log2, L.gate);
-    BXMI_LAUNCH_CHECK();
-    return BXMI_OK;
+    return launch_lds(bd_search_kernel<FMT, QB, EXP, DEPTH, PIPE, PAD, W8>, dim3(grid), dim3(BD_THREADS), L.search_lds, st, L.segs, h->bm_items.as<int4>() + 1,
+                      h->bm_items.as<int>(), h->bd_unitT.as<unsigned short>(), L.ntp, h->bm_recs.as<unsigned>(), h->bd_cnt16.as<unsigned short>(), L.tile_log2,
+                      L.gate);
 }
 
 // the persistent walk on cell images (count_dense.hpp, bw_*): one workgroup per CU, items handed out per XCD
@@ -820,12 +772,9 @@ static int bw_launch_search(const BmLaunch &L, hipStream_t st)
     bxmi_ivl *h = L.owner;
     constexpr int THREADS = WIDE && !BIG ? BD_THREADS / 2 : BD_THREADS;  // offset cells: two workgroups per CU (the clumped layout: one)
     constexpr int DEPTH = 3;  // (offset cells with rings of 2 / 3 / 4: genome pass 0.719 / 0.722 / 0.705 ms, an eighth of it 0.150 / 0.150 / 0.152)
-    BXMI_TRY(allow_big_lds((bw_search_kernel<W8, DEPTH, WIDE, THREADS, TOT>), L.search_lds));
-    hipLaunchKernelGGL((bw_search_kernel<W8, DEPTH, WIDE, THREADS, TOT>), dim3(WIDE && !BIG ? 512 : 256), dim3(THREADS), L.search_lds, st, L.segs, h->bm_items.as<int4>() + 1,
-                       h->bm_items.as<int>(), h->bd_unitT.as<unsigned short>(), L.ntp, h->bm_recs.as<unsigned>(), h->bd_cnt16.as<unsigned short>(),
-                       L.tile_log2, L.gate, L.xcd_next, L.tot_slots);
-    BXMI_LAUNCH_CHECK();
-    return BXMI_OK;
+    return launch_lds(bw_search_kernel<W8, DEPTH, WIDE, THREADS, TOT>, dim3(WIDE && !BIG ? 512 : 256), dim3(THREADS), L.search_lds, st, L.segs,
+                      h->bm_items.as<int4>() + 1, h->bm_items.as<int>(), h->bd_unitT.as<unsigned short>(), L.ntp, h->bm_recs.as<unsigned>(),
+                      h->bd_cnt16.as<unsigned short>(), L.tile_log2, L.gate, L.xcd_next, L.tot_slots);
 }
 
 // One shape per stage and layout (round 3 kept every ring depth, both pipelines and the diagnostics behind knobs: 66 kernels):
@@ -833,9 +782,10 @@ static int bw_launch_search(const BmLaunch &L, hipStream_t st)
 //   dense images  padded runs: the ring of three hand-issued loads; packed runs (units of a single bucket): two sets of four;
 //   key slices    the lean shape (two passes per round, compiler-issued loads: 64 registers) -- two workgroups share a CU when
 //                 the units are small, one stages its unit while the other searches (a third of a sparse index's search time).
-static int bd_launch_search(const BmLaunch &L, unsigned grid, int fmt /* 0 dense, 1 cells, 2 slices */, bool blocks, hipStream_t st)
+// `fmt`: the images the walk reads -- Stage::Slices here is the flat walk on key slices (never padded: see bm_plan_pass).
+static int bd_launch_search(const BmLaunch &L, unsigned grid, Stage fmt, bool blocks, hipStream_t st)
 {
-    if (fmt == 1) {
+    if (fmt == Stage::Cells || fmt == Stage::OffsetCells) {
         if (!L.pad) return fail(BXMI_ESTATE, "bd_launch_search: cell images on packed runs");
         if (L.tot && L.big) return bw_launch_search<false, true, true, true>(L, st);
         if (L.tot) return L.wide ? bw_launch_search<false, true, true>(L, st) : bw_launch_search<false, false, true>(L, st);
@@ -843,7 +793,7 @@ static int bd_launch_search(const BmLaunch &L, unsigned grid, int fmt /* 0 dense
         if (L.wide) return L.w8 ? bw_launch_search<true, true>(L, st) : bw_launch_search<false, true>(L, st);
         return L.w8 ? bw_launch_search<true, false>(L, st) : bw_launch_search<false, false>(L, st);
     }
-    if (fmt == 2) return bd_launch_search_t<2, false, 0, 2, false>(L, grid, st);  // (never padded: see bm_count_segments)
+    if (fmt == Stage::Slices) return bd_launch_search_t<2, false, 0, 2, false>(L, grid, st);
 #ifndef BD_EXP_V
 #define BD_EXP_V 0  // diagnostics (compile time, wrong results): 1 = the dense walk without its look-ups
 #endif
@@ -855,23 +805,40 @@ template <int THREADS, int ITEMS>
 static int bd_launch_unpermute(const BmLaunch &L, unsigned long long *slots, hipStream_t st)
 {
     bxmi_ivl *h = L.owner;
-    if (L.pad && L.w8) {
-        const size_t lds = (size_t)(THREADS * ITEMS + BM_PAD_ROOM);
-        BXMI_TRY(allow_big_lds((bd_unpermute_kernel<THREADS, ITEMS, true, true>), lds));
-        hipLaunchKernelGGL((bd_unpermute_kernel<THREADS, ITEMS, true, true>), dim3((unsigned)L.ntp), dim3(THREADS), lds, st, h->bd_cnt16.as<unsigned short>(),
-                           h->bm_slots.as<unsigned short>(), L.segs, L.tile_seg, slots, L.gate, h->bd_tend.as<unsigned>(),
-                           h->bd_fb.as<unsigned long long>(), h->bd_fb_host);
-    } else if (L.pad) {
-        const size_t lds = (size_t)(THREADS * ITEMS + BM_PAD_ROOM) * sizeof(unsigned short);
-        BXMI_TRY(allow_big_lds((bd_unpermute_kernel<THREADS, ITEMS, true>), lds));
-        hipLaunchKernelGGL((bd_unpermute_kernel<THREADS, ITEMS, true>), dim3((unsigned)L.ntp), dim3(THREADS), lds, st, h->bd_cnt16.as<unsigned short>(),
-                           h->bm_slots.as<unsigned short>(), L.segs, L.tile_seg, slots, L.gate, h->bd_tend.as<unsigned>());
-    } else {
-        const size_t lds = (size_t)THREADS * ITEMS * sizeof(unsigned short);
-        BXMI_TRY(allow_big_lds((bd_unpermute_kernel<THREADS, ITEMS, false>), lds));
-        hipLaunchKernelGGL((bd_unpermute_kernel<THREADS, ITEMS, false>), dim3((unsigned)L.ntp), dim3(THREADS), lds, st, h->bd_cnt16.as<unsigned short>(),
-                           h->bm_slots.as<unsigned short>(), L.segs, L.tile_seg, slots, L.gate, (const unsigned *)nullptr);
-    }
+    const bool w8 = L.pad && L.w8;
+    auto unpermute = [&](auto kern, size_t count_bytes) {
+        return launch_lds(kern, dim3((unsigned)L.ntp), dim3(THREADS), (size_t)(THREADS * ITEMS + (L.pad ? BM_PAD_ROOM : 0)) * count_bytes, st,
+                          h->bd_cnt16.as<unsigned short>(), h->bm_slots.as<unsigned short>(), L.segs, L.tile_seg, slots, L.gate,
+                          L.pad ? h->bd_tend.as<unsigned>() : nullptr, w8 ? h->bd_fb.as<unsigned long long>() : nullptr, w8 ? h->bd_fb_host : nullptr);
+    };
+    if (w8) return unpermute(bd_unpermute_kernel<THREADS, ITEMS, true, true>, 1);
+    if (L.pad) return unpermute(bd_unpermute_kernel<THREADS, ITEMS, true>, sizeof(unsigned short));
+    return unpermute(bd_unpermute_kernel<THREADS, ITEMS, false>, sizeof(unsigned short));
+}
+
+// the sorted walk on cell images (count_dense.hpp, bs_walk_kernel) in the shape of the persistent walk: offset cells two workgroups
+// per CU, the clumped layout and bitmap cells one
+static int bs_launch_walk(const BmLaunch &L, const int4 *items, const int *n_items, unsigned long long *tslots, hipStream_t st)
+{
+    auto walk = [&](auto kern, unsigned grid, unsigned threads) {
+        return launch_lds(kern, dim3(grid), dim3(threads), L.search_lds, st, L.segs, items, n_items, tslots, L.gate, L.xcd_next, L.owner->bd_fb_host + 1, L.order_seq);
+    };
+    if (L.wide && L.big) return walk(bs_walk_kernel<true, BD_THREADS>, 256, BD_THREADS);
+    if (L.wide) return walk(bs_walk_kernel<true, BD_THREADS / 2>, 512, BD_THREADS / 2);
+    return walk(bs_walk_kernel<false, BD_THREADS>, 256, BD_THREADS);
+}
+
+// The search items from the units' query counts.  Few segments: the one-workgroup plan (11 us where bm_plan_kernel<2> takes 37 on
+// configs[4]'s 1526 tiles).
+static int bm_launch_plan(const BmLaunch &L, int chunk, hipStream_t st)
+{
+    bxmi_ivl *h = L.owner;
+    if (L.n_segs <= BD_PLAN_SEGS)
+        hipLaunchKernelGGL(bd_plan_kernel, dim3(1), dim3(1024), 0, st, h->sl_unitcnt.as<unsigned>(), L.n_segs, L.segs, chunk, h->bm_items.as<int4>() + 1,
+                           h->bm_items.as<int>(), L.gate);
+    else
+        hipLaunchKernelGGL(bm_plan_kernel<2>, dim3(BM_PLAN_BLOCKS), dim3(BM_PLAN_THREADS), 0, st, h->sl_unitcnt.as<unsigned>(), L.ngroups, L.segs, L.tile_seg,
+                           chunk, h->bm_items.as<int4>() + 1, h->bm_items.as<int>(), L.gate);
     BXMI_LAUNCH_CHECK();
     return BXMI_OK;
 }
@@ -888,194 +855,51 @@ static int ensure_feedback(bxmi_ivl *h, hipStream_t st)
     return BXMI_OK;
 }
 
-// `kind`: what a search workgroup keeps in LDS -- 2 = key slices (count_slices.hpp), 3 = dense unit images, 4 = cell images of
-// units (both count_dense.hpp: the flat walk, counts out of place); every index of the batch must have qualified for it.
-// (kind 1 -- images of single buckets / bucket pairs, round 2's search -- is gone: an index it served qualifies for the cell
-// images of units as well, so no input selected it any more.)
-static int bm_count_segments(bxmi_ivl *const *hs, int n, const int32_t *const *qs, const int32_t *const *qe, const int64_t *nq,
-                             int32_t *const *counts, int64_t *const *totals_dev, hipStream_t st, int kind, BmFindCtx *fx = nullptr)
+// count_plan.hpp mirrors the layout constants its sizes depend on
+static_assert(PLAN_NB == BM_NB && PLAN_GROUP_TILES == BM_GROUP_TILES && PLAN_CHUNK == BM_CHUNK && PLAN_PAR_CHUNK == BM_PAR_CHUNK &&
+                  PLAN_PAD_ROOM == BM_PAD_ROOM && PLAN_PART_Q == BM_PART_Q && PLAN_SLOTS == PT_SLOTS && PLAN_WALK_THREADS == BD_THREADS &&
+                  PLAN_NBK == FX_NBK && PLAN_BOUNDS_ROW == BS_BOUNDS_ROW && PLAN_ITEM_BYTES == sizeof(int4),
+              "count_plan.hpp and the device headers disagree on a layout constant");
+
+static BmPlanKnobs bm_plan_knobs()
 {
-    if (kind < 2 || kind > 5) return fail(BXMI_EINVAL, "bm_count_segments: no such search stage (%d)", kind);
-    const bool wide = kind == 5;  // offset cells: the cell images of sparse indexes
-    const bool slices = kind == 2, cells = kind == 4 || wide;
-    const bool fxsub = fx && fx->sub;
-    // (find() needs 32-bit counts apart from the records and the tile-sorted offsets: the flat walk has that form for find_exchange.hpp only)
-    const bool slices_flat = slices && !fx && g_opt_sl_flat != 0;
-    const bool dense = kind == 3 || cells || slices_flat /* the flat walk */;
-    bxmi_ivl *h = hs[0];
-    int64_t nq_all = 0;
-    for (int i = 0; i < n; i++) nq_all += nq[i];
-    if (nq_all >= ((int64_t)1 << 31)) return fail(BXMI_EINVAL, "bxmi_ivl_count: more than 2^31 queries in one batch");
-    if (n > 4096) return fail(BXMI_EINVAL, "bxmi_ivl_count_multi: more than 4096 indexes in one batch");
-    // tile shape: 32768-query tiles halve the number of (tile, bucket) runs the search has to fetch, but their sort
-    // kernel runs one workgroup per CU and wants a grid of several hundred full tiles
-    // (a batch over several indexes: every segment starts on a group of 64 tiles, so the big tiles only where the segments are
-    // big too -- a genome of 100 M queries, not its eighth on one of eight GPUs)
-    int variant = g_opt_bm_variant >= 0 ? (int)g_opt_bm_variant : (nq_all >= ((int64_t)32 << 20) * (n == 1 ? 1 : 2) ? 2 : 0);
-    // cell images are searched on padded runs only: a unit of two buckets needs a tile sort whose threads own two buckets each
-    // (the 1024-thread shapes), the 512-thread shape owns four
-    // ... and the 1024-thread shape is the faster sort for cell images whatever the unit (a rank's share of a genome, offset cells,
-    // f >= 2: 0.413 / 0.241 / 0.138 ms for 50 / 25 / 13 M queries against 0.432 / 0.259 / 0.147 with 512 threads x 32 queries)
-    if (cells && variant == 0 && g_opt_bm_variant < 0) variant = 1;
-    if (cells && variant == 0)
-        for (int i = 0; i < n; i++)
-            if ((wide ? hs[i]->bo_geom : hs[i]->bp_geom).f < 2) variant = 1;
-    if (fxsub && (n != 1 || !slices)) return fail(BXMI_ESTATE, "bm_count_segments: the half-bucket order serves find() on one index's slices");
-    if (fxsub && variant == 0) variant = 1;  // (the half-bucket tile sort has the 1024-thread shapes only)
-    const int tile_log2 = variant == 2 ? 15 : 14;
-    const int64_t tile = (int64_t)1 << tile_log2;
-    // the batch's tile numbering: every segment starts on a plan-group boundary
-    std::vector<BmSeg> segs((size_t)n);
-    int64_t ntp = 0;
-    size_t max_stride = 0, sl_lds = 0;
-    int64_t sl_run = INT64_MAX;  // shortest expected (tile, unit) run of the batch
-    bool any_total = false, any_blocks = false;
-    for (int i = 0; i < n; i++) {
-        BmSeg &sg = segs[(size_t)i];
-        any_blocks |= kind == 3 && hs[i]->bd_blocks;
-        if (slices) {
-            size_t lds = 0;
-            int64_t run_len = 0;
-            sg.g = sl_geom(hs[i], tile, &lds, &run_len);
-            if (lds > sl_lds) sl_lds = lds;
-            if (run_len < sl_run) sl_run = run_len;
-        } else if (cells) {
-            sg.g = wide ? hs[i]->bo_geom : hs[i]->bp_geom;
-        } else {
-            sg.g = hs[i]->bd_geom;
-        }
-        sg.qs = qs[i], sg.qe = qe[i], sg.counts = counts[i];
-        sg.nq = nq[i];
-        sg.tile0 = ntp;
-        sg.ntiles = div_up(nq[i], tile);
-        sg.dimages = hs[i]->bd_images.as<unsigned char>();
-        sg.pimages = wide ? hs[i]->bo_images.as<unsigned char>() : hs[i]->bp_images.as<unsigned char>();
-        sg.smeta = slices ? hs[i]->sl_meta.as<int4>() : nullptr;
-        sg.ix = index_dev(hs[i]);
-        sg.e_sorted = hs[i]->e_sorted.as<int32_t>();
-        ntp += div_up(sg.ntiles, BM_GROUP_TILES) * BM_GROUP_TILES;
-        sg.tile_end = ntp;
-        if ((size_t)sg.g.stride > max_stride) max_stride = (size_t)sg.g.stride;
-        any_total |= totals_dev && totals_dev[i];
-    }
-    if (ntp == 0) return BXMI_OK;
-    const int ngroups = (int)(ntp / BM_GROUP_TILES);
-    // PAIR: a search workgroup holds the images of two neighbouring buckets (needs both in one CU's LDS)
-    int chunk = dense ? (g_opt_bd_chunk ? (int)g_opt_bd_chunk : (cells || slices_flat ? 2 : 4) * BM_CHUNK) : g_opt_bm_chunk ? (int)g_opt_bm_chunk : BM_CHUNK;
-    // a small batch (one rank's share of a genome on eight GPUs: 13 M queries) cut into items of 128 Ki queries is a hundred
-    // workgroups on 256 CUs (measured: search 154 us of a 255 us pass); items of nq / 512, at least a tile
-    // (every item stages its unit's keys again: at 25 M queries, 192 items, the smaller items already cost more than
-    // the idle CUs did -- 0.33 -> 0.38 ms -- so only batches that leave a third of the chip idle are cut finer)
-    if (!(dense ? g_opt_bd_chunk : g_opt_bm_chunk) && !(kind == 3 || cells) && nq_all / chunk < 160) {
-        const int64_t c = nq_all / 512;
-        chunk = (int)(c < 16384 ? 16384 : c);
-    }
-    int64_t max_items = (int64_t)n * (BM_NB + 2) + 2 * (nq_all / chunk) + 2;
-    if (dense) {  // every segment has at most BM_NB >> f units; empty workgroups of 157 KB of LDS are not free
-        // (the padded layout counts up to three more slots per tile and unit as "queries" of the unit)
-        int64_t pad_slots = 0;
-        for (int i = 0; i < n; i++) pad_slots += 3 * (int64_t)(BM_NB >> segs[(size_t)i].g.f) * (segs[(size_t)i].tile_end - segs[(size_t)i].tile0);
-        max_items = 2 * ((nq_all + pad_slots) / chunk) + 2;
-        for (int i = 0; i < n; i++) max_items += (BM_NB >> segs[(size_t)i].g.f) + 2;
-    }
-    // PAD: every unit's run of a tile on whole 16-byte slots (the search's load ring needs one store per pass); the tile
-    // sort's scan keeps a unit inside one thread or a few neighbouring lanes
-    bool pad = kind == 3 || cells;
-    for (int i = 0; i < n && pad; i++) pad = (1 << segs[(size_t)i].g.f) >= (variant == 0 ? 4 : 2);
-    const int64_t tile_stride = tile + (pad ? BM_PAD_ROOM : 0);
-    // nobody wants counts, only totals, and the persistent walk serves the batch: it keeps the totals itself (bw_search_kernel<.., TOT>)
-    bool tot_walk = g_opt_tot_walk != 0 && cells && pad && !fx && any_total;
-    for (int i = 0; i < n && tot_walk; i++) tot_walk = counts[i] == nullptr;
-    if (tot_walk) BXMI_TRY(h->bm_tesc.reserve((size_t)ntp * 4));
-    BXMI_TRY(h->bm_recs.reserve((size_t)ntp * tile_stride * 4));
-    if (pad) BXMI_TRY(h->bd_tend.reserve((size_t)ntp * 4));
-    BXMI_TRY(h->bm_slots.reserve((size_t)ntp * tile * 2));
-    BXMI_TRY(h->bm_tbl.reserve((size_t)ntp * BM_NB * 2));
-    if (!dense) BXMI_TRY(h->bm_runT.reserve((size_t)ntp * BM_NB * 4));
-    if (dense) BXMI_TRY(h->bd_unitT.reserve((size_t)ntp * (BM_NB + 1) * 2));  // (+ the row behind the last unit)
-    BXMI_TRY(h->bm_grpcnt.reserve((size_t)ngroups * BM_NB * 4));
-    BXMI_TRY(h->sl_unitcnt.reserve((size_t)ngroups * BM_NB * 4));
-    if (dense && !fxsub) BXMI_TRY(h->bd_cnt16.reserve((size_t)ntp * tile_stride * 2));
-    BXMI_TRY(h->bm_items.reserve((size_t)(max_items + 2) * sizeof(int4)));  // [0] = the item count, items from [1]
-    if (fx) {  // find(): counts apart from the records, and the tile-sorted offsets
-        BXMI_TRY(h->sl_cnt.reserve((size_t)ntp * tile * 4));
-        BXMI_TRY(h->sl_loff.reserve((size_t)ntp * tile * 4));
-    }
-    if (fxsub) {  // ... and what find_exchange.hpp's fill and copy read
-        BXMI_TRY(h->fx_tbl2.reserve((size_t)ntp * FX_NBK * 2));
-        BXMI_TRY(h->fx_runT2.reserve((size_t)ntp * FX_NBK * 4));
-        BXMI_TRY(h->fx_hc.reserve((size_t)ntp * tile * 4));
-        BXMI_TRY(h->fx_svq.reserve((size_t)ntp * tile * 4));
-        BXMI_TRY(h->fx_parts.reserve((size_t)ntp * (tile / BM_PART_Q) * 8));
-        BXMI_TRY(h->fx_tile_tot.reserve((size_t)ntp * 8));
-        BXMI_TRY(h->fx_tile_base.reserve((size_t)(ntp + 2) * 8));  // (+ the grand total, + the largest tile total)
-        fx->f = segs[0].g.f;
-        fx->ntiles = segs[0].ntiles;
-    }
-    unsigned *search_out = fx ? h->sl_cnt.as<unsigned>() : h->bm_recs.as<unsigned>();
-    // parameter block in HBM: [segments][totals pointers][tile -> segment], written by bm_params_kernel from its arguments
-    const size_t seg_bytes = (size_t)n * sizeof(BmSeg), tot_bytes = (size_t)n * sizeof(void *);
-    const size_t tile_off = (seg_bytes + tot_bytes + 15) & ~(size_t)15, par_bytes = tile_off + (size_t)ntp * sizeof(unsigned short);
-    BXMI_TRY(h->bm_params.reserve(par_bytes));
-    // [segments][PT_SLOTS partial totals], then the flag: 1 = the starts are NOT sorted
-    // ([+0] the order flag, [+4 .. +8) the search's item counters)
-    BXMI_TRY(h->p_slots.reserve(((size_t)n * PT_SLOTS + 8) * sizeof(unsigned long long)));
-    unsigned long long *slots = h->p_slots.as<unsigned long long>();
-    // (several indexes: only the walk on cell images has a sorted-batch form over segments)
-    bool multi_sorted = n > 1 && !fx && g_opt_sorted_path && g_opt_sorted_cells != 0 && cells && pad;
-    for (int i = 0; i < n && multi_sorted; i++) multi_sorted = nq[i] < ((int64_t)1 << 32) - 8;
-    unsigned *unsorted = g_opt_sorted_path && (n == 1 || multi_sorted) && !fx ? reinterpret_cast<unsigned *>(slots + (size_t)n * PT_SLOTS) : nullptr;
-    // The order check and the stand-down of the sorted-batch kernel cost a shuffled batch 24 us (of 750).  What the order
-    // checks find is mirrored into host memory (ivl_local_count_kernel, bs_walk_kernel or the workgroup that runs the probe write it, nobody waits for
-    // it): after two batches in a row that were NOT sorted the check is no longer launched -- every kernel of the exchange
-    // runs unconditionally -- and a PROBE rides on the parameter kernel instead: 8192 consecutive starts; a descent among
-    // them says "shuffled" for certain, none brings the exact check back with the next call.  A sorted batch that arrives
-    // in between goes through the exchange (0.78 instead of 0.62 ms per 100 M), exact as ever.  (Watching the order
-    // exactly inside the tile sort, which has every start in registers, cost that kernel 13-19 us -- what the check costs.)
-    unsigned *descent = nullptr;
-    unsigned long long order_seq = 0;
-    if (unsorted) {
-        BXMI_TRY(ensure_feedback(h, st));
-        const unsigned long long seen = reinterpret_cast<volatile unsigned long long *>(h->bd_fb_host)[1];
-        if ((seen >> 1) > h->order_seen) {
-            h->unsorted_streak = (seen & 1ull) ? h->unsorted_streak + 1 : 0;
-            h->order_seen = seen >> 1;
-            h->order_skip = h->unsorted_streak >= 2;
-        }
-        if (h->order_seq == 0 && g_opt_order_skip != 0) {
-            // The handle's first large batch: nothing is known about the caller's order yet, and this call has waited for the
-            // device already (it built the index's images) -- so the probe is asked alone and its answer read back: a descent
-            // among its 8192 starts drops the exact check from this very pass (a cold pass paid 24 us of 700 for it).
-            hipLaunchKernelGGL(bm_probe_kernel, dim3(1), dim3(256), 0, st, qs[0], nq[0], unsorted);
-            unsigned seen_descent = 0;
-            BXMI_HIP(hipMemcpyAsync(&seen_descent, unsorted, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-            BXMI_HIP(hipStreamSynchronize(st));
-            if (seen_descent) h->unsorted_streak = 2, h->order_skip = true;
-        }
-        order_seq = ++h->order_seq;
-        if (h->order_skip && g_opt_order_skip != 0) descent = unsorted, unsorted = nullptr;  // (the word is zeroed with the partial totals)
-    }
-    BmLaunch L;
+    BmPlanKnobs k;
+    k.bm_variant = g_opt_bm_variant, k.sl_flat = g_opt_sl_flat, k.bd_chunk = g_opt_bd_chunk, k.bm_chunk = g_opt_bm_chunk, k.sl_lanes = g_opt_sl_lanes;
+    k.bd_w8 = g_opt_bd_w8, k.tot_walk = g_opt_tot_walk, k.sorted_path = g_opt_sorted_path, k.sorted_cells = g_opt_sorted_cells;
+    k.order_skip = g_opt_order_skip;
+    return k;
+}
+
+// The scratch of one pass, as the plan sizes it (grow-only, in the first handle; the sorted walk's plan follows the order probe).
+static int bm_reserve(bxmi_ivl *h, const BmPassPlan::Bytes &b)
+{
+    const struct { DevBuf *buf; size_t bytes; } want[] = {
+        {&h->bm_tesc, b.tesc}, {&h->bm_recs, b.recs}, {&h->bd_tend, b.tend}, {&h->bm_slots, b.slots}, {&h->bm_tbl, b.tbl}, {&h->bm_runT, b.runT},
+        {&h->bd_unitT, b.unitT}, {&h->bm_grpcnt, b.grpcnt}, {&h->sl_unitcnt, b.unitcnt}, {&h->bd_cnt16, b.cnt16}, {&h->bm_items, b.items},
+        {&h->sl_cnt, b.sl_cnt}, {&h->sl_loff, b.sl_loff}, {&h->fx_tbl2, b.fx_tbl2}, {&h->fx_runT2, b.fx_runT2}, {&h->fx_hc, b.fx_hc}, {&h->fx_svq, b.fx_svq},
+        {&h->fx_parts, b.fx_parts}, {&h->fx_tile_tot, b.fx_tile_tot}, {&h->fx_tile_base, b.fx_tile_base}, {&h->bm_params, b.params}, {&h->p_slots, b.p_slots}};
+    for (const auto &w : want) BXMI_TRY(w.buf->reserve(w.bytes));
+    return BXMI_OK;
+}
+
+// The batch's parameter block in HBM -- [segments][totals pointers][tile -> segment] -- written on the device from kernel arguments:
+// by the tile sort's first workgroup (P.fold_params: the block rides in L.par) or by bm_params_kernel, BM_PAR_CHUNK segments a launch.
+static int bm_set_params(BmLaunch &L, const BmPassPlan &P, const std::vector<BmSeg> &segs, int64_t *const *totals_dev, unsigned long long *slots, hipStream_t st)
+{
+    bxmi_ivl *h = L.owner;
+    const int n = P.n;
+    unsigned char *block = h->bm_params.as<unsigned char>();
+    BmParOut po;
+    po.segs = reinterpret_cast<BmSeg *>(block);
+    po.totals = reinterpret_cast<unsigned long long **>(block + P.seg_bytes);
+    po.tile_seg = reinterpret_cast<unsigned short *>(block + P.tile_off);
+    po.zero_u64 = slots, po.n_zero = P.n_zero;
+    po.n_items = h->bm_items.as<int>();
+    po.probe = L.descent;
+    po.order_host = L.descent ? h->bd_fb_host + 1 : nullptr, po.order_seq = L.order_seq;
+    L.segs = po.segs, L.tile_seg = po.tile_seg;
     memset(&L.par, 0, sizeof(L.par));
-    // Folded: whenever the tile sort is the batch's first kernel.  With the order check in front (a handle's first batches, sorted
-    // input) or more than BM_PAR_CHUNK segments (a whole genome on one GPU) the parameter kernel stays a launch of its own.
-    const bool fold_params = n <= BM_PAR_CHUNK && !unsorted;
-    const int n_zero = n * PT_SLOTS + 8;
-    if (fold_params) {
-        for (int i = 0; i < n; i++) {
-            L.par.seg[i] = segs[(size_t)i];
-            L.par.total[i] = totals_dev ? reinterpret_cast<unsigned long long *>(totals_dev[i]) : nullptr;
-        }
-        L.npar = n;
-        L.par_out.segs = h->bm_params.as<BmSeg>();
-        L.par_out.totals = reinterpret_cast<unsigned long long **>(h->bm_params.as<unsigned char>() + seg_bytes);
-        L.par_out.tile_seg = reinterpret_cast<unsigned short *>(h->bm_params.as<unsigned char>() + tile_off);
-        L.par_out.zero_u64 = slots, L.par_out.n_zero = n_zero;
-        L.par_out.n_items = h->bm_items.as<int>();
-        L.par_out.probe = descent;
-        L.par_out.order_host = descent ? h->bd_fb_host + 1 : nullptr, L.par_out.order_seq = order_seq;
-    }
-    for (int first = 0; first < n && !fold_params; first += BM_PAR_CHUNK) {
+    for (int first = 0; first < n; first += BM_PAR_CHUNK) {
         BmSegChunk c;
         memset(&c, 0, sizeof(c));
         const int cnt = n - first < BM_PAR_CHUNK ? n - first : BM_PAR_CHUNK;
@@ -1083,192 +907,208 @@ static int bm_count_segments(bxmi_ivl *const *hs, int n, const int32_t *const *q
             c.seg[i] = segs[(size_t)(first + i)];
             c.total[i] = totals_dev ? reinterpret_cast<unsigned long long *>(totals_dev[first + i]) : nullptr;
         }
-        hipLaunchKernelGGL(bm_params_kernel, dim3((unsigned)cnt), dim3(256), 0, st, c, first, h->bm_params.as<BmSeg>(),
-                           reinterpret_cast<unsigned long long **>(h->bm_params.as<unsigned char>() + seg_bytes),
-                           reinterpret_cast<unsigned short *>(h->bm_params.as<unsigned char>() + tile_off), slots, n_zero,
-                           h->bm_items.as<int>(), first == 0 ? descent : (unsigned *)nullptr, descent ? h->bd_fb_host + 1 : (unsigned long long *)nullptr,
-                           order_seq);
+        if (P.fold_params) {  // (at most one chunk)
+            L.par = c, L.npar = n, L.par_out = po;
+            return BXMI_OK;
+        }
+        hipLaunchKernelGGL(bm_params_kernel, dim3((unsigned)cnt), dim3(256), 0, st, c, first, po.segs, po.totals, po.tile_seg, slots, P.n_zero, po.n_items,
+                           first == 0 ? L.descent : (unsigned *)nullptr, po.order_host, L.order_seq);
     }
     BXMI_LAUNCH_CHECK();
-    unsigned long long *tslots = any_total ? slots : nullptr;
-    L.segs = h->bm_params.as<BmSeg>();
-    L.tile_seg = reinterpret_cast<const unsigned short *>(h->bm_params.as<unsigned char>() + tile_off);
-    L.owner = h;
-    L.ntp = ntp, L.ngroups = ngroups, L.tile_log2 = tile_log2;
-    L.search_lds = slices ? sl_lds : max_stride * 16;
-    if (slices_flat && L.search_lds < 4096) L.search_lds = 4096;
-    L.gate = unsorted;
-    L.descent = descent;
-    L.pad = pad;
-    L.wide = wide;
-    L.xcd_next = reinterpret_cast<unsigned *>(slots + (size_t)n * PT_SLOTS + 4);
-    L.n_segs = n;
-    L.tot = tot_walk, L.tot_slots = slots;
-    L.big = wide && max_stride * 16 > (size_t)10 * (BD_THREADS / 2) * 16;  // (beyond what the 512-thread walk loads: 80 KB)
-    // 8-bit counts (0xFF = recomputed by the un-permute kernel, exact either way): half the bytes of the second exchange
-    // when the counts are small.  Cell images only serve indexes without piled-up coordinates, so the density says what to
-    // expect: fewer than 128 targets per 2048 coordinates (configs[1]: 82; a count of 255 needs a query of ~6000).  What the
-    // prediction misses -- long queries, targets crowded into part of the span -- the feedback catches: once more than one
-    // count in 64 did not fit, the index keeps 16-bit counts (worst case before that: every count recomputed, ~2 x the pass).
-    L.w8 = false;
-    // (a batch over several indexes -- a genome -- keeps the feedback with its first index: every index has to be sparse enough,
-    // none may have switched the narrow counts off)
-    if (pad && cells && g_opt_bd_w8 != 0 && !tot_walk) {  // (a total-only walk stores no counts at all)
-        BXMI_TRY(ensure_feedback(h, st));
-        const unsigned long long wide_counts = *reinterpret_cast<volatile unsigned long long *>(h->bd_fb_host);
-        if ((int64_t)wide_counts * 64 > h->w8_queries && wide_counts > 4096) h->w8_off = true;
-        bool narrow = true;
-        for (int i = 0; i < n; i++) {
-            const int64_t span = (int64_t)hs[i]->cmax - (int64_t)hs[i]->geom.cmin + 1;
-            narrow = narrow && !hs[i]->w8_off && (int64_t)hs[i]->n * 2048 < span * 128;
-            if (wide && hs[i]->bo_state == 2) narrow = false;  // (the clumped layout: hundreds of targets around every hot spot -- its first pass on 8-bit counts recomputed all of them: 24 ms)
-        }
-        L.w8 = g_opt_bd_w8 > 0 || narrow;
-        if (L.w8) h->w8_queries += nq_all;
-    }
-    if (unsorted) {
-        // one index, its batch possibly sorted by start already: one pass over the queries as they lie then, and every
-        // kernel below stands down (the local kernel exits at once otherwise)
-        // Cell images (bitmap or offset cells): a sorted batch is answered straight from them, stretch by stretch (count_dense.hpp,
-        // bs_*): the order check leaves where every unit's queries begin, a plan cuts long stretches, the walk loads a unit's
-        // image and answers its queries as they lie.  Other stages keep the first-generation kernel for sorted batches below.
-        const bool sorted_on_cells = cells && pad && g_opt_sorted_cells != 0 && nq[0] < ((int64_t)1 << 32) - 8;
-        if (multi_sorted) {
-            // a batch over several indexes: order check and plan per segment, one walk (count_dense.hpp, bs_*_multi)
-            const unsigned chunk = (unsigned)(g_opt_bd_chunk ? g_opt_bd_chunk : (wide ? 1 : 2) * BM_CHUNK);
-            size_t max_sorted_items = 4;
-            for (int i = 0; i < n; i++) max_sorted_items += (size_t)(BM_NB >> segs[(size_t)i].g.f) + 4 + (size_t)(nq[i] / chunk);
-            const size_t bounds_bytes = ((size_t)n * BS_BOUNDS_ROW * 4 + 16 + 15) & ~(size_t)15;
-            BXMI_TRY(h->bs_plan.reserve(bounds_bytes + (max_sorted_items + 1) * sizeof(int4)));
-            unsigned *bounds_all = h->bs_plan.as<unsigned>();
-            int *n_sorted = reinterpret_cast<int *>(bounds_all + (size_t)n * BS_BOUNDS_ROW);
-            int4 *sorted_items = reinterpret_cast<int4 *>(h->bs_plan.as<unsigned char>() + bounds_bytes);
-            BXMI_HIP(hipMemsetAsync(n_sorted, 0, sizeof(int), st));
-            hipLaunchKernelGGL(bs_check_multi_kernel, dim3((unsigned)(ntp < 2048 ? ntp : 2048)), dim3(256), 0, st, L.segs, L.tile_seg, ntp, tile_log2, unsorted, bounds_all);
-            hipLaunchKernelGGL(bs_plan_multi_kernel, dim3((unsigned)n), dim3(1024), 0, st, L.segs, bounds_all, chunk, sorted_items, n_sorted, unsorted);
-            if (wide && L.big) {
-                BXMI_TRY(allow_big_lds((bs_walk_kernel<true, BD_THREADS>), L.search_lds));
-                hipLaunchKernelGGL((bs_walk_kernel<true, BD_THREADS>), dim3(256), dim3(BD_THREADS), L.search_lds, st, L.segs, sorted_items, n_sorted, tslots,
-                                   unsorted, L.xcd_next, h->bd_fb_host + 1, order_seq);
-            } else if (wide) {
-                BXMI_TRY(allow_big_lds((bs_walk_kernel<true, BD_THREADS / 2>), L.search_lds));
-                hipLaunchKernelGGL((bs_walk_kernel<true, BD_THREADS / 2>), dim3(512), dim3(BD_THREADS / 2), L.search_lds, st, L.segs, sorted_items, n_sorted, tslots,
-                                   unsorted, L.xcd_next, h->bd_fb_host + 1, order_seq);
-            } else {
-                BXMI_TRY(allow_big_lds((bs_walk_kernel<false, BD_THREADS>), L.search_lds));
-                hipLaunchKernelGGL((bs_walk_kernel<false, BD_THREADS>), dim3(256), dim3(BD_THREADS), L.search_lds, st, L.segs, sorted_items, n_sorted, tslots,
-                                   unsorted, L.xcd_next, h->bd_fb_host + 1, order_seq);
-            }
-            BXMI_LAUNCH_CHECK();
-        } else if (sorted_on_cells) {
-            const BmGeom &g0 = segs[0].g;
-            const int units = BM_NB >> g0.f;
-            const unsigned chunk = (unsigned)(g_opt_bd_chunk ? g_opt_bd_chunk : (wide ? 1 : 2) * BM_CHUNK);
-            const size_t max_sorted_items = (size_t)units + 4 + (size_t)(nq[0] / chunk);
-            BXMI_TRY(h->bs_plan.reserve((size_t)(units + 2) * 4 + 16 + (max_sorted_items + 1) * sizeof(int4)));
-            BmBounds B;
-            B.bounds = h->bs_plan.as<unsigned>(), B.cmin = g0.cmin, B.ulog = g0.shift + g0.f, B.units = units;
-            int *n_sorted = reinterpret_cast<int *>(B.bounds + units + 2);
-            int4 *sorted_items = reinterpret_cast<int4 *>(h->bs_plan.as<unsigned char>() + (((size_t)(units + 2) * 4 + 16 + 15) & ~(size_t)15));
-            hipLaunchKernelGGL(bm_sorted_check_kernel<true>, dim3(2048), dim3(256), 0, st, qs[0], nq[0], unsorted, B);
-            hipLaunchKernelGGL(bs_plan_kernel, dim3(1), dim3(1024), 0, st, B.bounds, units, (unsigned)nq[0], chunk, sorted_items, n_sorted, unsorted);
-            if (wide && L.big) {
-                BXMI_TRY(allow_big_lds((bs_walk_kernel<true, BD_THREADS>), L.search_lds));
-                hipLaunchKernelGGL((bs_walk_kernel<true, BD_THREADS>), dim3(256), dim3(BD_THREADS), L.search_lds, st, L.segs, sorted_items, n_sorted, tslots,
-                                   unsorted, L.xcd_next, h->bd_fb_host + 1, order_seq);
-            } else if (wide) {
-                BXMI_TRY(allow_big_lds((bs_walk_kernel<true, BD_THREADS / 2>), L.search_lds));
-                hipLaunchKernelGGL((bs_walk_kernel<true, BD_THREADS / 2>), dim3(512), dim3(BD_THREADS / 2), L.search_lds, st, L.segs, sorted_items, n_sorted, tslots,
-                                   unsorted, L.xcd_next, h->bd_fb_host + 1, order_seq);
-            } else {
-                BXMI_TRY(allow_big_lds((bs_walk_kernel<false, BD_THREADS>), L.search_lds));
-                hipLaunchKernelGGL((bs_walk_kernel<false, BD_THREADS>), dim3(256), dim3(BD_THREADS), L.search_lds, st, L.segs, sorted_items, n_sorted, tslots,
-                                   unsorted, L.xcd_next, h->bd_fb_host + 1, order_seq);
-            }
-            BXMI_LAUNCH_CHECK();
-        } else {
+    return BXMI_OK;
+}
+
+// The order check in front of a pass, with the sorted batch's answer: every kernel of the exchange behind it stands down on a sorted batch,
+// the kernels here exit at once on any other.  P.multi_sorted / P.sorted_on_cells: from the cell images (count_dense.hpp, bs_*: the check
+// leaves where every unit's queries begin, a plan cuts long stretches, one walk); else the first-generation kernel for sorted batches.
+static int bm_launch_sorted(const BmLaunch &L, const BmPassPlan &P, const int32_t *const *qs, const int32_t *const *qe, const int64_t *nq, int32_t *const *counts,
+                            unsigned long long *tslots, hipStream_t st)
+{
+    bxmi_ivl *h = L.owner;
+    unsigned *unsorted = const_cast<unsigned *>(L.gate);
+    if (!P.multi_sorted && !P.sorted_on_cells) {
         hipLaunchKernelGGL(bm_sorted_check_kernel<false>, dim3(2048), dim3(256), 0, st, qs[0], nq[0], unsorted, BmBounds{nullptr, 0, 0, 0});
         TreeDev S = h->treeS.dev, E = h->treeE.dev;
         S.lds_from = S.nlev, S.lds_ints = 0, E.lds_from = E.nlev, E.lds_ints = 0;  // walk the global levels only
         const int64_t nchunks = div_up(nq[0], LC_CHUNK);
-        hipLaunchKernelGGL(ivl_local_count_kernel, dim3((unsigned)nchunks), dim3(LC_THREADS), 0, st, S, E, index_dev(h), h->e_sorted.as<int32_t>(),
-                           qs[0], qe[0], nq[0], counts[0], tslots, unsorted, (int32_t *)nullptr, h->bd_fb_host + 1, order_seq);
+        hipLaunchKernelGGL(ivl_local_count_kernel, dim3((unsigned)nchunks), dim3(LC_THREADS), 0, st, S, E, index_dev(h), h->e_sorted.as<int32_t>(), qs[0], qe[0],
+                           nq[0], counts[0], tslots, unsorted, (int32_t *)nullptr, h->bd_fb_host + 1, L.order_seq);
         BXMI_LAUNCH_CHECK();
-        }
+        return BXMI_OK;
     }
-    if (variant == 2)
-        BXMI_TRY((bm_launch_tiles<1024, 32>(L, st, fxsub)));
-    else if (variant == 1)
-        BXMI_TRY((bm_launch_tiles<1024, 16>(L, st, fxsub)));
+    // [unit bounds][item count][items], the items on the next 16 bytes
+    unsigned *bounds = h->bs_plan.as<unsigned>();
+    int4 *items = reinterpret_cast<int4 *>(h->bs_plan.as<unsigned char>() + ((P.bounds_bytes + 15) & ~(size_t)15));
+    if (P.multi_sorted) {  // order check and plan per segment
+        int *n_items = reinterpret_cast<int *>(bounds + (size_t)P.n * BS_BOUNDS_ROW);
+        BXMI_HIP(hipMemsetAsync(n_items, 0, sizeof(int), st));
+        hipLaunchKernelGGL(bs_check_multi_kernel, dim3((unsigned)(L.ntp < 2048 ? L.ntp : 2048)), dim3(256), 0, st, L.segs, L.tile_seg, L.ntp, L.tile_log2, unsorted, bounds);
+        hipLaunchKernelGGL(bs_plan_multi_kernel, dim3((unsigned)P.n), dim3(1024), 0, st, L.segs, bounds, P.sorted_chunk, items, n_items, unsorted);
+        return bs_launch_walk(L, items, n_items, tslots, st);
+    }
+    const int units = BM_NB >> L.g0.f;
+    BmBounds B;
+    B.bounds = bounds, B.cmin = L.g0.cmin, B.ulog = L.g0.shift + L.g0.f, B.units = units;
+    int *n_items = reinterpret_cast<int *>(bounds + units + 2);
+    hipLaunchKernelGGL(bm_sorted_check_kernel<true>, dim3(2048), dim3(256), 0, st, qs[0], nq[0], unsorted, B);
+    hipLaunchKernelGGL(bs_plan_kernel, dim3(1), dim3(1024), 0, st, bounds, units, (unsigned)nq[0], P.sorted_chunk, items, n_items, unsorted);
+    return bs_launch_walk(L, items, n_items, tslots, st);
+}
+
+static const BmGeom &bm_stage_geom(const bxmi_ivl *h, Stage stage)
+{
+    return stage == Stage::OffsetCells ? h->bo_geom : (stage == Stage::Cells ? h->bp_geom : h->bd_geom);
+}
+
+// The large-batch count pass over a batch of n segments (n sealed indexes that qualified for `stage`, with their queries): [order check ->]
+// tile sort (with the batch's parameter block) -> run table -> plan -> search -> un-permute -> totals, all on `st`, six launches
+// for up to 16 segments (five when nobody asks for totals); with the order check in front or more segments the parameter kernel
+// is a launch of its own.  Every decision is bm_plan_pass's (count_plan.hpp); this function reads the feedback words, plans, reserves,
+// keeps the first handle's books and launches.
+// counts[i] may be NULL (total only: nothing is stored per query); totals_dev[i] may be.  The scratch of hs[0] serves the whole batch.
+static int bm_count_segments(bxmi_ivl *const *hs, int n, const int32_t *const *qs, const int32_t *const *qe, const int64_t *nq,
+                             int32_t *const *counts, int64_t *const *totals_dev, hipStream_t st, Stage stage, BmFindCtx *fx = nullptr)
+{
+    if (stage == Stage::None) return fail(BXMI_EINVAL, "bm_count_segments: no search stage");
+    bxmi_ivl *h = hs[0];
+    const bool slices = stage == Stage::Slices, wide = stage == Stage::OffsetCells;
+    BmPlanIn in;
+    in.stage = stage;
+    in.find = fx != nullptr, in.sub = fx && fx->sub, in.direct = fx && fx->direct;
+    in.knobs = bm_plan_knobs();
+    in.seg_bytes = sizeof(BmSeg);
+    in.seg.resize((size_t)n);
+    for (int i = 0; i < n; i++) in.seg[(size_t)i].nq = nq[i], in.seg[(size_t)i].f = slices ? 0 : bm_stage_geom(hs[i], stage).f;
+    const int64_t tile = (int64_t)1 << (bm_plan_variant(in) == 2 ? 15 : 14);  // (the slice geometry depends on it)
+    std::vector<BmSeg> segs((size_t)n);
+    for (int i = 0; i < n; i++) {
+        BmSeg &sg = segs[(size_t)i];
+        BmPlanSegIn &si = in.seg[(size_t)i];
+        sg.g = slices ? sl_geom(hs[i], tile, &si.sl_lds, &si.sl_run) : bm_stage_geom(hs[i], stage);
+        sg.qs = qs[i], sg.qe = qe[i], sg.counts = counts[i];
+        sg.nq = nq[i];
+        sg.dimages = hs[i]->bd_images.as<unsigned char>();
+        sg.pimages = wide ? hs[i]->bo_images.as<unsigned char>() : hs[i]->bp_images.as<unsigned char>();
+        sg.smeta = slices ? hs[i]->sl_meta.as<int4>() : nullptr;
+        sg.ix = index_dev(hs[i]);
+        sg.e_sorted = hs[i]->e_sorted.as<int32_t>();
+        si.f = sg.g.f, si.shift = sg.g.shift, si.stride = sg.g.stride;
+        si.want_counts = counts[i] != nullptr, si.want_total = totals_dev && totals_dev[i];
+        si.bd_blocks = hs[i]->bd_blocks, si.bo_state = hs[i]->bo_state, si.w8_off = hs[i]->w8_off;
+        si.n = hs[i]->n, si.span = (int64_t)hs[i]->cmax - (int64_t)hs[i]->geom.cmin + 1;
+    }
+    // the feedback words as they stand (no memory yet: nothing has been written)
+    const volatile unsigned long long *fb = h->bd_fb_host;
+    in.fb_wide_counts = fb ? fb[0] : 0, in.fb_order = fb ? fb[1] : 0;
+    in.w8_queries = h->w8_queries;
+    in.order_seq = h->order_seq, in.order_seen = h->order_seen, in.unsorted_streak = h->unsorted_streak, in.order_skip = h->order_skip;
+
+    BmPassPlan P = bm_plan_pass(in);
+    if (P.error == BmPlanError::TooManyQueries) return fail(BXMI_EINVAL, "bxmi_ivl_count: more than 2^31 queries in one batch");
+    if (P.error == BmPlanError::TooManySegments) return fail(BXMI_EINVAL, "bxmi_ivl_count_multi: more than 4096 indexes in one batch");
+    if (P.error != BmPlanError::None) return fail(BXMI_ESTATE, "bm_count_segments: the half-bucket order serves find() on one index's slices");
+    if (P.empty) return BXMI_OK;
+    for (int i = 0; i < n; i++) segs[(size_t)i].tile0 = P.seg[(size_t)i].tile0, segs[(size_t)i].ntiles = P.seg[(size_t)i].ntiles, segs[(size_t)i].tile_end = P.seg[(size_t)i].tile_end;
+
+    BXMI_TRY(bm_reserve(h, P.bytes));
+    if (P.fxsub) fx->f = segs[0].g.f, fx->ntiles = segs[0].ntiles;
+    unsigned long long *slots = h->p_slots.as<unsigned long long>();
+    unsigned *order_word = reinterpret_cast<unsigned *>(slots + (size_t)n * PT_SLOTS);  // raised when the starts are NOT sorted (zeroed with the partial totals)
+
+    // the first handle's books: the order of its batches, its 8-bit counts
+    if (P.order_aware || P.w8_asked) BXMI_TRY(ensure_feedback(h, st));
+    BmLaunch L;
+    if (P.order_aware) {
+        h->order_seen = P.order_seen, h->unsorted_streak = P.unsorted_streak, h->order_skip = P.order_skip;
+        if (P.probe_first) {
+            hipLaunchKernelGGL(bm_probe_kernel, dim3(1), dim3(256), 0, st, qs[0], nq[0], order_word);
+            unsigned seen_descent = 0;
+            BXMI_HIP(hipMemcpyAsync(&seen_descent, order_word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+            BXMI_HIP(hipStreamSynchronize(st));
+            if (seen_descent) {
+                h->unsorted_streak = 2, h->order_skip = true;
+                bm_plan_set_order_skip(P, true, in.knobs);
+            }
+        }
+        L.order_seq = ++h->order_seq;
+    }
+    BXMI_TRY(h->bs_plan.reserve(P.bytes.bs_plan));
+    if (P.w8_trip) h->w8_off = true;
+    if (P.w8) h->w8_queries += P.nq_all;
+
+    unsigned long long *tslots = P.any_total ? slots : nullptr;
+    L.owner = h;
+    L.gate = P.order_check ? order_word : nullptr;
+    L.descent = P.probe_rides ? order_word : nullptr;
+    BXMI_TRY(bm_set_params(L, P, segs, totals_dev, slots, st));
+    L.ntp = P.ntp, L.ngroups = P.ngroups, L.tile_log2 = P.tile_log2;
+    L.search_lds = P.search_lds;
+    L.pad = P.pad, L.wide = wide, L.big = P.big, L.w8 = P.w8;
+    L.xcd_next = reinterpret_cast<unsigned *>(slots + (size_t)n * PT_SLOTS + 4);
+    L.n_segs = n;
+    L.g0 = segs[0].g;
+    L.tot = P.tot_walk, L.tot_slots = slots;
+    // one index -- or several on cell images -- whose batch may be sorted by start already: one pass over the queries as they lie then,
+    // and every kernel below stands down
+    if (P.order_check) BXMI_TRY(bm_launch_sorted(L, P, qs, qe, nq, counts, tslots, st));
+    if (P.variant == 2)
+        BXMI_TRY((bm_launch_tiles<1024, 32>(L, st, P.fxsub)));
+    else if (P.variant == 1)
+        BXMI_TRY((bm_launch_tiles<1024, 16>(L, st, P.fxsub)));
     else
         BXMI_TRY((bm_launch_tiles<512, 32>(L, st)));
-    if (tot_walk) {
+    if (P.tot_walk) {
         // the queries behind escape records, answered from the index tile by tile (none in most batches): behind the tile sort, which
         // flags the tiles and whose first workgroup has zeroed the partial totals.  (On a stream of its own between the tile sort
         // and the fold, beside the run table, the plan and the walk: 0.499 against 0.503 ms per pass -- not worth a second stream.)
-        hipLaunchKernelGGL(bm_escape_totals_kernel, dim3((unsigned)ntp), dim3(1024), 0, st, L.segs, L.tile_seg, h->bm_tesc.as<unsigned>(), ntp, tile_log2, slots,
-                           unsorted);
+        hipLaunchKernelGGL(bm_escape_totals_kernel, dim3((unsigned)P.ntp), dim3(1024), 0, st, L.segs, L.tile_seg, h->bm_tesc.as<unsigned>(), P.ntp, P.tile_log2, slots,
+                           L.gate);
         BXMI_LAUNCH_CHECK();
     }
-    if (fxsub) {  // the half-bucket run table, half-major (nobody needs its group counts: the fill has its own plan)
-        hipLaunchKernelGGL(bm_transpose_kernel<FX_NBK>, dim3((unsigned)ngroups, FX_NBK / 64), dim3(256), 0, st, h->fx_tbl2.as<unsigned short>(), L.segs,
-                           L.tile_seg, tile_log2, h->fx_runT2.as<unsigned>(), ntp, (unsigned *)nullptr, unsorted);
+    if (P.fxsub) {  // the half-bucket run table, half-major (nobody needs its group counts: the fill has its own plan)
+        hipLaunchKernelGGL(bm_transpose_kernel<FX_NBK>, dim3((unsigned)P.ngroups, FX_NBK / 64), dim3(256), 0, st, h->fx_tbl2.as<unsigned short>(), L.segs,
+                           L.tile_seg, P.tile_log2, h->fx_runT2.as<unsigned>(), P.ntp, (unsigned *)nullptr, L.gate);
         BXMI_LAUNCH_CHECK();
     }
-    if (dense) {
-        hipLaunchKernelGGL(bd_transpose_kernel, dim3((unsigned)ngroups, BM_NB / 64), dim3(256), 0, st, h->bm_tbl.as<unsigned short>(), L.segs, L.tile_seg,
-                           tile_log2, h->bd_unitT.as<unsigned short>(), ntp, h->sl_unitcnt.as<unsigned>(), unsorted,
-                           pad ? h->bd_tend.as<unsigned>() : (const unsigned *)nullptr);
-        if (n <= BD_PLAN_SEGS)
-            hipLaunchKernelGGL(bd_plan_kernel, dim3(1), dim3(1024), 0, st, h->sl_unitcnt.as<unsigned>(), n, L.segs, chunk, h->bm_items.as<int4>() + 1,
-                               h->bm_items.as<int>(), unsorted);
-        else
-            hipLaunchKernelGGL(bm_plan_kernel<2>, dim3(BM_PLAN_BLOCKS), dim3(BM_PLAN_THREADS), 0, st, h->sl_unitcnt.as<unsigned>(), ngroups, L.segs, L.tile_seg,
-                               chunk, h->bm_items.as<int4>() + 1, h->bm_items.as<int>(), unsorted);
+    if (P.dense) {
+        hipLaunchKernelGGL(bd_transpose_kernel, dim3((unsigned)P.ngroups, BM_NB / 64), dim3(256), 0, st, h->bm_tbl.as<unsigned short>(), L.segs, L.tile_seg,
+                           P.tile_log2, h->bd_unitT.as<unsigned short>(), P.ntp, h->sl_unitcnt.as<unsigned>(), L.gate,
+                           P.pad ? h->bd_tend.as<unsigned>() : (const unsigned *)nullptr);
     } else {
-    hipLaunchKernelGGL(bm_transpose_kernel<BM_NB>, dim3((unsigned)ngroups, BM_NB / 64), dim3(256), 0, st, h->bm_tbl.as<unsigned short>(), L.segs, L.tile_seg,
-                       tile_log2, h->bm_runT.as<unsigned>(), ntp, h->bm_grpcnt.as<unsigned>(), unsorted);
-    hipLaunchKernelGGL(sl_unit_sums_kernel, dim3((unsigned)ngroups), dim3(1024), 0, st, h->bm_grpcnt.as<unsigned>(), L.segs, L.tile_seg,
-                       h->sl_unitcnt.as<unsigned>(), unsorted);
-    if (n <= BD_PLAN_SEGS)  // (the one-workgroup plan: 11 us where bm_plan_kernel<2> takes 37 on configs[4]'s 1526 tiles)
-        hipLaunchKernelGGL(bd_plan_kernel, dim3(1), dim3(1024), 0, st, h->sl_unitcnt.as<unsigned>(), n, L.segs, chunk, h->bm_items.as<int4>() + 1,
-                           h->bm_items.as<int>(), unsorted);
-    else
-        hipLaunchKernelGGL(bm_plan_kernel<2>, dim3(BM_PLAN_BLOCKS), dim3(BM_PLAN_THREADS), 0, st, h->sl_unitcnt.as<unsigned>(), ngroups, L.segs, L.tile_seg,
-                           chunk, h->bm_items.as<int4>() + 1, h->bm_items.as<int>(), unsorted);
+        hipLaunchKernelGGL(bm_transpose_kernel<BM_NB>, dim3((unsigned)P.ngroups, BM_NB / 64), dim3(256), 0, st, h->bm_tbl.as<unsigned short>(), L.segs, L.tile_seg,
+                           P.tile_log2, h->bm_runT.as<unsigned>(), P.ntp, h->bm_grpcnt.as<unsigned>(), L.gate);
+        hipLaunchKernelGGL(sl_unit_sums_kernel, dim3((unsigned)P.ngroups), dim3(1024), 0, st, h->bm_grpcnt.as<unsigned>(), L.segs, L.tile_seg,
+                           h->sl_unitcnt.as<unsigned>(), L.gate);
     }
-    BXMI_LAUNCH_CHECK();
-    const unsigned sgrid = (unsigned)(div_up(max_items, 8) * 8);
-    if (slices_flat)
-        BXMI_TRY(bd_launch_search(L, sgrid, 2, false, st));
+    BXMI_TRY(bm_launch_plan(L, P.chunk, st));
+    unsigned *search_out = fx ? h->sl_cnt.as<unsigned>() : h->bm_recs.as<unsigned>();
+    if (P.slices_flat)
+        BXMI_TRY(bd_launch_search(L, P.sgrid, Stage::Slices, false, st));
     else if (slices) {
-        // long runs (sparse index, big units): the flat walk; else L lanes per run
-        int lanes = g_opt_sl_lanes < 0 ? 0 : (g_opt_sl_lanes ? (int)g_opt_sl_lanes : (sl_run >= 96 ? 0 : (sl_run >= 40 ? 64 : 16)));
-        if (fx && lanes == 0) lanes = 64;  // (the fill half has no flat walk)
-        if (lanes == 0)
-            BXMI_TRY(sl_launch_search_flat(L, sgrid, st));
-        else if (lanes == 64)
-            BXMI_TRY(sl_launch_search<64>(L, sgrid, st, search_out, fxsub ? h->fx_hc.as<unsigned>() : nullptr));
+        if (P.lanes == 0)
+            BXMI_TRY(sl_launch_search_flat(L, P.sgrid, st));
+        else if (P.lanes == 64)
+            BXMI_TRY(sl_launch_search<64>(L, P.sgrid, st, search_out, P.fxsub ? h->fx_hc.as<unsigned>() : nullptr));
         else
-            BXMI_TRY(sl_launch_search<16>(L, sgrid, st, search_out, fxsub ? h->fx_hc.as<unsigned>() : nullptr));
-        if (fx) fx->L = L, fx->sgrid = sgrid, fx->lanes = lanes, fx->variant = variant;
+            BXMI_TRY(sl_launch_search<16>(L, P.sgrid, st, search_out, P.fxsub ? h->fx_hc.as<unsigned>() : nullptr));
+        if (fx) fx->L = L, fx->sgrid = P.sgrid, fx->lanes = P.lanes, fx->variant = P.variant;
     } else
-        BXMI_TRY(bd_launch_search(L, sgrid, cells ? 1 : 0, any_blocks, st));
+        BXMI_TRY(bd_launch_search(L, P.sgrid, stage, P.any_blocks, st));
     unsigned *loff = fx ? h->sl_loff.as<unsigned>() : nullptr;
-    if (tot_walk) {
+    if (P.tot_walk) {
         // (the walk has added every tile's share to the partial totals: nothing to put back into query order)
-    } else if (dense && !fxsub) {
-        if (variant == 2)
+    } else if (P.dense && !P.fxsub) {
+        if (P.variant == 2)
             BXMI_TRY((bd_launch_unpermute<1024, 32>(L, tslots, st)));
         else
             BXMI_TRY((bd_launch_unpermute<1024, 16>(L, tslots, st)));
-    } else if (variant == 2)
-        BXMI_TRY((bm_launch_unpermute<1024, 32>(L, tslots, st, search_out, loff, fxsub ? (fx->direct ? 3 : 2) : 0)));
+    } else if (P.variant == 2)
+        BXMI_TRY((bm_launch_unpermute<1024, 32>(L, tslots, st, search_out, loff, P.fxsub ? (fx->direct ? 3 : 2) : 0)));
     else
-        BXMI_TRY((bm_launch_unpermute<1024, 16>(L, tslots, st, search_out, loff, fxsub ? (fx->direct ? 3 : 2) : 0)));
-    if (any_total) {
+        BXMI_TRY((bm_launch_unpermute<1024, 16>(L, tslots, st, search_out, loff, P.fxsub ? (fx->direct ? 3 : 2) : 0)));
+    if (P.any_total) {
         hipLaunchKernelGGL(bm_fold_totals_kernel, dim3((unsigned)n), dim3(64), 0, st, slots,
-                           reinterpret_cast<unsigned long long *const *>(h->bm_params.as<unsigned char>() + seg_bytes));
+                           reinterpret_cast<unsigned long long *const *>(h->bm_params.as<unsigned char>() + P.seg_bytes));
         BXMI_LAUNCH_CHECK();
     }
     return BXMI_OK;
@@ -1344,7 +1184,7 @@ static int ivl_find_fx(bxmi_ivl *h, const int32_t *qs, const int32_t *qe, int64_
     }
     int32_t *counts = h->q_cnt.as<int32_t>();
     int64_t *no_total = nullptr;
-    BXMI_TRY(bm_count_segments(&h, 1, &qs, &qe, &nq, &counts, &no_total, st, 2, &fx));
+    BXMI_TRY(bm_count_segments(&h, 1, &qs, &qe, &nq, &counts, &no_total, st, Stage::Slices, &fx));
     const int64_t ntp = fx.L.ntp;
     // (only the tiles that hold queries: the un-permute kernel leaves the padding up to the plan group alone)
     hipLaunchKernelGGL(fx_tile_scan_kernel, dim3(1), dim3(1024), 0, st, h->fx_tile_tot.as<unsigned long long>(), fx.ntiles, h->fx_tile_base.as<long long>(),
@@ -1391,12 +1231,10 @@ static int ivl_find_fx(bxmi_ivl *h, const int32_t *qs, const int32_t *qe, int64_
     if (nchunks < 1) nchunks = 1;
     const int64_t tiles_per_chunk = div_up(div_up(fx.ntiles, nchunks), 64) * 64;
     nchunks = div_up(fx.ntiles, tiles_per_chunk);
-    BXMI_TRY(allow_big_lds(fx_fill_kernel, FX_LDS_BYTES));
-    hipLaunchKernelGGL(fx_fill_kernel, dim3((unsigned)device_props().cus), dim3(FX_THREADS), FX_LDS_BYTES, st, fx.L.segs, h->fx_pieces.as<FxPiece>(), npieces,
+    BXMI_TRY(launch_lds(fx_fill_kernel, dim3((unsigned)device_props().cus), dim3(FX_THREADS), FX_LDS_BYTES, st, fx.L.segs, h->fx_pieces.as<FxPiece>(), npieces,
                        (int)nchunks, (int)tiles_per_chunk, h->fx_runT2.as<unsigned>(), ntp, h->bm_recs.as<unsigned>(), h->fx_hc.as<unsigned>(),
                        h->sl_cnt.as<unsigned>(), h->sl_loff.as<unsigned>(), h->fx_tile_base.as<long long>(), h->sl_eid.as<int2>() + SL_WALK,
-                       h->fx_meta2.as<int2>(), fx.direct ? hits : h->sl_hits.as<int32_t>(), fx.L.tile_log2, h->fx_work.as<unsigned>(), h->fx_work.as<int32_t>() + 16);
-    BXMI_LAUNCH_CHECK();
+                       h->fx_meta2.as<int2>(), fx.direct ? hits : h->sl_hits.as<int32_t>(), fx.L.tile_log2, h->fx_work.as<unsigned>(), h->fx_work.as<int32_t>() + 16));
     if (fx.direct) return BXMI_OK;  // (every record's hits went where the CSR offsets say)
     const unsigned cgrid = (unsigned)(div_up(ntp, 8) * 8 * (((int64_t)1 << fx.L.tile_log2) / BM_PART_Q));
     {  // two consecutive queries per lane (one: 0.91 ms on configs[4], two: 0.78, four: 0.85)
@@ -1410,12 +1248,19 @@ static int ivl_find_fx(bxmi_ivl *h, const int32_t *qs, const int32_t *qe, int64_
     return BXMI_OK;
 }
 
-// Which search stage serves a sealed index in the large-batch pass: 0 = neither (older paths), 1 = bucket images,
-// 2 = key slices, 3 = dense unit images (dense indexes try them before the bucket images).  Images cost 0.5 B per coordinate of the span and win on dense indexes; sparse ones (fewer than one
-// target per 64 coordinates) and spans whose bucket image outgrows the LDS take slices.  Prepared on first use.
-static int bm_choose_stage(bxmi_ivl *h, hipStream_t st, int *kind, int64_t nq)
+// Which search stage (count_plan.hpp: Stage) serves a sealed index in the large-batch pass for a batch of nq queries; Stage::None = the
+// older paths (an index with reversed targets or fewer than 4096).  Every stage's images or tables are prepared on first use and the
+// kernel that builds them says whether the index qualifies.  In this order, unless a knob forces or forbids a stage:
+//   offset cells   sparse indexes (a cell of 64..256 coordinates holds about one key), when the batch brings enough queries per unit image;
+//                  ivl.clumped = 1 tries their clumped layout next
+//   key slices     first for indexes with fewer than one target per 64 coordinates, or buckets too wide for dense images (ivl.slice = 1: always first)
+//   bitmap cells   indexes whose hard cells stay below ivl.bm_hard_ppm
+//   offset cells, clumped layout   duplicate-heavy indexes that bitmap cells refused, if a rank table per hard cell fits the LDS
+//   dense images   whatever fits their format
+//   key slices     last, for what is left, where a single bucket's keys fit the LDS.
+static int bm_choose_stage(bxmi_ivl *h, hipStream_t st, Stage *stage, int64_t nq)
 {
-    *kind = 0;
+    *stage = Stage::None;
     if (h->has_reversed || h->n < 4096) return BXMI_OK;
     int64_t span = (int64_t)h->cmax - (int64_t)h->geom.cmin;
     if (span < 0) span = 0;
@@ -1428,7 +1273,7 @@ static int bm_choose_stage(bxmi_ivl *h, hipStream_t st, int *kind, int64_t nq)
         if (h->bo_state == 1) {
             const int64_t units = (span >> (h->bo_geom.shift + h->bo_geom.f)) + 1;
             if (g_opt_sparse > 0 || nq >= units * g_opt_bo_min_per_unit) {
-                *kind = 5;
+                *stage = Stage::OffsetCells;
                 return BXMI_OK;
             }
         }
@@ -1441,40 +1286,40 @@ static int bm_choose_stage(bxmi_ivl *h, hipStream_t st, int *kind, int64_t nq)
             h->bo_tried_clumped = true;
             BXMI_TRY(bo_prepare_index(h, st, true));
         }
-        if (h->bo_state == 2) *kind = 5;
+        if (h->bo_state == 2) *stage = Stage::OffsetCells;
         return BXMI_OK;
     };
     if (g_opt_clumped > 0 && g_opt_dense != 1) {
         BXMI_TRY(try_clumped());
-        if (*kind) return BXMI_OK;
+        if (*stage != Stage::None) return BXMI_OK;
     }
     const bool slices_first = g_opt_dense != 1 && g_opt_flat != 1 && (g_opt_slice == 1 || (g_opt_slice < 0 && (span / h->n >= 64 || h->geom.shift > BD_MAX_SHIFT)));
     if (slices_first) {
         if (h->sl_state == 0) BXMI_TRY(sl_prepare_index(h, st));
         if (h->sl_state == 1) {
-            *kind = 2;
+            *stage = Stage::Slices;
             return BXMI_OK;
         }
     }
     if (g_opt_flat != 0) {
         if (h->bp_state == 0) BXMI_TRY(bp_prepare_index(h, st));
         if (h->bp_state == 1) {
-            *kind = 4;
+            *stage = Stage::Cells;
             return BXMI_OK;
         }
     }
     if (g_opt_clumped < 0 && g_opt_flat != 0 && h->bp_state == -1 && g_opt_dense < 0 && g_opt_sparse != 0 && g_opt_slice < 1) BXMI_TRY(try_clumped());
-    if (*kind) return BXMI_OK;
+    if (*stage != Stage::None) return BXMI_OK;
     if (g_opt_dense != 0) {
         if (h->bd_state == 0) BXMI_TRY(bd_prepare_index(h, st));
         if (h->bd_state == 1) {
-            *kind = 3;
+            *stage = Stage::Dense;
             return BXMI_OK;
         }
     }
     if (!slices_first && g_opt_slice != 0) {
         if (h->sl_state == 0) BXMI_TRY(sl_prepare_index(h, st));
-        if (h->sl_state == 1) *kind = 2;
+        if (h->sl_state == 1) *stage = Stage::Slices;
     }
     return BXMI_OK;
 }
@@ -1484,6 +1329,18 @@ static int ivl_stream(bxmi_ivl *h)
     if (!h->stream) BXMI_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     return BXMI_OK;
 }
+
+namespace bxmi {
+
+// the same stream for liftover.hip, whose host-pointer form runs on its index's stream and knows the handle no further
+int ivl_host_stream(bxmi_ivl_t *h, hipStream_t *out)
+{
+    BXMI_TRY(ivl_stream(h));
+    *out = h->stream;
+    return BXMI_OK;
+}
+
+}  // namespace bxmi
 
 extern "C" int bxmi_ivl_create(bxmi_ivl_t **out)
 {
@@ -1753,13 +1610,6 @@ static IndexDev index_dev(const bxmi_ivl *h)
     return ix;
 }
 
-template <typename Kern>
-static int allow_big_lds(Kern k, size_t bytes)
-{
-    BXMI_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return BXMI_OK;
-}
-
 extern "C" int bxmi_ivl_count_dev(bxmi_ivl_t *h, const int32_t *qs, const int32_t *qe, int64_t nq, int32_t *counts,
                                   int64_t *total_dev, void *stream)
 {
@@ -1778,11 +1628,11 @@ extern "C" int bxmi_ivl_count_dev(bxmi_ivl_t *h, const int32_t *qs, const int32_
     const bool bitmap = (counts || total_dev) && g_opt_bitmap != 0 && !h->has_reversed && h->n >= 4096 &&
                         (g_opt_partition == 1 || (g_opt_partition < 0 && nq >= g_opt_bitmap_min));
     if (bitmap) {
-        int kind = 0;
-        BXMI_TRY(bm_choose_stage(h, st, &kind, nq));
-        if (kind) {
+        Stage stage = Stage::None;
+        BXMI_TRY(bm_choose_stage(h, st, &stage, nq));
+        if (stage != Stage::None) {
             // (counts == NULL: the same pass, its un-permute kernel sums without storing -- no scratch array of counts)
-            return bm_count_segments(&h, 1, &qs, &qe, &nq, &counts, &total_dev, st, kind);
+            return bm_count_segments(&h, 1, &qs, &qe, &nq, &counts, &total_dev, st, stage);
         }
     }
     if (partition) return ivl_count_partitioned(h, qs, qe, nq, counts, total_dev, st);
@@ -1792,9 +1642,7 @@ extern "C" int bxmi_ivl_count_dev(bxmi_ivl_t *h, const int32_t *qs, const int32_
     int64_t need = div_up(nq, (int64_t)(CNT_THREADS / 8) * CNT_Q);
     if (need < grid) grid = (int)need;
     unsigned long long *tot = reinterpret_cast<unsigned long long *>(total_dev);
-    BXMI_TRY(allow_big_lds(ivl_count_kernel<true>, lds_bytes));
-    hipLaunchKernelGGL(ivl_count_kernel<true>, dim3(grid), dim3(CNT_THREADS), lds_bytes, st, S, E, index_dev(h), qs, qe, nq, counts, tot);
-    BXMI_LAUNCH_CHECK();
+    BXMI_TRY(launch_lds(ivl_count_kernel<true>, dim3(grid), dim3(CNT_THREADS), lds_bytes, st, S, E, index_dev(h), qs, qe, nq, counts, tot));
     return BXMI_OK;
 }
 
@@ -1804,11 +1652,13 @@ extern "C" int bxmi_ivl_count_multi_dev(bxmi_ivl_t *const *hs, int n, const int3
     if (n < 0 || (n > 0 && (!hs || !qs || !qe || !nq))) return fail(BXMI_EINVAL, "bxmi_ivl_count_multi_dev: bad arguments");
     hipStream_t st = as_stream(stream);
     // indexes whose batch can ride the bitmap-cell pass are answered together (one pass, six launches); the others one by one
-    std::vector<bxmi_ivl *> fh[5];  // by search stage (kind - 1): [1] slices, [2] dense unit images, [3] cell images of units, [4] offset cells
-    std::vector<const int32_t *> fqs[5], fqe[5];
-    std::vector<int64_t> fnq[5];
-    std::vector<int32_t *> fc[5];
-    std::vector<int64_t *> ft[5];
+    struct Group {  // the segments of one search stage
+        std::vector<bxmi_ivl *> h;
+        std::vector<const int32_t *> qs, qe;
+        std::vector<int64_t> nq;
+        std::vector<int32_t *> counts;
+        std::vector<int64_t *> totals;
+    } groups[N_STAGES];  // by Stage (Stage::None stays empty)
     std::vector<int> rest;
     int64_t nq_all = 0;
     for (int i = 0; i < n; i++) {
@@ -1822,25 +1672,25 @@ extern "C" int bxmi_ivl_count_multi_dev(bxmi_ivl_t *const *hs, int n, const int3
     for (int i = 0; i < n; i++) {
         bxmi_ivl *h = hs[i];
         if (nq[i] == 0) continue;
-        int kind = 0;
+        Stage stage = Stage::None;
         // a segment occupies whole groups of 64 tiles of scratch whatever its size: in a batch over hundreds of indexes
         // (a scaffold-level assembly) the ones with a handful of queries are answered one by one instead
         const bool tiny = n > 256 && nq[i] < 65536;
         // (an index whose caller wants neither counts nor a total has nothing to compute; total-only segments ride the same pass)
         const bool wanted = (counts && counts[i]) || (totals_dev && totals_dev[i]);
-        if (fused && wanted && !tiny) BXMI_TRY(bm_choose_stage(h, st, &kind, nq[i]));
-        if (kind) {
-            const int k = kind - 1;
-            fh[k].push_back(h), fqs[k].push_back(qs[i]), fqe[k].push_back(qe[i]), fnq[k].push_back(nq[i]), fc[k].push_back(counts ? counts[i] : nullptr);
-            ft[k].push_back(totals_dev ? totals_dev[i] : nullptr);
+        if (fused && wanted && !tiny) BXMI_TRY(bm_choose_stage(h, st, &stage, nq[i]));
+        if (stage != Stage::None) {
+            Group &g = groups[(int)stage];
+            g.h.push_back(h), g.qs.push_back(qs[i]), g.qe.push_back(qe[i]), g.nq.push_back(nq[i]), g.counts.push_back(counts ? counts[i] : nullptr);
+            g.totals.push_back(totals_dev ? totals_dev[i] : nullptr);
         } else {
             rest.push_back(i);
         }
     }
-    for (int k = 0; k < 5; k++)
-        if (!fh[k].empty())
-            BXMI_TRY(bm_count_segments(fh[k].data(), (int)fh[k].size(), fqs[k].data(), fqe[k].data(), fnq[k].data(), fc[k].data(), ft[k].data(), st,
-                                       k + 1));
+    for (const Stage stage : {Stage::Slices, Stage::Dense, Stage::Cells, Stage::OffsetCells}) {
+        Group &g = groups[(int)stage];
+        if (!g.h.empty()) BXMI_TRY(bm_count_segments(g.h.data(), (int)g.h.size(), g.qs.data(), g.qe.data(), g.nq.data(), g.counts.data(), g.totals.data(), st, stage));
+    }
     for (int i : rest)
         BXMI_TRY(bxmi_ivl_count_dev(hs[i], qs[i], qe[i], nq[i], counts ? counts[i] : nullptr, totals_dev ? totals_dev[i] : nullptr, stream));
     return BXMI_OK;
@@ -1947,10 +1797,8 @@ extern "C" int bxmi_ivl_find_dev(bxmi_ivl_t *h, const int32_t *qs, const int32_t
     int grid = device_props().cus * 2;
     int64_t need = div_up(nq, (int64_t)(FIND_THREADS / 8) * FIND_Q);
     if (need < grid) grid = (int)need;
-    BXMI_TRY(allow_big_lds(ivl_find_count_kernel<true>, lds_bytes));
-    hipLaunchKernelGGL(ivl_find_count_kernel<true>, dim3(grid), dim3(FIND_THREADS), lds_bytes, st, S, P, ix, qs, qe, nq,
-                       h->q_lo.as<int32_t>(), h->q_hi.as<int32_t>(), h->q_cnt.as<int32_t>());
-    BXMI_LAUNCH_CHECK();
+    BXMI_TRY(launch_lds(ivl_find_count_kernel<true>, dim3(grid), dim3(FIND_THREADS), lds_bytes, st, S, P, ix, qs, qe, nq,
+                       h->q_lo.as<int32_t>(), h->q_hi.as<int32_t>(), h->q_cnt.as<int32_t>()));
     // offsets[0..nq) = exclusive sum of counts, offsets[nq] = total
     BXMI_TRY((device_scan<int32_t, long long, OpSum, false>(h->q_cnt.as<int32_t>(), reinterpret_cast<long long *>(offsets), nq, 0ll,
                                                            reinterpret_cast<long long *>(offsets) + nq, h->scan_scratch, st)));
@@ -2239,10 +2087,8 @@ extern "C" int bxmi_ivl_neighbors_batch_dev(bxmi_ivl_t *h, const int32_t *pos, i
     if (need < grid) grid = (int)need;
     if (dir > 0) {
         size_t lds_bytes = (size_t)S.lds_ints * 4;
-        BXMI_TRY(allow_big_lds(nb_after_kernel<true>, lds_bytes));
-        hipLaunchKernelGGL(nb_after_kernel<true>, dim3(grid), dim3(FIND_THREADS), lds_bytes, st, S, ix, pos, nq, (int)k, (int)max_dist, out,
-                           n_out, n_cand);
-        BXMI_LAUNCH_CHECK();
+        BXMI_TRY(launch_lds(nb_after_kernel<true>, dim3(grid), dim3(FIND_THREADS), lds_bytes, st, S, ix, pos, nq, (int)k, (int)max_dist, out,
+                           n_out, n_cand));
         return BXMI_OK;
     }
     TreeDev P = h->treeP.dev;
@@ -2252,10 +2098,8 @@ extern "C" int bxmi_ivl_neighbors_batch_dev(bxmi_ivl_t *h, const int32_t *pos, i
     int32_t *big = h->q_hi.as<int32_t>();
     BXMI_HIP(hipMemsetAsync(big, 0, 4, st));
     size_t lds_bytes = (size_t)(S.lds_ints + P.lds_ints) * 4;
-    BXMI_TRY(allow_big_lds(nb_before_window_kernel<true>, lds_bytes));
-    hipLaunchKernelGGL(nb_before_window_kernel<true>, dim3(grid), dim3(FIND_THREADS), lds_bytes, st, S, P, ix, pos, nq, (int)max_dist, win,
-                       big);
-    BXMI_LAUNCH_CHECK();
+    BXMI_TRY(launch_lds(nb_before_window_kernel<true>, dim3(grid), dim3(FIND_THREADS), lds_bytes, st, S, P, ix, pos, nq, (int)max_dist, win,
+                       big));
     int wgrid = device_props().cus * 8;
     int64_t wneed = div_up(nq, (int64_t)(NB_WAVE_THREADS / 64));
     if (wneed < wgrid) wgrid = (int)wneed;
@@ -2293,258 +2137,4 @@ extern "C" int bxmi_ivl_neighbors_batch(bxmi_ivl_t *h, const int32_t *pos, int64
     if (n_cand) BXMI_HIP(hipMemcpyAsync(n_cand, d_cand, (size_t)nq * 8, hipMemcpyDeviceToHost, st));
     BXMI_HIP(hipStreamSynchronize(st));
     return BXMI_OK;
-}
-
-// ---- liftover through chain alignments (liftover.hpp) ----
-struct bxmi_chainmap {
-    bxmi_ivl *ivl = nullptr;  // the chain spans, in the order given
-    int64_t n_chains = 0, n_blocks = 0, max_chain_blocks = 0;
-    DevBuf t_start, t_end, q_start, cum, run_of, run_first, rne, blk_chain, c_meta, c_off, c_minus;
-    DevBuf gapc;              // the gap rule's prefix counts for gap_for
-    int64_t gap_for = -1;     // the max_gap gapc was made for (-1 = none yet)
-    // scratch of one batch
-    DevBuf hoff, hits, sel, rows, big, scan_scratch;
-    unsigned *bad_host = nullptr;  // host-visible word lo_check_kernel writes
-    // device staging of the host-pointer entry point
-    DevBuf d_fs, d_fe, d_chain, d_status, d_off, d_os, d_oe;
-};
-
-static LoDev lo_dev(const bxmi_chainmap *m)
-{
-    LoDev L;
-    L.t_start = m->t_start.as<int32_t>(), L.t_end = m->t_end.as<int32_t>(), L.q_start = m->q_start.as<int32_t>();
-    L.cum = m->cum.as<int32_t>(), L.gapc = m->gapc.as<int32_t>();
-    L.run_of = m->run_of.as<int32_t>(), L.run_first = m->run_first.as<int32_t>(), L.rne = m->rne.as<int32_t>();
-    L.c_meta = m->c_meta.as<int4>(), L.c_off = m->c_off.as<int32_t>(), L.c_minus = m->c_minus.as<int32_t>();
-    L.n_chains = (int32_t)m->n_chains;
-    return L;
-}
-
-template <typename T>
-static int lo_upload(DevBuf &b, const std::vector<T> &v)
-{
-    BXMI_TRY(b.reserve(v.size() * sizeof(T) + 16));
-    if (!v.empty()) BXMI_HIP(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return BXMI_OK;
-}
-
-extern "C" int bxmi_chainmap_destroy(bxmi_chainmap_t *m)
-{
-    if (!m) return BXMI_OK;
-    if (m->ivl) (void)bxmi_ivl_destroy(m->ivl);
-    if (m->bad_host) (void)hipHostFree(m->bad_host);
-    delete m;
-    return BXMI_OK;
-}
-
-extern "C" int bxmi_chainmap_create(bxmi_chainmap_t **out, int64_t n_chains, const int32_t *t_start, const int32_t *t_end,
-                                    const int32_t *q_start, const int32_t *q_span, const uint8_t *q_minus, const int64_t *block_off,
-                                    const int32_t *blk_t_start, const int32_t *blk_t_end, const int32_t *blk_q_start)
-{
-    if (!out || n_chains < 0 || n_chains > INT_MAX ||
-        (n_chains > 0 && (!t_start || !t_end || !q_start || !q_span || !q_minus || !block_off || !blk_t_start || !blk_t_end || !blk_q_start)))
-        return fail(BXMI_EINVAL, "bxmi_chainmap_create: bad arguments");
-    *out = nullptr;
-    const int64_t nb = n_chains > 0 ? block_off[n_chains] : 0;
-    if (n_chains > 0 && (block_off[0] != 0 || nb > INT_MAX)) return fail(BXMI_EINVAL, "bxmi_chainmap_create: block_off must run from 0 to at most 2^31-1");
-    // the tables as the kernels read them, validated on the way (see the head of liftover.hpp for what rests on this)
-    std::vector<int32_t> cum((size_t)nb), run_of((size_t)nb), run_first, rne, blk_chain((size_t)nb), c_off((size_t)n_chains + 1, 0), c_minus((size_t)n_chains);
-    std::vector<int4> c_meta((size_t)n_chains);
-    int64_t longest = 0;
-    int32_t run_nonempty = 0;  // the run being walked holds a non-empty block
-    for (int64_t c = 0; c < n_chains; c++) {
-        const int64_t b0 = block_off[c], b1 = block_off[c + 1];
-        if (b1 <= b0 || b1 > nb) return fail(BXMI_EINVAL, "bxmi_chainmap_create: chain %lld has no blocks", (long long)c);
-        const long long t_span = (long long)t_end[c] - t_start[c];
-        if (t_span < 0 || t_span > INT_MAX || q_span[c] < 0 || q_start[c] < 0 || (long long)q_start[c] + q_span[c] > INT_MAX)
-            return fail(BXMI_EINVAL, "bxmi_chainmap_create: chain %lld: a span is negative or reaches beyond 2^31-1", (long long)c);
-        long long sum = 0;
-        for (int64_t j = b0; j < b1; j++) {
-            const long long len = (long long)blk_t_end[j] - blk_t_start[j], qe = (long long)blk_q_start[j] + len;
-            bool ok = len >= 0 && blk_t_start[j] >= 0 && blk_q_start[j] >= 0 && blk_t_end[j] <= t_span && qe <= q_span[c];
-            if (ok && j > b0)
-                ok = blk_t_start[j] >= blk_t_end[j - 1] && (long long)blk_q_start[j] >= (long long)blk_q_start[j - 1] + (blk_t_end[j - 1] - blk_t_start[j - 1]);
-            if (!ok)
-                return fail(BXMI_EINVAL, "bxmi_chainmap_create: chain %lld, block %lld: negative length, outside its chain's span, or before the end of the block before it",
-                            (long long)c, (long long)(j - b0));
-            cum[(size_t)j] = (int32_t)sum;
-            sum += len;
-            // a run begins with its chain and after every junction with a gap on the query side
-            if (j == b0 || (long long)blk_q_start[j] > (long long)blk_q_start[j - 1] + (blk_t_end[j - 1] - blk_t_start[j - 1])) {
-                run_first.push_back((int32_t)j);
-                rne.push_back(rne.empty() ? 0 : rne.back() + run_nonempty);
-                run_nonempty = 0;
-            }
-            if (len > 0) run_nonempty = 1;
-            run_of[(size_t)j] = (int32_t)run_first.size() - 1;
-            blk_chain[(size_t)j] = (int32_t)c;
-        }
-        c_off[(size_t)c] = (int32_t)b0;
-        c_minus[(size_t)c] = q_minus[c] ? 1 : 0;
-        c_meta[(size_t)c] = make_int4(t_start[c], t_end[c], q_start[c], q_span[c]);
-        if (b1 - b0 > longest) longest = b1 - b0;
-    }
-    c_off[(size_t)n_chains] = (int32_t)nb;
-    run_first.push_back((int32_t)nb);  // [n_runs]: what ends the last run
-    rne.push_back(rne.empty() ? 0 : rne.back() + run_nonempty);
-    bxmi_chainmap *m = new (std::nothrow) bxmi_chainmap();
-    if (!m) return fail(BXMI_ENOMEM, "bxmi_chainmap_create: out of host memory");
-    m->n_chains = n_chains, m->n_blocks = nb, m->max_chain_blocks = longest;
-    auto build = [&]() -> int {
-        BXMI_TRY(bxmi_ivl_create(&m->ivl));
-        if (n_chains > 0) BXMI_TRY(bxmi_ivl_append(m->ivl, t_start, t_end, n_chains));
-        BXMI_TRY(bxmi_ivl_seal(m->ivl, nullptr));
-        BXMI_TRY(lo_upload(m->cum, cum));
-        BXMI_TRY(lo_upload(m->run_of, run_of));
-        BXMI_TRY(lo_upload(m->run_first, run_first));
-        BXMI_TRY(lo_upload(m->rne, rne));
-        BXMI_TRY(lo_upload(m->blk_chain, blk_chain));
-        BXMI_TRY(lo_upload(m->c_meta, c_meta));
-        BXMI_TRY(lo_upload(m->c_off, c_off));
-        BXMI_TRY(lo_upload(m->c_minus, c_minus));
-        DevBuf *dst[3] = {&m->t_start, &m->t_end, &m->q_start};
-        const int32_t *src[3] = {blk_t_start, blk_t_end, blk_q_start};
-        for (int i = 0; i < 3; i++) {
-            BXMI_TRY(dst[i]->reserve((size_t)nb * 4 + 16));
-            if (nb > 0) BXMI_HIP(hipMemcpy(dst[i]->p, src[i], (size_t)nb * 4, hipMemcpyHostToDevice));
-        }
-        BXMI_HIP(hipHostMalloc(reinterpret_cast<void **>(&m->bad_host), 64, hipHostMallocDefault));
-        *m->bad_host = 0;
-        return BXMI_OK;
-    };
-    const int rc = build();
-    if (rc != BXMI_OK) {
-        (void)bxmi_chainmap_destroy(m);
-        return rc;
-    }
-    *out = m;
-    return BXMI_OK;
-}
-
-extern "C" int bxmi_chainmap_info(const bxmi_chainmap_t *m, int64_t *n_chains, int64_t *n_blocks, int64_t *max_chain_blocks)
-{
-    if (!m) return fail(BXMI_EINVAL, "bxmi_chainmap_info: NULL handle");
-    if (n_chains) *n_chains = m->n_chains;
-    if (n_blocks) *n_blocks = m->n_blocks;
-    if (max_chain_blocks) *max_chain_blocks = m->max_chain_blocks;
-    return BXMI_OK;
-}
-
-// gapc for this max_gap: one pass over the blocks and a scan, kept until another value is asked for
-static int lo_ensure_gapc(bxmi_chainmap *m, int max_gap, hipStream_t st)
-{
-    if (max_gap < 0 || m->gap_for == (int64_t)max_gap || m->n_blocks == 0) return BXMI_OK;
-    BXMI_TRY(m->gapc.reserve((size_t)m->n_blocks * 4 + 16));
-    m->gap_for = -1;
-    int32_t *g = m->gapc.as<int32_t>();
-    hipLaunchKernelGGL(lo_gap_flag_kernel, dim3(stream_grid(m->n_blocks, LO_THREADS)), dim3(LO_THREADS), 0, st, lo_dev(m),
-                       m->blk_chain.as<int32_t>(), m->n_blocks, max_gap, g);
-    BXMI_LAUNCH_CHECK();
-    BXMI_TRY((device_scan<int32_t, int32_t, OpSum, false>(g, g, m->n_blocks, 0, nullptr, m->scan_scratch, st)));
-    m->gap_for = max_gap;
-    return BXMI_OK;
-}
-
-extern "C" int bxmi_chainmap_map_dev(bxmi_chainmap_t *m, const int32_t *fs, const int32_t *fe, int64_t nf, int32_t max_gap, int select,
-                                     double threshold, int32_t *chain, int32_t *status, int64_t *offsets, int32_t *out_start,
-                                     int32_t *out_end, int64_t cap, int64_t *total_host, void *stream)
-{
-    if (!m) return fail(BXMI_EINVAL, "bxmi_chainmap_map_dev: NULL handle");
-    if (nf < 0 || nf > INT_MAX || !offsets || (nf > 0 && (!fs || !fe || !chain || !status)) || cap < 0 || (cap > 0 && (!out_start || !out_end)) ||
-        select < 0 || select > 2 || threshold != threshold)
-        return fail(BXMI_EINVAL, "bxmi_chainmap_map_dev: bad arguments");
-    hipStream_t st = as_stream(stream);
-    if (total_host) *total_host = 0;
-    if (nf == 0) {
-        BXMI_HIP(hipMemsetAsync(offsets, 0, 8, st));
-        return BXMI_OK;
-    }
-    // fs <= fe everywhere?  The answer lies in host memory by the time the find below has waited for the stream.
-    *m->bad_host = 0;
-    hipLaunchKernelGGL(lo_check_kernel, dim3(stream_grid(nf, LO_THREADS)), dim3(LO_THREADS), 0, st, fs, fe, nf, m->bad_host);
-    BXMI_LAUNCH_CHECK();
-    // pass 1: the chains every feature meets, in find order
-    BXMI_TRY(m->hoff.reserve((size_t)(nf + 2) * 8));
-    int64_t pairs = 0;
-    if (m->n_chains == 0) {
-        BXMI_HIP(hipMemsetAsync(m->hoff.p, 0, (size_t)(nf + 1) * 8, st));
-        BXMI_HIP(hipStreamSynchronize(st));
-    } else {
-        BXMI_TRY(m->hits.reserve((size_t)(2 * nf + 1024) * 4));  // (overlapping chains: room for two per feature before the find has to run twice)
-        for (int attempt = 0;; attempt++) {
-            const int64_t hcap = (int64_t)(m->hits.cap / 4) - 4;
-            const int rc = bxmi_ivl_find_dev(m->ivl, fs, fe, nf, m->hoff.as<int64_t>(), m->hits.as<int32_t>(), hcap, &pairs, st);
-            if (rc == BXMI_OK) break;
-            if (rc != BXMI_ERANGE || attempt > 0) return rc;
-            BXMI_TRY(m->hits.reserve((size_t)(pairs + 4) * 4));  // (the list did not fit the scratch: once more with room for it)
-        }
-    }
-    if (*m->bad_host) return fail(BXMI_EINVAL, "bxmi_chainmap_map_dev: a feature has start > end");
-    BXMI_TRY(lo_ensure_gapc(m, max_gap, st));
-    BXMI_TRY(m->sel.reserve((size_t)nf * 16));
-    BXMI_TRY(m->rows.reserve((size_t)(nf + 4) * 4));
-    BXMI_TRY(m->big.reserve((size_t)(nf + 1) * 4));
-    const LoDev L = lo_dev(m);
-    int4 *sel = m->sel.as<int4>();
-    int32_t *rows = m->rows.as<int32_t>(), *big = m->big.as<int32_t>();
-    BXMI_HIP(hipMemsetAsync(big, 0, 4, st));
-    const int grid = stream_grid(nf, LO_THREADS);
-    // passes 2 and 3
-    hipLaunchKernelGGL(lo_select_kernel, dim3(grid), dim3(LO_THREADS), 0, st, L, fs, fe, nf, m->hoff.as<int64_t>(), m->hits.as<int32_t>(),
-                       (int)max_gap, select, threshold, sel, chain, status, rows, big);
-    BXMI_LAUNCH_CHECK();
-    BXMI_TRY((device_scan<int32_t, long long, OpSum, false>(rows, reinterpret_cast<long long *>(offsets), nf, 0ll,
-                                                           reinterpret_cast<long long *>(offsets) + nf, m->scan_scratch, st)));
-    // pass 4: both kernels stand down on the device when the rows do not fit cap
-    hipLaunchKernelGGL(lo_emit_kernel, dim3(grid), dim3(LO_THREADS), 0, st, L, nf, sel, chain, offsets, cap, out_start, out_end);
-    BXMI_LAUNCH_CHECK();
-    hipLaunchKernelGGL(lo_emit_wave_kernel, dim3(device_props().cus * 4), dim3(LO_THREADS), 0, st, L, nf, sel, chain, big, offsets, cap,
-                       out_start, out_end);
-    BXMI_LAUNCH_CHECK();
-    int64_t total = 0;  // (copied behind the launches: nothing returns between this copy and the wait for it)
-    BXMI_HIP(hipMemcpyAsync(&total, offsets + nf, 8, hipMemcpyDeviceToHost, st));
-    BXMI_HIP(hipStreamSynchronize(st));
-    if (total_host) *total_host = total;
-    if (total > cap) return fail(BXMI_ERANGE, "bxmi_chainmap_map: %lld rows need larger buffers than cap=%lld", (long long)total, (long long)cap);
-    return BXMI_OK;
-}
-
-extern "C" int bxmi_chainmap_map(bxmi_chainmap_t *m, const int32_t *fs, const int32_t *fe, int64_t nf, int32_t max_gap, int select,
-                                 double threshold, int32_t *chain, int32_t *status, int64_t *offsets, int32_t *out_start, int32_t *out_end,
-                                 int64_t cap, int64_t *total)
-{
-    if (!m) return fail(BXMI_EINVAL, "bxmi_chainmap_map: NULL handle");
-    if (nf < 0 || nf > INT_MAX || !offsets || (nf > 0 && (!fs || !fe || !chain || !status)) || cap < 0 || (cap > 0 && (!out_start || !out_end)))
-        return fail(BXMI_EINVAL, "bxmi_chainmap_map: bad arguments");
-    if (total) *total = 0;
-    if (nf == 0) {
-        offsets[0] = 0;
-        return BXMI_OK;
-    }
-    BXMI_TRY(ivl_stream(m->ivl));
-    hipStream_t st = m->ivl->stream;
-    BXMI_TRY(m->d_fs.reserve((size_t)(nf + 4) * 4));
-    BXMI_TRY(m->d_fe.reserve((size_t)(nf + 4) * 4));
-    BXMI_TRY(m->d_chain.reserve((size_t)(nf + 4) * 4));
-    BXMI_TRY(m->d_status.reserve((size_t)(nf + 4) * 4));
-    BXMI_TRY(m->d_off.reserve((size_t)(nf + 2) * 8));
-    BXMI_TRY(m->d_os.reserve((size_t)(cap + 4) * 4));
-    BXMI_TRY(m->d_oe.reserve((size_t)(cap + 4) * 4));
-    BXMI_HIP(hipMemcpyAsync(m->d_fs.p, fs, (size_t)nf * 4, hipMemcpyHostToDevice, st));
-    BXMI_HIP(hipMemcpyAsync(m->d_fe.p, fe, (size_t)nf * 4, hipMemcpyHostToDevice, st));
-    int64_t tot = 0;
-    const int rc = bxmi_chainmap_map_dev(m, m->d_fs.as<int32_t>(), m->d_fe.as<int32_t>(), nf, max_gap, select, threshold, m->d_chain.as<int32_t>(),
-                                         m->d_status.as<int32_t>(), m->d_off.as<int64_t>(), m->d_os.as<int32_t>(), m->d_oe.as<int32_t>(), cap,
-                                         &tot, st);
-    if (total) *total = tot;
-    if (rc != BXMI_OK && rc != BXMI_ERANGE) return rc;
-    BXMI_HIP(hipMemcpyAsync(chain, m->d_chain.p, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
-    BXMI_HIP(hipMemcpyAsync(status, m->d_status.p, (size_t)nf * 4, hipMemcpyDeviceToHost, st));
-    BXMI_HIP(hipMemcpyAsync(offsets, m->d_off.p, (size_t)(nf + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (rc == BXMI_OK && tot > 0) {
-        BXMI_HIP(hipMemcpyAsync(out_start, m->d_os.p, (size_t)tot * 4, hipMemcpyDeviceToHost, st));
-        BXMI_HIP(hipMemcpyAsync(out_end, m->d_oe.p, (size_t)tot * 4, hipMemcpyDeviceToHost, st));
-    }
-    BXMI_HIP(hipStreamSynchronize(st));
-    return rc;
 }

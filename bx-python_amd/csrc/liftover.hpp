@@ -1,5 +1,5 @@
 // liftover.hpp -- mapping features through chain alignments (the reference's scripts/bnMapper.py) for a whole array of
-// features in one device pass.  Included by intervals.hip (one translation unit; the entry points bxmi_chainmap_* are there).
+// features in one device pass.  Included by liftover.hip (the entry points bxmi_chainmap_*).
 //
 // Resident per source chromosome (bxmi_chainmap): a sealed interval index over the chain spans [tStart, tEnd) in file order,
 // the block tables of all chains concatenated (coordinates relative to their chain's start, bnMapper.py:293-308,

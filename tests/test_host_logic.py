@@ -519,6 +519,18 @@ def test_offset_cells_encoding_and_unit_model(tmp_path):
     assert out.strip().endswith("offset cells ok"), out
 
 
+def test_count_plan_decisions(tmp_path):
+    """bx-python_amd/csrc/count_plan.hpp holds every decision of the large-batch count pass that needs no device (tile shape,
+    padding, item size, total-only walk, 8-bit counts, folded parameter block, order check or probe, sorted paths, slice lanes,
+    tile numbering, scratch sizes) as one pure function of plain values: tests/cpp/count_plan_test.cpp checks the rules its
+    comments and DESIGN.md 3.1 state, the forced knobs included."""
+    exe = str(tmp_path / "count_plan_test")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "bx-python_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "count_plan_test.cpp"), "-o", exe])
+    out = subprocess.check_output([exe], text=True, timeout=60)
+    assert out.strip().endswith("count plan ok"), out
+
+
 def test_bench_refuses_more_ranks_than_devices():
     """`python bench.py --gpus N` launches its own N ranks (the driver's command shape carries no launcher); with fewer than N
     devices visible it must exit non-zero with a message, never run one rank and print n_gpus 1."""
