@@ -1,0 +1,159 @@
+"""
+bigWig -> per-chromosome span arrays on the host, in plain Python (``struct`` + ``zlib``): what ``BigWigFile.get_as_array``
+(lib/bx/bbi/bigwig_file.pyx:46-88, 122-137, 200-211) would assign position by position, collected for ``ScoreTrack.set_spans``
+in the shape ``bxmi.wiggle.read_spans_file`` returns: {chrom: (starts, ends, values)}, int32 / int32 / float32, in file order
+(a later span overwrites an earlier one, as the reference's assignment does).
+
+Read: the header in either byte order (fields in the order of lib/bx/bbi/bbi_file.pyx:138-152), the chromosome B+ tree (names,
+ids, sizes; bpt_file.pyx), the R-tree over the full-resolution data (cirtree_file.pyx) leaf by leaf, left to right, and the
+three kinds of data block: bedGraph (1), variableStep (2), fixedStep (3), inflated when ``uncompress_buf_size > 0``.  As in the
+reference, item i of a fixedStep block starts at ``block start + i * span`` (its ``step`` field is read and not used), and a
+block of another kind contributes nothing.  Zoom levels and summaries are not read.
+"""
+import struct
+import zlib
+
+import numpy as np
+
+BIGWIG_MAGIC = 0x888FFC26
+BIGBED_MAGIC = 0x8789F2EB
+BPT_MAGIC = 0x78CA8C91
+CIRTREE_MAGIC = 0x2468ACE0
+BEDGRAPH, VARIABLE_STEP, FIXED_STEP = 1, 2, 3
+
+
+def byte_order(head):
+    """'<' or '>' when the first four bytes are the bigWig magic number in that order, else None."""
+    if len(head) >= 4:
+        for order in (">", "<"):
+            if struct.unpack(order + "I", head[:4])[0] == BIGWIG_MAGIC:
+                return order
+    return None
+
+
+def is_bigwig(path):
+    with open(path, "rb") as f:
+        return byte_order(f.read(4)) is not None
+
+
+class _Header:
+    def __init__(self, data):
+        order = byte_order(data)
+        if order is None:
+            magic = data[:4]
+            if len(magic) == 4 and BIGBED_MAGIC in (struct.unpack(">I", magic)[0], struct.unpack("<I", magic)[0]):
+                raise ValueError("a bigBed file, not a bigWig file")
+            raise ValueError("not a bigWig file: bad magic number %r" % magic.hex())
+        if len(data) < 64:
+            raise ValueError("not a bigWig file: the header is cut short")
+        self.order = order
+        (self.version, self.zoom_levels, self.chrom_tree_offset, self.unzoomed_data_offset, self.unzoomed_index_offset, self.field_count,
+         self.defined_field_count, self.as_offset, self.total_summary_offset, self.uncompress_buf_size) = struct.unpack_from(order + "HHQQQHHQQI", data, 4)
+
+
+def _sub_order(data, at, magic, what):
+    for order in (">", "<"):
+        if struct.unpack_from(order + "I", data, at)[0] == magic:
+            return order
+    raise ValueError("bigWig file: bad magic number of the %s at offset %d" % (what, at))
+
+
+def _chrom_tree(data, at):
+    """[(name, id, size)] of the B+ tree at `at`, leaves left to right."""
+    order = _sub_order(data, at, BPT_MAGIC, "chromosome tree")
+    block_size, key_size, value_size, item_count = struct.unpack_from(order + "IIIQ", data, at + 4)
+    if value_size != 8:
+        raise ValueError("bigWig file: chromosome tree values of %d bytes (8 expected)" % value_size)
+    out = []
+
+    def walk(off):
+        is_leaf, _, count = struct.unpack_from(order + "BBH", data, off)
+        off += 4
+        for _ in range(count):
+            key = data[off:off + key_size]
+            if is_leaf:
+                chrom_id, size = struct.unpack_from(order + "II", data, off + key_size)
+                out.append((key.rstrip(b"\0").decode(), chrom_id, size))
+            else:
+                walk(struct.unpack_from(order + "Q", data, off + key_size)[0])
+            off += key_size + 8
+
+    walk(at + 32)
+    return out
+
+
+def _leaf_blocks(data, at):
+    """[(offset, size)] of every data block the R-tree at `at` lists, leaves left to right."""
+    order = _sub_order(data, at, CIRTREE_MAGIC, "R-tree")
+    out = []
+
+    def walk(off):
+        is_leaf, _, count = struct.unpack_from(order + "BBH", data, off)
+        off += 4
+        for _ in range(count):
+            if is_leaf:
+                out.append(struct.unpack_from(order + "QQ", data, off + 16))
+                off += 32
+            else:
+                walk(struct.unpack_from(order + "Q", data, off + 16)[0])
+                off += 24
+
+    walk(at + 48)
+    return out
+
+
+def _block_spans(block, order):
+    """(chrom id, starts, ends, values) of one inflated data block"""
+    chrom_id, b_start, _b_end, _step, span, kind, _, count = struct.unpack_from(order + "IIIIIBBH", block, 0)
+    if kind == BEDGRAPH:
+        rec = np.frombuffer(block, dtype=np.dtype([("s", order + "u4"), ("e", order + "u4"), ("v", order + "f4")]), count=count, offset=24)
+        return chrom_id, rec["s"].astype(np.int64), rec["e"].astype(np.int64), rec["v"].astype(np.float32)
+    if kind == VARIABLE_STEP:
+        rec = np.frombuffer(block, dtype=np.dtype([("s", order + "u4"), ("v", order + "f4")]), count=count, offset=24)
+        s = rec["s"].astype(np.int64)
+        return chrom_id, s, s + span, rec["v"].astype(np.float32)
+    if kind == FIXED_STEP:
+        v = np.frombuffer(block, dtype=order + "f4", count=count, offset=24).astype(np.float32)
+        s = b_start + np.arange(count, dtype=np.int64) * span
+        return chrom_id, s, s + span, v
+    empty = np.zeros(0, dtype=np.int64)
+    return chrom_id, empty, empty, np.zeros(0, dtype=np.float32)
+
+
+def _read(path):
+    with open(path, "rb") as f:
+        data = f.read()
+    return data, _Header(data)
+
+
+def chroms(path):
+    """{name: size} of the file's chromosomes, in the order of the chromosome tree."""
+    data, h = _read(path)
+    return {name: size for name, _, size in _chrom_tree(data, h.chrom_tree_offset)}
+
+
+def read_spans_file(path):
+    """{chrom: (starts int32, ends int32, values float32)} of the full-resolution data, spans in file order.  A chromosome
+    without data has empty arrays.  Raises ValueError for a file that is not bigWig (bigBed included)."""
+    data, h = _read(path)
+    tree = _chrom_tree(data, h.chrom_tree_offset)
+    by_id = {chrom_id: name for name, chrom_id, _ in tree}
+    per = {name: ([], [], []) for name, _, _ in tree}
+    for offset, size in _leaf_blocks(data, h.unzoomed_index_offset):
+        block = data[offset:offset + size]
+        if h.uncompress_buf_size > 0:
+            block = zlib.decompress(block)
+        chrom_id, s, e, v = _block_spans(block, h.order)
+        name = by_id.get(chrom_id)
+        if name is None:
+            raise ValueError("bigWig file: a data block of chromosome id %d, which the chromosome tree does not list" % chrom_id)
+        lists = per[name]
+        lists[0].append(s), lists[1].append(e), lists[2].append(v)
+    out = {}
+    for name, (s, e, v) in per.items():
+        s = np.concatenate(s) if s else np.zeros(0, dtype=np.int64)
+        e = np.concatenate(e) if e else np.zeros(0, dtype=np.int64)
+        if len(e) and e.max() > 2147483647:
+            raise ValueError("bigWig file: a span of %s ends beyond 2^31 - 1" % name)
+        out[name] = (s.astype(np.int32), e.astype(np.int32), np.concatenate(v) if v else np.zeros(0, dtype=np.float32))
+    return out

@@ -6,6 +6,10 @@ scripts/aggregate_scores_in_intervals.py:107-134 over lib/bx/binned_array.py).
 ``ScoreTrack`` is one chromosome's scores as a dense float32 array in HBM (``bxmi_scores_*`` of include/bxmi.h), NaN = no
 score.  ``aggregate`` answers from host arrays, ``aggregate_dev`` from device arrays.  The sums are the reference's bit for
 bit: float32, added in position order.
+
+``profile`` / ``profile_dev`` are the site profile of scripts/bed_bigwig_profile.py:27-41 over any number of tracks: per offset of
+a window, the float64 sum over all windows in input order and the number of windows with a score there -- the engine under
+``bxmi.cli.bed_bigwig_profile``.
 """
 import collections
 import ctypes as C
@@ -17,6 +21,10 @@ from ._ffi import as_i32, call, ptr
 
 # per interval: valid bases, their ordered float32 sum, their smallest and largest score (+inf / -inf where count == 0)
 Aggregate = collections.namedtuple("Aggregate", "count total minimum maximum")
+
+# per window offset: the float64 sum over the windows in input order, the windows with a score there; and how many columns had to
+# take the ordered chain because their parallel sum was not provably the same bits
+Profile = collections.namedtuple("Profile", "totals valid chain_columns")
 
 MIN_SENTINEL, MAX_SENTINEL = 100000000, -100000000  # aggregate_scores_in_intervals.py:112-113
 
@@ -112,6 +120,58 @@ class ScoreTrack:
         self.aggregate_ptrs(mask, starts.data_ptr(), ends.data_ptr(), n, count.data_ptr(), total.data_ptr(), mn.data_ptr(), mx.data_ptr(),
                             stream=stream)
         return Aggregate(count, total, mn, mx)
+
+
+    def profile(self, win_starts, width):
+        """`profile` of windows that all lie on this track."""
+        return profile([self], np.zeros(len(win_starts), dtype=np.int32), win_starts, width)
+
+
+def _handles(tracks):
+    arr = (C.c_void_p * max(len(tracks), 1))(*[t._h.value for t in tracks])
+    return arr
+
+
+def profile(tracks, track_of, win_starts, width):
+    """Site profile over windows [win_starts[i], win_starts[i] + width) of tracks[track_of[i]] (-1: no track) -> Profile of numpy
+    arrays: totals (float64, the reference's `totals` of bed_bigwig_profile.py:38 bit for bit: one chain over the windows in input
+    order, whatever tracks they interleave), valid (int32) and chain_columns (int).  Positions outside a track, NaN there and
+    windows without a track have no score -- the reference raises OverflowError on a negative window start and fails on an
+    unknown chromosome; here those positions have no data.  +-0 is a score.  The profile itself is totals / valid."""
+    _ffi.require_gpu()
+    tracks = list(tracks)
+    t, s = as_i32(track_of), as_i32(win_starts)
+    if t.shape != s.shape or t.ndim != 1:
+        raise ValueError("track_of and win_starts must be 1-d arrays of equal length")
+    width = int(width)
+    totals = np.zeros(max(width, 0), dtype=np.float64)
+    valid = np.zeros(max(width, 0), dtype=np.int32)
+    chain = C.c_int64(0)
+    call("bxmi_scores_profile", _handles(tracks), len(tracks), ptr(t), ptr(s), len(t), width, ptr(totals), ptr(valid), C.byref(chain))
+    return Profile(totals, valid, chain.value)
+
+
+def profile_dev(tracks, track_of, win_starts, width, stream=None):
+    """`profile` on device arrays: int32 torch tensors on the GPU in, a Profile of torch tensors out (totals float64[width], valid
+    int32[width], chain_columns int64[1]), queued on torch's current stream (or `stream`); nothing is waited for.  An entry of
+    track_of outside [0, len(tracks)) means no track (the device form cannot report it)."""
+    import torch
+
+    tracks = list(tracks)
+    if track_of.dtype != torch.int32 or win_starts.dtype != torch.int32 or track_of.shape != win_starts.shape or track_of.dim() != 1:
+        raise ValueError("track_of and win_starts must be 1-d int32 tensors of equal length")
+    if not (track_of.is_cuda and win_starts.is_cuda):
+        raise ValueError("profile_dev takes device tensors (host arrays: profile)")
+    track_of, win_starts = track_of.contiguous(), win_starts.contiguous()
+    n, dev, width = track_of.numel(), track_of.device, int(width)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    totals = torch.empty(max(width, 0), dtype=torch.float64, device=dev)
+    valid = torch.empty(max(width, 0), dtype=torch.int32, device=dev)
+    chain = torch.empty(1, dtype=torch.int64, device=dev)
+    call("bxmi_scores_profile_dev", _handles(tracks), len(tracks), track_of.data_ptr(), win_starts.data_ptr(), n, width, totals.data_ptr(),
+         valid.data_ptr(), chain.data_ptr(), stream)
+    return Profile(totals, valid, chain)
 
 
 def format_row(chrom, start, stop, count, total, minimum, maximum):

@@ -48,6 +48,7 @@ int bits_set_option(const char *key, int64_t value);
 int64_t bits_get_grid();
 int scores_set_option(const char *key, int64_t value);
 int64_t scores_get_wave_min_len();
+int64_t scores_get_profile_chain();
 
 }  // namespace bxmi
 
@@ -171,7 +172,7 @@ extern "C" int bxmi_set_option(const char *key, int64_t value)
     return fail(BXMI_EINVAL, "bxmi_set_option: unknown key '%s'", key);
 }
 
-// every option in turn: i = 0, 1, ... until BXMI_EINVAL (the interval path's table, then bits.grid, core.poll and scores.wave_min_len)
+// every option in turn: i = 0, 1, ... until BXMI_EINVAL (the interval path's table, then bits.grid, core.poll, scores.wave_min_len and scores.profile_chain)
 extern "C" int bxmi_option_at(int i, const char **key, int64_t *value)
 {
     if (!key || !value) return fail(BXMI_EINVAL, "bxmi_option_at: NULL output");
@@ -189,6 +190,10 @@ extern "C" int bxmi_option_at(int i, const char **key, int64_t *value)
         *key = "scores.wave_min_len", *value = scores_get_wave_min_len();
         return BXMI_OK;
     }
+    if (i == n + 3) {
+        *key = "scores.profile_chain", *value = scores_get_profile_chain();
+        return BXMI_OK;
+    }
     return fail(BXMI_EINVAL, "bxmi_option_at: no option %d", i);
 }
 
@@ -197,7 +202,7 @@ extern "C" int bxmi_get_option(const char *key, int64_t *value)
     if (!key || !value) return fail(BXMI_EINVAL, "bxmi_get_option: NULL argument");
     // (a local: an unknown key must leave *value alone; the loop is bounded by the table, so no failing call overwrites
     // the thread's error text before the real message is set)
-    const int n = ivl_option_count() + 3;
+    const int n = ivl_option_count() + 4;
     for (int i = 0; i < n; i++) {
         const char *k = nullptr;
         int64_t v = 0;

@@ -21,6 +21,7 @@
  *   scripts/bnMapper.py:83-193   transform, the choice between chains, union_elements -> bxmi_chainmap_*
  *   scripts/aggregate_scores_in_intervals.py:107-134, lib/bx/binned_array.py:72-100
  *                                the per-base loop over a BinnedArray of scores      -> bxmi_scores_*
+ *   scripts/bed_bigwig_profile.py:27-41   totals += values; valid += ~isnan per site   -> bxmi_scores_profile*
  *   (intersection.pyx has no C ABI of its own: its cdef classes are the
  *    interface, so the entry points below are what a Cython/ctypes shim of
  *    those classes binds; see INTEGRATION.md.)
@@ -93,6 +94,10 @@ int bxmi_memset(void *dst_dev, int value, size_t bytes);
  *                      word their kernel writes to host memory; 0: they wait for the stream
  *   scores.wave_min_len  bxmi_scores_aggregate: intervals with at least this many bases inside the track get a wave each
  *                      (default 8192; 0 = all of them), shorter ones share a wave 64 at a time
+ *   scores.profile_chain  bxmi_scores_profile: 0 (default) = a column takes the ordered float64 chain where the parallel sum is
+ *                      not provably the same bits; 1 = every column takes it (what exactness costs at most); -1 = no column
+ *                      does and the failing ones keep their parallel sums: WRONG ON PURPOSE, for the test that shows the
+ *                      chain is what makes the totals right
  * Unknown keys return BXMI_EINVAL. */
 int bxmi_set_option(const char *key, int64_t value);
 /* The current value of an option, and every option in turn (i = 0, 1, ... until BXMI_EINVAL): what the tests and A/B tools
@@ -384,6 +389,25 @@ int bxmi_scores_aggregate(bxmi_scores_t *h, const bxmi_bits_t *mask_or_null, con
  * be complete before the work on `stream` starts (the host forms of bxmi_bits_* return with them written). */
 int bxmi_scores_aggregate_dev(bxmi_scores_t *h, const bxmi_bits_t *mask_or_null, const int32_t *start, const int32_t *end, int64_t n,
                               int32_t *count, float *sum, float *min, float *max, void *stream);
+/* Site profile (scripts/bed_bigwig_profile.py:27-41): n windows of `width` bases, window i over positions win_start[i] + j
+ * (j = 0 .. width-1, computed in int64: any int32 start is legal) of tracks[track_of[i]]; track_of[i] == -1 = no track.  A
+ * position outside [0, size) of its track, or a NaN there, has no score (the reference crashes on a negative window start and
+ * on an unknown chromosome; here such positions simply have no data).  +-0 IS a score.  Per column j:
+ *   totals[j]  float64: +0.0, then += (double)score for i = 0 .. n-1 IN INPUT ORDER, one rounding per add, +0.0 for a missing
+ *              score -- bit for bit the reference's `totals`, chromosomes interleaved as the input interleaves them
+ *   valid[j]   the windows that have a score at offset j
+ * Columns whose parallel sum is provably exact (csrc/profile.hpp; e.g. any realistic batch of three-decimal scores) never
+ * run the chain; the others do, and a chain costs n dependent float64 adds however many CUs there are.
+ * *chain_columns_or_null = the columns that took the chain.  width < 1, n outside [0, 2^31-1], n_tracks < 0 or a
+ * track_of[i] >= n_tracks -> BXMI_EINVAL; n == 0 gives zeros.  All tracks live on the current device.  The pass's scratch
+ * belongs to the library: one profile call at a time per process.  Host arrays; BLOCKS until the outputs are written. */
+int bxmi_scores_profile(bxmi_scores_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *win_start, int64_t n,
+                        int32_t width, double *totals, int32_t *valid, int64_t *chain_columns_or_null);
+/* Device variant: `tracks` stays a host array of handles; track_of, win_start, totals, valid and chain_columns_or_null are device
+ * pointers of natural alignment.  Stream-ordered on `stream`, no host synchronisation; the library's scratch is in use until the
+ * work completes.  The entries of track_of cannot be checked without a synchronisation: one outside [0, n_tracks) is no track. */
+int bxmi_scores_profile_dev(bxmi_scores_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *win_start, int64_t n,
+                            int32_t width, double *totals, int32_t *valid, int64_t *chain_columns_or_null, void *stream);
 
 /* ---- BED text -> SoA columns on the host (the step before the hot path) ------
  * Strict single-pass parser for what lib/bx/bitset_builders.py:33-46 and
