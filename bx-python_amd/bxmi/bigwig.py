@@ -8,7 +8,9 @@ Read: the header in either byte order (fields in the order of lib/bx/bbi/bbi_fil
 ids, sizes; bpt_file.pyx), the R-tree over the full-resolution data (cirtree_file.pyx) leaf by leaf, left to right, and the
 three kinds of data block: bedGraph (1), variableStep (2), fixedStep (3), inflated when ``uncompress_buf_size > 0``.  As in the
 reference, item i of a fixedStep block starts at ``block start + i * span`` (its ``step`` field is read and not used), and a
-block of another kind contributes nothing.  Zoom levels and summaries are not read.
+block of another kind contributes nothing.  Of the zoom levels only the headers' reduction levels are read (``zoom_reductions``:
+what the reference's choice between a zoom level and the full data depends on); their summaries are not.  ``chroms``,
+``read_spans_file`` and ``zoom_reductions`` take a path, or ``data=`` the file's bytes already in memory.
 """
 import struct
 import zlib
@@ -120,22 +122,31 @@ def _block_spans(block, order):
     return chrom_id, empty, empty, np.zeros(0, dtype=np.float32)
 
 
-def _read(path):
-    with open(path, "rb") as f:
-        data = f.read()
+def _read(path, data=None):
+    if data is None:
+        with open(path, "rb") as f:
+            data = f.read()
     return data, _Header(data)
 
 
-def chroms(path):
+def zoom_reductions(path=None, data=None):
+    """[reduction_level] of the zoom headers (bbi_file.pyx:156-164: 24 bytes each from offset 64), in file order."""
+    data, h = _read(path, data)
+    if len(data) < 64 + 24 * h.zoom_levels:
+        raise ValueError("not a bigWig file: the zoom headers are cut short")
+    return [struct.unpack_from(h.order + "I", data, 64 + 24 * i)[0] for i in range(h.zoom_levels)]
+
+
+def chroms(path=None, data=None):
     """{name: size} of the file's chromosomes, in the order of the chromosome tree."""
-    data, h = _read(path)
+    data, h = _read(path, data)
     return {name: size for name, _, size in _chrom_tree(data, h.chrom_tree_offset)}
 
 
-def read_spans_file(path):
+def read_spans_file(path=None, data=None):
     """{chrom: (starts int32, ends int32, values float32)} of the full-resolution data, spans in file order.  A chromosome
     without data has empty arrays.  Raises ValueError for a file that is not bigWig (bigBed included)."""
-    data, h = _read(path)
+    data, h = _read(path, data)
     tree = _chrom_tree(data, h.chrom_tree_offset)
     by_id = {chrom_id: name for name, chrom_id, _ in tree}
     per = {name: ([], [], []) for name, _, _ in tree}

@@ -1,0 +1,64 @@
+#!/usr/bin/env python
+"""
+Summarize a bigWig file over every interval of a BED file: SIZE equal bins per interval, one statistic per bin, computed from
+the file's full-resolution data (no zoom levels).  One output line per BED row: chrom, start, end and SIZE values, separated
+by tabs.  A row whose chromosome the bigWig file does not have, or whose interval is empty, prints n/a for every value.
+
+usage: %prog score.bw SIZE [-t mean|min|max|coverage|std] < bed_file.bed
+"""
+# There is no reference script for this: the reference offers BigWigFile.summarize / query (lib/bx/bbi/bbi_file.pyx:187-260) as
+# calls only, one region at a time; the line format here is this project's own.  The values are those of `query` from full data
+# (summarize_from_full), printed with %.17g so that they read back as the same float64; the whole BED file is ONE device call
+# (bxmi.summary.summarize).  Comment and header lines of the BED are skipped.
+import sys
+
+import numpy as np
+
+from bxmi import summary
+from bxmi.genomic import GenomicInterval, GenomicIntervalReader
+
+KINDS = ("mean", "min", "max", "coverage", "std")
+
+
+def main(argv=None, stdin=None, out=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    kind = "mean"
+    if "-t" in argv:
+        at = argv.index("-t")
+        if at + 1 >= len(argv):
+            sys.exit(__doc__.replace("%prog", "bigwig_summary"))
+        kind = argv[at + 1]
+        del argv[at:at + 2]
+    if len(argv) != 2 or kind not in KINDS:
+        sys.exit(__doc__.replace("%prog", "bigwig_summary"))
+    out = out or sys.stdout
+    size = int(argv[1])
+    tracks = summary.SpanTrack.from_bigwig(argv[0])
+    try:
+        order = list(tracks)
+        index = {chrom: k for k, chrom in enumerate(order)}
+        rows = [r for r in GenomicIntervalReader(stdin or sys.stdin) if isinstance(r, GenomicInterval)]
+        track_of = np.array([index.get(r.chrom, -1) for r in rows], dtype=np.int32)
+        starts = np.array([r.start for r in rows], dtype=np.int64)
+        ends = np.array([r.end for r in rows], dtype=np.int64)
+        res = summary.summarize([tracks[c] for c in order], track_of, starts, ends, size)
+        answered = (track_of >= 0) & (starts < ends)
+        if kind == "min":
+            values = res.min_val
+        elif kind == "max":
+            values = res.max_val
+        else:
+            safe_ends = np.where(answered, ends, starts + 1)
+            mean, coverage, std_dev = summary.stats(res, starts, safe_ends, size)
+            values = {"mean": mean, "coverage": coverage, "std": std_dev}[kind]
+        for i, r in enumerate(rows):
+            cells = ["%.17g" % x for x in values[i]] if answered[i] else ["n/a"] * size
+            out.write("\t".join([r.chrom, str(r.start), str(r.end)] + cells) + "\n")
+        out.flush()
+    finally:
+        for t in tracks.values():
+            t.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -22,6 +22,8 @@
  *   scripts/aggregate_scores_in_intervals.py:107-134, lib/bx/binned_array.py:72-100
  *                                the per-base loop over a BinnedArray of scores      -> bxmi_scores_*
  *   scripts/bed_bigwig_profile.py:27-41   totals += values; valid += ~isnan per site   -> bxmi_scores_profile*
+ *   lib/bx/bbi/bbi_file.pyx:66-111,187-260, bigwig_file.pyx:93-108,176-185
+ *                                BigWigFile.summarize_from_full / query over full data -> bxmi_spans_*
  *   (intersection.pyx has no C ABI of its own: its cdef classes are the
  *    interface, so the entry points below are what a Cython/ctypes shim of
  *    those classes binds; see INTEGRATION.md.)
@@ -408,6 +410,38 @@ int bxmi_scores_profile(bxmi_scores_t *const *tracks, int32_t n_tracks, const in
  * work completes.  The entries of track_of cannot be checked without a synchronisation: one outside [0, n_tracks) is no track. */
 int bxmi_scores_profile_dev(bxmi_scores_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *win_start, int64_t n,
                             int32_t width, double *totals, int32_t *valid, int64_t *chain_columns_or_null, void *stream);
+
+/* ---- span tracks and their binned summaries  (lib/bx/bbi/bbi_file.pyx, bigwig_file.pyx) ----------
+ * One bxmi_spans_t is ONE chromosome's bigWig items -- [start[i], end[i]) with value[i] -- in HBM, IN FILE ORDER (the order the
+ * reference's block handler meets them; bxmi.bigwig.read_spans_file returns it).  The dense bxmi_scores_t cannot serve summaries:
+ * the reference weights each ITEM, by size * (overlap / size) in float64, which is not always the integer overlap.
+ * A negative coordinate -> BXMI_EINVAL.  *ordered (bxmi_spans_info) = 1 when starts AND ends are both non-decreasing, as in every
+ * real bigWig: the items that overlap a range are then one contiguous run and summaries take the fast path (csrc/summary.hpp);
+ * any other track is legal and takes the general path, which walks the whole track for every region. */
+typedef struct bxmi_spans bxmi_spans_t;
+int bxmi_spans_create(const int32_t *start, const int32_t *end, const float *value, int64_t n, bxmi_spans_t **out);
+int bxmi_spans_destroy(bxmi_spans_t *h);
+int bxmi_spans_info(const bxmi_spans_t *h, int64_t *n, int *ordered);
+/* BigWigFile.summarize_from_full (bbi_file.pyx:80-111, bigwig_file.pyx:176-185) for n regions [start[i], end[i]) of
+ * tracks[track_of[i]], `size` bins each.  step = (end - start) / size; bin j = [start + step * j, start + step * (j + 1)); the last
+ * (end - start) % size bases belong to no bin; step == 0 leaves every bin empty.  Items are clipped to the region; per bin, over the
+ * items that overlap it IN FILE ORDER, with n = the clipped length and w = (double)n * ((double)overlap / n):
+ *   valid += w, sum += (double)value * w, sumsq += (double)(value * value) * w  (the square in float32), one rounding per operation,
+ *   never fused; max / min take the value where it is larger / smaller (compared in double: a NaN value changes neither);
+ *   valid is rounded half to even at the end.  Start values: 0, +inf (min), -inf (max), 0, 0.
+ * The five outputs are [n, size] float64 planes, row-major (64-bit offsets: n * size may pass 2^31), bit for bit the reference's
+ * valid_count, min_val, max_val, sum_data, sum_squares.  track_of[i] < 0 (unknown chromosome) or start[i] >= end[i] (the
+ * reference answers None) is an EMPTY ROW: 0, +inf, -inf, 0, 0 in every bin.  Zoom levels are not involved.
+ * size < 1, n outside [0, 2^31-1], n_tracks < 0, a track_of[i] >= n_tracks, a negative start[i] or end[i] -> BXMI_EINVAL; n == 0
+ * succeeds without a launch.  All tracks live on the current device.  The track table and the staging belong to the library: one
+ * summary call at a time per process.  Host arrays; BLOCKS until the outputs are written. */
+int bxmi_spans_summarize(bxmi_spans_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                         int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq);
+/* Device variant: `tracks` stays a host array of handles; the other arrays are device pointers of natural alignment.  Stream-ordered
+ * on `stream`, no host synchronisation.  The entries cannot be checked without a synchronisation: a track_of[i] outside
+ * [0, n_tracks) or a negative coordinate gives an empty row. */
+int bxmi_spans_summarize_dev(bxmi_spans_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                             int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq, void *stream);
 
 /* ---- BED text -> SoA columns on the host (the step before the hot path) ------
  * Strict single-pass parser for what lib/bx/bitset_builders.py:33-46 and
