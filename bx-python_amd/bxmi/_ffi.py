@@ -206,6 +206,31 @@ def ptr(a):
     return a.ctypes.data_as(vp) if a is not None else None
 
 
+def handles(tracks):
+    """The handle array (`T *const *`, never of length 0) the track-batch entry points take for a list of tracks."""
+    return (vp * max(len(tracks), 1))(*[t._h.value for t in tracks])
+
+
+def close_all(tracks):
+    for t in tracks:
+        t.close()
+
+
+def device_args(who, host_form, names, tensors, stream):
+    """What every device form begins with: `tensors` (called `names`) must be 1-d int32 torch tensors of equal length on the GPU
+    -> (the tensors made contiguous, their length, their device, `stream` or else torch's current stream there)."""
+    import torch
+
+    first = tensors[0]
+    if any(a.dtype != torch.int32 or a.dim() != 1 or a.shape != first.shape for a in tensors):
+        raise ValueError("%s and %s must be 1-d int32 tensors of equal length" % (", ".join(names[:-1]), names[-1]))
+    if not all(a.is_cuda for a in tensors):
+        raise ValueError("%s takes device tensors (host arrays: %s)" % (who, host_form))
+    if stream is None:
+        stream = torch.cuda.current_stream(first.device).cuda_stream
+    return [a.contiguous() for a in tensors], first.numel(), first.device, stream
+
+
 class DeviceArray:
     """A raw HBM allocation owned by Python (used by the bench / sharded driver)."""
 

@@ -13,7 +13,7 @@ import sys
 
 import numpy as np
 
-from bxmi import scores, wiggle
+from bxmi import _ffi, scores, wiggle
 
 MAX = 512 * 1024 * 1024  # BinnedArray's default max_size (lib/bx/binned_array.py) and the size of a default bitset
 
@@ -92,8 +92,7 @@ def main(argv=None, out=None):
             with open(opt.out_file, "w") as fd:
                 aggregate_file(opt.interval_file, fd, tracks, masks)
     finally:
-        for t in tracks.values():
-            t.close()
+        _ffi.close_all(tracks.values())
 
 
 if __name__ == "__main__":

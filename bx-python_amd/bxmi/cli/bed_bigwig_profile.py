@@ -14,8 +14,8 @@ import sys
 
 import numpy as np
 
-from bxmi import bigwig, scores, wiggle
-from bxmi.genomic import GenomicInterval, GenomicIntervalReader
+from bxmi import _ffi, bigwig, scores, wiggle
+from bxmi.genomic import track_rows
 
 
 def load_tracks(path):
@@ -32,16 +32,6 @@ def load_tracks(path):
     return tracks
 
 
-def windows(bed_lines, names, padding):
-    """(track_of, win_starts) of the BED's rows, in file order; names: chromosome -> index of its track"""
-    track_of, starts = [], []
-    for row in GenomicIntervalReader(bed_lines):
-        if isinstance(row, GenomicInterval):
-            track_of.append(names.get(row.chrom, -1))
-            starts.append((row.start + row.end) // 2 - padding)
-    return np.array(track_of, dtype=np.int32), np.array(starts, dtype=np.int64)
-
-
 def main(argv=None, stdin=None, out=None):
     argv = sys.argv[1:] if argv is None else argv
     if len(argv) != 2:
@@ -50,16 +40,15 @@ def main(argv=None, stdin=None, out=None):
     padding = int(argv[1])
     tracks = load_tracks(argv[0])
     try:
-        order = list(tracks)
-        track_of, starts = windows(stdin or sys.stdin, {chrom: k for k, chrom in enumerate(order)}, padding)
+        rows, track_of = track_rows(stdin or sys.stdin, tracks)
+        starts = np.array([(r.start + r.end) // 2 - padding for r in rows], dtype=np.int64)
         if padding > 0:
-            res = scores.profile([tracks[c] for c in order], track_of, starts, 2 * padding)
+            res = scores.profile(tracks.values(), track_of, starts, 2 * padding)
             with np.errstate(all="ignore"):
                 np.savetxt(out, res.totals / res.valid)
         out.flush()
     finally:
-        for t in tracks.values():
-            t.close()
+        _ffi.close_all(tracks.values())
 
 
 if __name__ == "__main__":

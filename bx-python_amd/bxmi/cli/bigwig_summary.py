@@ -14,8 +14,8 @@ import sys
 
 import numpy as np
 
-from bxmi import summary
-from bxmi.genomic import GenomicInterval, GenomicIntervalReader
+from bxmi import _ffi, summary
+from bxmi.genomic import track_rows
 
 KINDS = ("mean", "min", "max", "coverage", "std")
 
@@ -35,13 +35,10 @@ def main(argv=None, stdin=None, out=None):
     size = int(argv[1])
     tracks = summary.SpanTrack.from_bigwig(argv[0])
     try:
-        order = list(tracks)
-        index = {chrom: k for k, chrom in enumerate(order)}
-        rows = [r for r in GenomicIntervalReader(stdin or sys.stdin) if isinstance(r, GenomicInterval)]
-        track_of = np.array([index.get(r.chrom, -1) for r in rows], dtype=np.int32)
+        rows, track_of = track_rows(stdin or sys.stdin, tracks)
         starts = np.array([r.start for r in rows], dtype=np.int64)
         ends = np.array([r.end for r in rows], dtype=np.int64)
-        res = summary.summarize([tracks[c] for c in order], track_of, starts, ends, size)
+        res = summary.summarize(tracks.values(), track_of, starts, ends, size)
         answered = (track_of >= 0) & (starts < ends)
         if kind == "min":
             values = res.min_val
@@ -56,8 +53,7 @@ def main(argv=None, stdin=None, out=None):
             out.write("\t".join([r.chrom, str(r.start), str(r.end)] + cells) + "\n")
         out.flush()
     finally:
-        for t in tracks.values():
-            t.close()
+        _ffi.close_all(tracks.values())
 
 
 if __name__ == "__main__":

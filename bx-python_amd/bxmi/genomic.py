@@ -11,6 +11,7 @@ A reader yields, in file order, `Header` (first line if it is a comment line), `
 `ParseError`s and logs them in `skipped` / `skipped_lines`; `BitsetSafeReaderWrapper`
 additionally drops rows that end beyond the chromosome length.
 """
+import numpy as np
 from bx.bitset import MAX
 
 FIRST_LINE_IS_HEADER = object()
@@ -613,3 +614,12 @@ class BitsetSafeReaderWrapper(NiceReaderWrapper):
                 continue
             self.delivered += 1
             return item
+
+
+def track_rows(lines, tracks):
+    """(rows, track_of) for the track-batch command lines: the GenomicInterval rows of a BED in file order (comment and header
+    lines skipped) and, as an int32 array, the position of each row's chromosome in the {chrom: track} dict `tracks`, -1 where it
+    has none."""
+    index = {chrom: k for k, chrom in enumerate(tracks)}
+    rows = [r for r in GenomicIntervalReader(lines) if isinstance(r, GenomicInterval)]
+    return rows, np.array([index.get(r.chrom, -1) for r in rows], dtype=np.int32)

@@ -121,14 +121,7 @@ class ChainMap:
         stream (or `stream`).  Blocks until the row total is known (bxmi.h: bxmi_chainmap_map_dev)."""
         import torch
 
-        if starts.dtype != torch.int32 or ends.dtype != torch.int32 or starts.shape != ends.shape or starts.dim() != 1:
-            raise ValueError("starts and ends must be 1-d int32 tensors of equal length")
-        if not (starts.is_cuda and ends.is_cuda):
-            raise ValueError("map_dev takes device tensors (host arrays: map)")
-        starts, ends = starts.contiguous(), ends.contiguous()
-        nf, dev = starts.numel(), starts.device
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
+        (starts, ends), nf, dev, stream = _ffi.device_args("map_dev", "map", ("starts", "ends"), (starts, ends), stream)
         chain = torch.empty(nf, dtype=torch.int32, device=dev)
         status = torch.empty(nf, dtype=torch.int32, device=dev)
         offsets = torch.empty(nf + 1, dtype=torch.int64, device=dev)

@@ -107,29 +107,16 @@ class ScoreTrack:
         current stream (or `stream`); nothing is waited for."""
         import torch
 
-        if starts.dtype != torch.int32 or ends.dtype != torch.int32 or starts.shape != ends.shape or starts.dim() != 1:
-            raise ValueError("starts and ends must be 1-d int32 tensors of equal length")
-        if not (starts.is_cuda and ends.is_cuda):
-            raise ValueError("aggregate_dev takes device tensors (host arrays: aggregate)")
-        starts, ends = starts.contiguous(), ends.contiguous()
-        n, dev = starts.numel(), starts.device
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
+        (starts, ends), n, dev, stream = _ffi.device_args("aggregate_dev", "aggregate", ("starts", "ends"), (starts, ends), stream)
         count = torch.empty(n, dtype=torch.int32, device=dev)
         total, mn, mx = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
         self.aggregate_ptrs(mask, starts.data_ptr(), ends.data_ptr(), n, count.data_ptr(), total.data_ptr(), mn.data_ptr(), mx.data_ptr(),
                             stream=stream)
         return Aggregate(count, total, mn, mx)
 
-
     def profile(self, win_starts, width):
         """`profile` of windows that all lie on this track."""
         return profile([self], np.zeros(len(win_starts), dtype=np.int32), win_starts, width)
-
-
-def _handles(tracks):
-    arr = (C.c_void_p * max(len(tracks), 1))(*[t._h.value for t in tracks])
-    return arr
 
 
 def profile(tracks, track_of, win_starts, width):
@@ -147,7 +134,7 @@ def profile(tracks, track_of, win_starts, width):
     totals = np.zeros(max(width, 0), dtype=np.float64)
     valid = np.zeros(max(width, 0), dtype=np.int32)
     chain = C.c_int64(0)
-    call("bxmi_scores_profile", _handles(tracks), len(tracks), ptr(t), ptr(s), len(t), width, ptr(totals), ptr(valid), C.byref(chain))
+    call("bxmi_scores_profile", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), len(t), width, ptr(totals), ptr(valid), C.byref(chain))
     return Profile(totals, valid, chain.value)
 
 
@@ -158,18 +145,12 @@ def profile_dev(tracks, track_of, win_starts, width, stream=None):
     import torch
 
     tracks = list(tracks)
-    if track_of.dtype != torch.int32 or win_starts.dtype != torch.int32 or track_of.shape != win_starts.shape or track_of.dim() != 1:
-        raise ValueError("track_of and win_starts must be 1-d int32 tensors of equal length")
-    if not (track_of.is_cuda and win_starts.is_cuda):
-        raise ValueError("profile_dev takes device tensors (host arrays: profile)")
-    track_of, win_starts = track_of.contiguous(), win_starts.contiguous()
-    n, dev, width = track_of.numel(), track_of.device, int(width)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    (track_of, win_starts), n, dev, stream = _ffi.device_args("profile_dev", "profile", ("track_of", "win_starts"), (track_of, win_starts), stream)
+    width = int(width)
     totals = torch.empty(max(width, 0), dtype=torch.float64, device=dev)
     valid = torch.empty(max(width, 0), dtype=torch.int32, device=dev)
     chain = torch.empty(1, dtype=torch.int64, device=dev)
-    call("bxmi_scores_profile_dev", _handles(tracks), len(tracks), track_of.data_ptr(), win_starts.data_ptr(), n, width, totals.data_ptr(),
+    call("bxmi_scores_profile_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), win_starts.data_ptr(), n, width, totals.data_ptr(),
          valid.data_ptr(), chain.data_ptr(), stream)
     return Profile(totals, valid, chain)
 

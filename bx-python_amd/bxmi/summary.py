@@ -56,10 +56,6 @@ class SpanTrack:
             pass
 
 
-def _handles(tracks):
-    return (C.c_void_p * max(len(tracks), 1))(*[t._h.value for t in tracks])
-
-
 def summarize(tracks, track_of, starts, ends, size):
     """summarize_from_full of regions [starts[i], ends[i]) of tracks[track_of[i]], `size` bins each -> Summary of [n, size] float64
     numpy arrays.  track_of[i] < 0 (unknown chromosome) or starts[i] >= ends[i] -- where the reference returns None -- gives an
@@ -71,7 +67,7 @@ def summarize(tracks, track_of, starts, ends, size):
         raise ValueError("track_of, starts and ends must be 1-d arrays of equal length")
     size = int(size)
     out = [np.empty((len(t), max(size, 0)), dtype=np.float64) for _ in range(5)]
-    call("bxmi_spans_summarize", _handles(tracks), len(tracks), ptr(t), ptr(s), ptr(e), len(t), size, *[ptr(a) for a in out])
+    call("bxmi_spans_summarize", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), ptr(e), len(t), size, *[ptr(a) for a in out])
     return Summary(*out)
 
 
@@ -85,17 +81,11 @@ def summarize_dev(tracks, track_of, starts, ends, size, stream=None):
     import torch
 
     tracks = list(tracks)
-    for a in (track_of, starts, ends):
-        if a.dtype != torch.int32 or a.dim() != 1 or a.shape != track_of.shape:
-            raise ValueError("track_of, starts and ends must be 1-d int32 tensors of equal length")
-        if not a.is_cuda:
-            raise ValueError("summarize_dev takes device tensors (host arrays: summarize)")
-    track_of, starts, ends = track_of.contiguous(), starts.contiguous(), ends.contiguous()
-    n, dev, size = track_of.numel(), track_of.device, int(size)
-    if stream is None:
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    (track_of, starts, ends), n, dev, stream = _ffi.device_args("summarize_dev", "summarize", ("track_of", "starts", "ends"),
+                                                                (track_of, starts, ends), stream)
+    size = int(size)
     out = [torch.empty((n, max(size, 0)), dtype=torch.float64, device=dev) for _ in range(5)]
-    call("bxmi_spans_summarize_dev", _handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), ends.data_ptr(), n, size,
+    call("bxmi_spans_summarize_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), ends.data_ptr(), n, size,
          *[a.data_ptr() for a in out], stream)
     return Summary(*out)
 

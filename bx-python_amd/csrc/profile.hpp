@@ -23,6 +23,7 @@
 //   (A bound by count and largest exponent, n * 2^(E+1), is up to two bits looser: a million three-decimal scores of [0, 1]
 //   would miss it by one bit, S' passes with room.)
 //
+//   track_table_kernel (track_batch.hpp, 16 tracks per launch) writes the table PfTrack[n_tracks + 1] the others read.
 //   pf_partial_kernel  a wave owns 64 adjacent columns (lane = column) and one chunk of PF_CHUNK consecutive windows.  The
 //                      window's track and start are wave-uniform; the 64 lanes read 64 consecutive floats with one coalesced,
 //                      generally unaligned load, PF_AHEAD windows' loads in flight (pf_meta / pf_fetch).  Per lane: the float64
@@ -43,25 +44,11 @@ constexpr int PF_AHEAD = 8;           // windows whose loads a wave of the parti
 constexpr int PF_CHAIN_AHEAD = 16;    // the same for the chain, which has nothing else to hide its loads behind
 constexpr int PF_THREADS = 256;       // partial pass and combine: 4 waves
 constexpr int PF_Q_NONE = 1 << 20;    // q of a column (chunk) without a finite non-zero score
-constexpr int PF_TABLE_PACK = 16;     // tracks per launch of pf_table_kernel
 
 struct PfTrack {
     const float *values;
     int64_t size;
 };
-struct PfTrackPack {
-    PfTrack t[PF_TABLE_PACK];
-};
-
-// table[base .. base + count) = pack: the track table travels in kernel arguments, so filling it is stream-ordered without a
-// host buffer that would have to outlive the call.
-__global__ __launch_bounds__(64) void pf_table_kernel(PfTrack *__restrict__ table, int base, int count, PfTrackPack pack)
-{
-    if (threadIdx.x != 0) return;
-#pragma unroll
-    for (int k = 0; k < PF_TABLE_PACK; k++)
-        if (k < count) table[base + k] = pack.t[k];
-}
 
 // What a wave needs of 64 consecutive windows, window base + l in lane l: its track's array and size (0 where the window has
 // no track or lies beyond `end`) and its start.  Three vector loads per 64 windows; pf_fetch hands a window's triple to the

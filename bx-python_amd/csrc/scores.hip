@@ -8,6 +8,7 @@
 #include "common.hpp"
 #include "scores.hpp"
 #include "profile.hpp"
+#include "track_batch.hpp"
 
 namespace bxmi {
 
@@ -236,35 +237,20 @@ extern "C" int bxmi_scores_aggregate(bxmi_scores_t *h, const bxmi_bits_t *mask_o
 // The scratch of the profile pass belongs to the library, not to a track (a call may name no track at all): one profile call
 // at a time per process may be in flight.
 namespace {
-struct ProfileScratch {
-    int device = -1;
+struct ProfileBufs {
     DevBuf table;                        // PfTrack[n_tracks + 1], the last one the spare entry
     DevBuf p_sum, p_abs, p_valid, p_q;   // [chunks][width]
     DevBuf col_flag, group_list;         // int32[width], int32[groups]
     DevBuf ctl;                          // 8 bytes chain_columns, 4 bytes listed groups, 4 bytes the spare entry's "track"
     DevBuf q_track, q_start, r_totals, r_valid;  // staging of the host form
-    hipStream_t stream = nullptr;
-    void release()
-    {
-        for (DevBuf *b : {&table, &p_sum, &p_abs, &p_valid, &p_q, &col_flag, &group_list, &ctl, &q_track, &q_start, &r_totals, &r_valid}) b->release();
-        if (stream) (void)hipStreamDestroy(stream);
-        stream = nullptr;
-    }
 };
-// (never destroyed: at process exit the runtime may be gone before a static destructor could free device memory)
-ProfileScratch &g_profile = *new ProfileScratch();
-std::mutex g_profile_lock;
+LibraryScratch<ProfileBufs> &g_profile = LibraryScratch<ProfileBufs>::leaked();
 }  // namespace
 
 static int profile_check(const char *who, bxmi_scores_t *const *tracks, int32_t n_tracks, const void *track_of, const void *win_start, int64_t n,
                          int32_t width, const void *totals, const void *valid)
 {
-    if (width < 1) return fail(BXMI_EINVAL, "%s: width = %d, must be at least 1", who, (int)width);
-    if (n < 0 || n > 2147483647LL) return fail(BXMI_EINVAL, "%s: n = %lld outside [0, 2^31-1]", who, (long long)n);
-    if (n_tracks < 0) return fail(BXMI_EINVAL, "%s: n_tracks = %d is negative", who, (int)n_tracks);
-    if (n_tracks > 0 && !tracks) return fail(BXMI_EINVAL, "%s: NULL track list", who);
-    for (int32_t t = 0; t < n_tracks; t++)
-        if (!tracks[t]) return fail(BXMI_EINVAL, "%s: track %d is a NULL handle", who, (int)t);
+    BXMI_TRY(track_batch_check(who, "width", width, tracks, n_tracks, n));
     if (!totals || !valid || (n > 0 && (!track_of || !win_start))) return fail(BXMI_EINVAL, "%s: NULL array", who);
     return BXMI_OK;
 }
@@ -272,13 +258,7 @@ static int profile_check(const char *who, bxmi_scores_t *const *tracks, int32_t 
 static int profile_dev_locked(const char *who, bxmi_scores_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *win_start,
                               int64_t n, int32_t width, double *totals, int32_t *valid, int64_t *chain_columns_or_null, hipStream_t st)
 {
-    ProfileScratch &S = g_profile;
-    int dev = -1;
-    BXMI_HIP(hipGetDevice(&dev));
-    if (S.device != dev) {
-        S.release();
-        S.device = dev;
-    }
+    ProfileBufs &S = g_profile.bufs;
     BXMI_HIP(hipMemsetAsync(totals, 0, (size_t)width * sizeof(double), st));
     BXMI_HIP(hipMemsetAsync(valid, 0, (size_t)width * sizeof(int32_t), st));
     if (chain_columns_or_null) BXMI_HIP(hipMemsetAsync(chain_columns_or_null, 0, sizeof(int64_t), st));
@@ -287,7 +267,6 @@ static int profile_dev_locked(const char *who, bxmi_scores_t *const *tracks, int
     const int64_t blocks = div_up(items, PF_THREADS / 64);
     if (blocks > 2147483647LL) return fail(BXMI_EINVAL, "%s: %lld windows of %d bases are more than one call takes", who, (long long)n, (int)width);
     const size_t cells = (size_t)chunks * (size_t)width;
-    BXMI_TRY(S.table.reserve((size_t)(n_tracks + 1) * sizeof(PfTrack)));
     BXMI_TRY(S.p_sum.reserve(cells * sizeof(double)));
     BXMI_TRY(S.p_abs.reserve(cells * sizeof(double)));
     BXMI_TRY(S.p_valid.reserve(cells * sizeof(int32_t)));
@@ -298,17 +277,9 @@ static int profile_dev_locked(const char *who, bxmi_scores_t *const *tracks, int
     BXMI_HIP(hipMemsetAsync(S.ctl.p, 0, 16, st));
     unsigned long long *chain_columns = S.ctl.as<unsigned long long>();
     int32_t *n_listed = S.ctl.as<int32_t>() + 2;
-    PfTrack *table = S.table.as<PfTrack>();
-    for (int32_t base = 0; base <= n_tracks; base += PF_TABLE_PACK) {
-        PfTrackPack pack{};
-        const int count = n_tracks + 1 - base < PF_TABLE_PACK ? n_tracks + 1 - base : PF_TABLE_PACK;
-        for (int k = 0; k < count; k++) {
-            if (base + k < n_tracks) pack.t[k] = PfTrack{tracks[base + k]->values.as<float>(), tracks[base + k]->size};
-            else pack.t[k] = PfTrack{reinterpret_cast<const float *>(S.ctl.as<int32_t>() + 3), 0};
-        }
-        hipLaunchKernelGGL(pf_table_kernel, dim3(1), dim3(64), 0, st, table, (int)base, count, pack);
-        BXMI_LAUNCH_CHECK();
-    }
+    const PfTrack spare{reinterpret_cast<const float *>(S.ctl.as<int32_t>() + 3), 0};
+    BXMI_TRY((fill_track_table<PfTrack, 16>(S.table, n_tracks, [&](int k) { return PfTrack{tracks[k]->values.as<float>(), tracks[k]->size}; }, spare, st)));
+    const PfTrack *table = S.table.as<PfTrack>();
     hipLaunchKernelGGL(pf_partial_kernel, dim3((unsigned)blocks), dim3(PF_THREADS), 0, st, table, (int)n_tracks, track_of, win_start, n, (int64_t)width,
                        groups, items, S.p_sum.as<double>(), S.p_abs.as<double>(), S.p_valid.as<int32_t>(), S.p_q.as<int32_t>());
     BXMI_LAUNCH_CHECK();
@@ -330,7 +301,8 @@ extern "C" int bxmi_scores_profile_dev(bxmi_scores_t *const *tracks, int32_t n_t
                                        int32_t width, double *totals, int32_t *valid, int64_t *chain_columns_or_null, void *stream)
 {
     BXMI_TRY(profile_check("bxmi_scores_profile_dev", tracks, n_tracks, track_of, win_start, n, width, totals, valid));
-    std::lock_guard<std::mutex> hold(g_profile_lock);
+    std::lock_guard<std::mutex> hold(g_profile.lock);
+    BXMI_TRY(g_profile.enter());
     return profile_dev_locked("bxmi_scores_profile_dev", tracks, n_tracks, track_of, win_start, n, width, totals, valid, chain_columns_or_null,
                               as_stream(stream));
 }
@@ -340,33 +312,26 @@ extern "C" int bxmi_scores_profile(bxmi_scores_t *const *tracks, int32_t n_track
 {
     const char *who = "bxmi_scores_profile";
     BXMI_TRY(profile_check(who, tracks, n_tracks, track_of, win_start, n, width, totals, valid));
-    for (int64_t i = 0; i < n; i++)
-        if (track_of[i] >= n_tracks)
-            return fail(BXMI_EINVAL, "%s: track_of[%lld] = %d, but there are %d tracks", who, (long long)i, (int)track_of[i], (int)n_tracks);
-    std::lock_guard<std::mutex> hold(g_profile_lock);
-    ProfileScratch &S = g_profile;
-    int dev = -1;
-    BXMI_HIP(hipGetDevice(&dev));
-    if (S.device != dev) {
-        S.release();
-        S.device = dev;
-    }
-    if (!S.stream) BXMI_HIP(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
+    BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    std::lock_guard<std::mutex> hold(g_profile.lock);
+    BXMI_TRY(g_profile.enter(true));
+    ProfileBufs &S = g_profile.bufs;
+    const hipStream_t stream = g_profile.stream;
     const size_t rows = (size_t)(n > 0 ? n : 1) * sizeof(int32_t);
     BXMI_TRY(S.q_track.reserve(rows));
     BXMI_TRY(S.q_start.reserve(rows));
     BXMI_TRY(S.r_totals.reserve((size_t)width * sizeof(double) + sizeof(int64_t)));  // (the count of chain columns rides behind the totals)
     BXMI_TRY(S.r_valid.reserve((size_t)width * sizeof(int32_t)));
     if (n > 0) {
-        BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, S.stream));
-        BXMI_HIP(hipMemcpyAsync(S.q_start.p, win_start, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, S.stream));
+        BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        BXMI_HIP(hipMemcpyAsync(S.q_start.p, win_start, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     }
     int64_t *r_chain = reinterpret_cast<int64_t *>(S.r_totals.as<double>() + width);
     BXMI_TRY(profile_dev_locked(who, tracks, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), n, width, S.r_totals.as<double>(),
-                                S.r_valid.as<int32_t>(), r_chain, S.stream));
-    BXMI_HIP(hipMemcpyAsync(totals, S.r_totals.p, (size_t)width * sizeof(double), hipMemcpyDeviceToHost, S.stream));
-    BXMI_HIP(hipMemcpyAsync(valid, S.r_valid.p, (size_t)width * sizeof(int32_t), hipMemcpyDeviceToHost, S.stream));
-    if (chain_columns_or_null) BXMI_HIP(hipMemcpyAsync(chain_columns_or_null, r_chain, sizeof(int64_t), hipMemcpyDeviceToHost, S.stream));
-    BXMI_HIP(hipStreamSynchronize(S.stream));
+                                S.r_valid.as<int32_t>(), r_chain, stream));
+    BXMI_HIP(hipMemcpyAsync(totals, S.r_totals.p, (size_t)width * sizeof(double), hipMemcpyDeviceToHost, stream));
+    BXMI_HIP(hipMemcpyAsync(valid, S.r_valid.p, (size_t)width * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    if (chain_columns_or_null) BXMI_HIP(hipMemcpyAsync(chain_columns_or_null, r_chain, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    BXMI_HIP(hipStreamSynchronize(stream));
     return BXMI_OK;
 }

@@ -11,6 +11,7 @@
 
 #include "common.hpp"
 #include "summary.hpp"
+#include "track_batch.hpp"
 
 using namespace bxmi;
 
@@ -18,6 +19,7 @@ struct bxmi_spans {
     int64_t n = 0;
     int ordered = 1;
     DevBuf start, end, value;
+    SmTrack entry() const { return SmTrack{start.as<int32_t>(), end.as<int32_t>(), value.as<float>(), n, ordered}; }
 };
 
 extern "C" int bxmi_spans_create(const int32_t *start, const int32_t *end, const float *value, int64_t n, bxmi_spans_t **out)
@@ -72,33 +74,18 @@ extern "C" int bxmi_spans_info(const bxmi_spans_t *h, int64_t *n, int *ordered)
 namespace {
 constexpr int64_t SM_SLAB_CELLS = 1 << 23;  // the host form goes through the device in slabs of about this many (row, bin) cells
 
-struct SummaryScratch {
-    int device = -1;
+struct SummaryBufs {
     DevBuf table;                      // SmTrack[n_tracks + 1], the last one the spare entry
     DevBuf q_track, q_start, q_end;    // staging of the host form
     DevBuf r[5];
-    hipStream_t stream = nullptr;
-    void release()
-    {
-        for (DevBuf *b : {&table, &q_track, &q_start, &q_end, &r[0], &r[1], &r[2], &r[3], &r[4]}) b->release();
-        if (stream) (void)hipStreamDestroy(stream);
-        stream = nullptr;
-    }
 };
-// (never destroyed: at process exit the runtime may be gone before a static destructor could free device memory)
-SummaryScratch &g_summary = *new SummaryScratch();
-std::mutex g_summary_lock;
+LibraryScratch<SummaryBufs> &g_summary = LibraryScratch<SummaryBufs>::leaked();
 }  // namespace
 
 static int summary_check(const char *who, bxmi_spans_t *const *tracks, int32_t n_tracks, const void *track_of, const void *start, const void *end,
                          int64_t n, int32_t size, void *const *out)
 {
-    if (size < 1) return fail(BXMI_EINVAL, "%s: size = %d, must be at least 1", who, (int)size);
-    if (n < 0 || n > 2147483647LL) return fail(BXMI_EINVAL, "%s: n = %lld outside [0, 2^31-1]", who, (long long)n);
-    if (n_tracks < 0) return fail(BXMI_EINVAL, "%s: n_tracks = %d is negative", who, (int)n_tracks);
-    if (n_tracks > 0 && !tracks) return fail(BXMI_EINVAL, "%s: NULL track list", who);
-    for (int32_t t = 0; t < n_tracks; t++)
-        if (!tracks[t]) return fail(BXMI_EINVAL, "%s: track %d is a NULL handle", who, (int)t);
+    BXMI_TRY(track_batch_check(who, "size", size, tracks, n_tracks, n));
     if (n > 0) {
         if (!track_of || !start || !end) return fail(BXMI_EINVAL, "%s: NULL array", who);
         for (int k = 0; k < 5; k++)
@@ -107,39 +94,13 @@ static int summary_check(const char *who, bxmi_spans_t *const *tracks, int32_t n
     return BXMI_OK;
 }
 
-static int summary_scratch_for_device(SummaryScratch &S)
+// S.table for this call's tracks, 8 per launch; the spare entry has no items
+static int summary_fill_table(SummaryBufs &S, bxmi_spans_t *const *tracks, int32_t n_tracks, hipStream_t st)
 {
-    int dev = -1;
-    BXMI_HIP(hipGetDevice(&dev));
-    if (S.device != dev) {
-        S.release();
-        S.device = dev;
-    }
-    return BXMI_OK;
+    return fill_track_table<SmTrack, 8>(S.table, n_tracks, [&](int k) { return tracks[k]->entry(); }, SmTrack{nullptr, nullptr, nullptr, 0, 1}, st);
 }
 
-static int summary_table(SummaryScratch &S, bxmi_spans_t *const *tracks, int32_t n_tracks, hipStream_t st)
-{
-    BXMI_TRY(S.table.reserve((size_t)(n_tracks + 1) * sizeof(SmTrack)));
-    SmTrack *table = S.table.as<SmTrack>();
-    for (int32_t base = 0; base <= n_tracks; base += SM_TABLE_PACK) {
-        SmTrackPack pack{};
-        const int count = n_tracks + 1 - base < SM_TABLE_PACK ? n_tracks + 1 - base : SM_TABLE_PACK;
-        for (int k = 0; k < count; k++) {
-            if (base + k < n_tracks) {
-                const bxmi_spans *h = tracks[base + k];
-                pack.t[k] = SmTrack{h->start.as<int32_t>(), h->end.as<int32_t>(), h->value.as<float>(), h->n, h->ordered};
-            } else {
-                pack.t[k] = SmTrack{nullptr, nullptr, nullptr, 0, 1};
-            }
-        }
-        hipLaunchKernelGGL(sm_table_kernel, dim3(1), dim3(64), 0, st, table, (int)base, count, pack);
-        BXMI_LAUNCH_CHECK();
-    }
-    return BXMI_OK;
-}
-
-static int summary_launch(SummaryScratch &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, int64_t n,
+static int summary_launch(SummaryBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, int64_t n,
                           int32_t size, double *const *out, hipStream_t st)
 {
     constexpr int64_t ROWS_PER_LAUNCH = 1 << 25;  // (a grid's threads are counted in 32 bits: 2^25 workgroups of 64)
@@ -160,11 +121,10 @@ extern "C" int bxmi_spans_summarize_dev(bxmi_spans_t *const *tracks, int32_t n_t
     double *const out[5] = {valid, min, max, sum, sumsq};
     BXMI_TRY(summary_check(who, tracks, n_tracks, track_of, start, end, n, size, reinterpret_cast<void *const *>(out)));
     if (n == 0) return BXMI_OK;
-    std::lock_guard<std::mutex> hold(g_summary_lock);
-    SummaryScratch &S = g_summary;
-    BXMI_TRY(summary_scratch_for_device(S));
-    BXMI_TRY(summary_table(S, tracks, n_tracks, as_stream(stream)));
-    return summary_launch(S, n_tracks, track_of, start, end, n, size, out, as_stream(stream));
+    std::lock_guard<std::mutex> hold(g_summary.lock);
+    BXMI_TRY(g_summary.enter());
+    BXMI_TRY(summary_fill_table(g_summary.bufs, tracks, n_tracks, as_stream(stream)));
+    return summary_launch(g_summary.bufs, n_tracks, track_of, start, end, n, size, out, as_stream(stream));
 }
 
 extern "C" int bxmi_spans_summarize(bxmi_spans_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
@@ -173,17 +133,15 @@ extern "C" int bxmi_spans_summarize(bxmi_spans_t *const *tracks, int32_t n_track
     const char *who = "bxmi_spans_summarize";
     double *const out[5] = {valid, min, max, sum, sumsq};
     BXMI_TRY(summary_check(who, tracks, n_tracks, track_of, start, end, n, size, reinterpret_cast<void *const *>(out)));
-    for (int64_t i = 0; i < n; i++) {
-        if (track_of[i] >= n_tracks)
-            return fail(BXMI_EINVAL, "%s: track_of[%lld] = %d, but there are %d tracks", who, (long long)i, (int)track_of[i], (int)n_tracks);
+    BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    for (int64_t i = 0; i < n; i++)
         if (start[i] < 0 || end[i] < 0)
             return fail(BXMI_EINVAL, "%s: region %lld = [%d, %d) has a negative coordinate", who, (long long)i, (int)start[i], (int)end[i]);
-    }
     if (n == 0) return BXMI_OK;
-    std::lock_guard<std::mutex> hold(g_summary_lock);
-    SummaryScratch &S = g_summary;
-    BXMI_TRY(summary_scratch_for_device(S));
-    if (!S.stream) BXMI_HIP(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
+    std::lock_guard<std::mutex> hold(g_summary.lock);
+    BXMI_TRY(g_summary.enter(true));
+    SummaryBufs &S = g_summary.bufs;
+    const hipStream_t st = g_summary.stream;
     int64_t slab = SM_SLAB_CELLS / size;  // rows per slab
     if (slab < 1) slab = 1;
     if (slab > n) slab = n;
@@ -196,17 +154,17 @@ extern "C" int bxmi_spans_summarize(bxmi_spans_t *const *tracks, int32_t n_track
         BXMI_TRY(S.r[k].reserve(cells));
         dev_out[k] = S.r[k].as<double>();
     }
-    BXMI_TRY(summary_table(S, tracks, n_tracks, S.stream));
+    BXMI_TRY(summary_fill_table(S, tracks, n_tracks, st));
     for (int64_t first = 0; first < n; first += slab) {
         const int64_t m = n - first < slab ? n - first : slab;
         const size_t in_bytes = (size_t)m * sizeof(int32_t), out_bytes = (size_t)m * (size_t)size * sizeof(double);
-        BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of + first, in_bytes, hipMemcpyHostToDevice, S.stream));
-        BXMI_HIP(hipMemcpyAsync(S.q_start.p, start + first, in_bytes, hipMemcpyHostToDevice, S.stream));
-        BXMI_HIP(hipMemcpyAsync(S.q_end.p, end + first, in_bytes, hipMemcpyHostToDevice, S.stream));
-        BXMI_TRY(summary_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), S.q_end.as<int32_t>(), m, size, dev_out, S.stream));
+        BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of + first, in_bytes, hipMemcpyHostToDevice, st));
+        BXMI_HIP(hipMemcpyAsync(S.q_start.p, start + first, in_bytes, hipMemcpyHostToDevice, st));
+        BXMI_HIP(hipMemcpyAsync(S.q_end.p, end + first, in_bytes, hipMemcpyHostToDevice, st));
+        BXMI_TRY(summary_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), S.q_end.as<int32_t>(), m, size, dev_out, st));
         for (int k = 0; k < 5; k++)
-            BXMI_HIP(hipMemcpyAsync(out[k] + first * (int64_t)size, dev_out[k], out_bytes, hipMemcpyDeviceToHost, S.stream));
-        BXMI_HIP(hipStreamSynchronize(S.stream));  // the staging is reused by the next slab
+            BXMI_HIP(hipMemcpyAsync(out[k] + first * (int64_t)size, dev_out[k], out_bytes, hipMemcpyDeviceToHost, st));
+        BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
     }
     return BXMI_OK;
 }

@@ -16,6 +16,7 @@
 // x86-64 build rounds the product and the sum separately.  Float64 division on gfx950 is correctly rounded (its expansion uses
 // fused operations internally; that is the division's own algorithm, not a contraction of the chain).
 //
+//   track_table_kernel (track_batch.hpp, 8 tracks per launch) writes the table SmTrack[n_tracks + 1] that sm_summary_kernel reads.
 //   sm_summary_kernel  one wave (== one workgroup) per region.  Bins are taken 64 at a time, lane = bin; the lane keeps its bin's
 //                      five accumulators in registers across all chunks of items and writes them once, so the five [n, size]
 //                      planes are written coalesced along the bin axis.
@@ -35,7 +36,6 @@ namespace bxmi {
 
 constexpr int SM_CHUNK = 256;        // items staged in LDS at a time (3 KiB per workgroup)
 constexpr int SM_THREADS = 64;       // one wave per region
-constexpr int SM_TABLE_PACK = 8;     // tracks per launch of sm_table_kernel
 
 struct SmTrack {
     const int32_t *start;
@@ -44,18 +44,6 @@ struct SmTrack {
     int64_t n;
     int64_t ordered;
 };
-struct SmTrackPack {
-    SmTrack t[SM_TABLE_PACK];
-};
-
-// table[base .. base + count) = pack (the table travels in kernel arguments: stream-ordered, no host buffer to keep alive)
-__global__ __launch_bounds__(64) void sm_table_kernel(SmTrack *__restrict__ table, int base, int count, SmTrackPack pack)
-{
-    if (threadIdx.x != 0) return;
-#pragma unroll
-    for (int k = 0; k < SM_TABLE_PACK; k++)
-        if (k < count) table[base + k] = pack.t[k];
-}
 
 struct SmAcc {
     double valid, mn, mx, sum, sumsq;

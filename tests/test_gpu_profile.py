@@ -345,6 +345,90 @@ def test_bad_arguments_are_einval():
     t.close()
 
 
+# ------------------------------------------------------------ the track table --
+TABLE_TRACKS = (0, 1, 15, 16, 17, 33)  # around the 16 tracks one launch of the table kernel carries; 16 itself: the spare entry alone in a launch
+_table = {}
+
+
+def table_case(n_tracks):
+    """(tracks: track k is 8 floats of value k + 1; one window per track at 2 and two rows without a track; the device form's rows:
+    one more, naming the track behind the last; the model's answer, the same for both), once per n_tracks"""
+    if n_tracks not in _table:
+        arrays = [np.full(8, k + 1, dtype=np.float32) for k in range(n_tracks)]
+        track_of = np.array(list(range(n_tracks)) + [-1, -1], dtype=np.int32)
+        starts = np.full(len(track_of) + 1, 2, dtype=np.int32)
+        want = M.profile(arrays, np.append(track_of, -1), starts, 4)
+        assert list(want[0]) == [n_tracks * (n_tracks + 1) / 2.0] * 4 and list(want[1]) == [n_tracks] * 4
+        _table[n_tracks] = (arrays, track_of, starts[:-1], np.append(track_of, n_tracks).astype(np.int32), starts, want)
+    return _table[n_tracks]
+
+
+def profile_dev_raw(tracks, track_of, starts, width):
+    """bxmi_scores_profile_dev on arrays in device memory, on the null stream -> (totals, valid) as numpy arrays"""
+    ffi = _ffi()
+    bufs = [ffi.DeviceArray.from_numpy(track_of), ffi.DeviceArray.from_numpy(starts), ffi.DeviceArray(8 * width), ffi.DeviceArray(4 * width)]
+    ffi.call("bxmi_scores_profile_dev", ffi.handles(tracks), len(tracks), bufs[0].ptr, bufs[1].ptr, len(track_of), width, bufs[2].ptr,
+             bufs[3].ptr, None, None)
+    ffi.call("bxmi_synchronize", None)
+    out = bufs[2].to_numpy(np.float64, width), bufs[3].to_numpy(np.int32, width)
+    for b in bufs:
+        b.free()
+    return out
+
+
+@pytest.mark.parametrize("n_tracks", TABLE_TRACKS)
+def test_track_table_beyond_one_launch(n_tracks):
+    """every track's entry and the spare entry behind them arrive, however many launches the table takes: host form and device form"""
+    from bxmi import scores
+
+    arrays, track_of, starts, dev_track_of, dev_starts, want = table_case(n_tracks)
+    dev = device_tracks(arrays)
+    assert_same(scores.profile(dev, track_of, starts, 4), want, ("host", n_tracks))
+    assert_same(profile_dev_raw(dev, dev_track_of, dev_starts, 4), want, ("device", n_tracks))
+    for t in dev:
+        t.close()
+
+
+def test_track_table_is_reused_by_a_call_with_fewer_tracks():
+    """17 tracks, then 1 track on the same stream: the spare entry now sits where track 1's entry was, so a row naming track 5 has no
+    score (not track 5's of the call before); then the 17 again"""
+    arrays, _, _, dev_track_of, dev_starts, want = table_case(17)
+    dev = device_tracks(arrays)
+    assert_same(profile_dev_raw(dev, dev_track_of, dev_starts, 4), want, "17 tracks")
+    one = M.profile(arrays[:1], np.array([0, -1], dtype=np.int32), dev_starts[:2], 4)
+    assert list(one[0]) == [1.0] * 4 and list(one[1]) == [1] * 4
+    assert_same(profile_dev_raw(dev[:1], np.array([0, 5], dtype=np.int32), dev_starts[:2], 4), one, "1 track after 17")
+    assert_same(profile_dev_raw(dev, dev_track_of, dev_starts, 4), want, "17 tracks again")
+    for t in dev:
+        t.close()
+
+
+def test_library_scratch_follows_the_device():
+    """one profile and one summary call on device 0, on device 1, on device 0 again, tracks made on the device that uses them: the
+    library's scratch (buffers and stream) is dropped and made again at each change.  One pass."""
+    import summary_model as SM
+    from bxmi import scores, summary
+
+    ffi = _ffi()
+    if ffi.device_count() < 2:
+        pytest.skip("one device visible: the scratch never changes device")
+    arrays, track_of, starts, _, _, want = table_case(17)
+    spans = [(np.array([0, 4], dtype=np.int32), np.array([4, 8], dtype=np.int32), np.array([k + 1, 2 * k + 3], dtype=np.float32)) for k in range(9)]
+    s_track_of, s_starts, s_ends = np.array(list(range(9)) + [-1], dtype=np.int32), np.zeros(10, dtype=np.int32), np.full(10, 8, dtype=np.int32)
+    s_want = SM.summarize(spans, s_track_of, s_starts, s_ends, 2)
+    try:
+        for device in (0, 1, 0):
+            ffi.call("bxmi_set_device", device)
+            dev, sdev = device_tracks(arrays), [summary.SpanTrack(*t) for t in spans]
+            assert_same(scores.profile(dev, track_of, starts, 4), want, ("profile on device", device))
+            got = summary.summarize(sdev, s_track_of, s_starts, s_ends, 2)
+            assert all(SM.same_bits(g, w) for g, w in zip(got, s_want)), ("summary on device", device)
+            for t in dev + sdev:
+                t.close()
+    finally:
+        ffi.call("bxmi_set_device", 0)
+
+
 # ------------------------------------------------------------ the command line --
 def run_cli(score_file, padding, bed):
     from bxmi.cli import bed_bigwig_profile

@@ -185,6 +185,72 @@ def test_no_regions_and_bad_arguments():
     t.close()
 
 
+# ------------------------------------------------------------ the track table --
+TABLE_TRACKS = (0, 1, 7, 8, 9, 17)  # around the 8 tracks one launch of the table kernel carries; 8 itself: the spare entry alone in a launch
+_table = {}
+
+
+def table_case(n_tracks):
+    """(tracks: track k holds (0, 4, k + 1) and (4, 8, 2 k + 3); one region [0, 8) per track and one row without a track; the device
+    form's track_of: one more row, naming the track behind the last; the model's answer for the device form's rows), once per n_tracks"""
+    if n_tracks not in _table:
+        tracks = [(np.array([0, 4], dtype=np.int32), np.array([4, 8], dtype=np.int32), np.array([k + 1, 2 * k + 3], dtype=np.float32))
+                  for k in range(n_tracks)]
+        track_of = np.array(list(range(n_tracks)) + [-1], dtype=np.int32)
+        starts, ends = np.zeros(len(track_of) + 1, dtype=np.int32), np.full(len(track_of) + 1, 8, dtype=np.int32)
+        want = M.summarize(tracks, np.append(track_of, -1), starts, ends, 2)
+        _table[n_tracks] = (tracks, track_of, np.append(track_of, n_tracks).astype(np.int32), starts, ends, want)
+    return _table[n_tracks]
+
+
+def summarize_dev_raw(tracks, track_of, starts, ends, size):
+    """bxmi_spans_summarize_dev on arrays in device memory, on the null stream -> five [n, size] numpy arrays"""
+    from bxmi import _ffi as ffi
+
+    n = len(track_of)
+    rows = [ffi.DeviceArray.from_numpy(a) for a in (track_of, starts, ends)]
+    planes = [ffi.DeviceArray(8 * n * size) for _ in range(5)]
+    ffi.call("bxmi_spans_summarize_dev", ffi.handles(tracks), len(tracks), *[a.ptr for a in rows], n, size, *[a.ptr for a in planes], None)
+    ffi.call("bxmi_synchronize", None)
+    out = [a.to_numpy(np.float64, n * size).reshape(n, size) for a in planes]
+    for a in rows + planes:
+        a.free()
+    return out
+
+
+@pytest.mark.parametrize("n_tracks", TABLE_TRACKS)
+def test_track_table_beyond_one_launch(n_tracks):
+    """every track's entry and the spare entry behind them arrive, however many launches the table takes: host form (without the row
+    the host form refuses) and device form, whose row naming the track behind the last is an empty row"""
+    from bxmi import summary
+
+    tracks, track_of, dev_track_of, starts, ends, want = table_case(n_tracks)
+    dev = [summary.SpanTrack(*t) for t in tracks]
+    assert_planes(summary.summarize(dev, track_of, starts[:-1], ends[:-1], 2), [p[:-1] for p in want], ("host", n_tracks))
+    got = summarize_dev_raw(dev, dev_track_of, starts, ends, 2)
+    assert_planes(got, want, ("device", n_tracks))
+    assert_planes([p[-1:] for p in got], empty_planes(2)[:, None, :], ("the row behind the last track", n_tracks))
+    for k in range(n_tracks):
+        assert [p[k].tolist() for p in got[:3]] == [[4.0, 4.0], [k + 1.0, 2 * k + 3.0], [k + 1.0, 2 * k + 3.0]]
+    for t in dev:
+        t.close()
+
+
+def test_track_table_is_reused_by_a_call_with_fewer_tracks():
+    """17 tracks, then 1 track on the same stream: the spare entry now sits where track 1's entry was, so a row naming track 5 is an
+    empty row (not track 5's of the call before); then the 17 again"""
+    from bxmi import summary
+
+    tracks, _, dev_track_of, starts, ends, want = table_case(17)
+    dev = [summary.SpanTrack(*t) for t in tracks]
+    assert_planes(summarize_dev_raw(dev, dev_track_of, starts, ends, 2), want, "17 tracks")
+    one = M.summarize(tracks[:1], np.array([0, -1], dtype=np.int32), starts[:2], ends[:2], 2)
+    assert_planes(summarize_dev_raw(dev[:1], np.array([0, 5], dtype=np.int32), starts[:2], ends[:2], 2), one, "1 track after 17")
+    assert_planes(summarize_dev_raw(dev, dev_track_of, starts, ends, 2), want, "17 tracks again")
+    for t in dev:
+        t.close()
+
+
 # ------------------------------------------------------------ device entry point --
 def test_summarize_dev_equals_summarize_and_the_recorded_arrays():
     """summarize_dev on torch tensors -- every recorded case, a seeded batch on slices that start 4 bytes into their allocation,
