@@ -4,8 +4,11 @@ MI355X (bxmi.summary).
 
 ``summarize_from_full`` is the reference's bit for bit.  ``summarize`` and ``query`` are served from full data exactly when the
 reference's own rule picks no zoom level (bbi_file.pyx:205-215, 281-294: ``((end - start) // size) // 2`` is at most 1, or no
-level's ``reduction_level`` is at most that value); otherwise they raise NotImplementedError -- zoom-level answers are float32
-arithmetic over on-disk summaries, which this module does not read -- and ``summarize_from_full`` is the call to make.
+level's ``reduction_level`` is at most that value); otherwise, BY DEFAULT, they raise NotImplementedError and
+``summarize_from_full`` is the call to make.  ``BigWigFile(file, use_zoom=True)`` answers those regions as the reference does, from
+the zoom level its rule picks (bbi_file.pyx:296-432; bxmi.summary.ZoomTrack), bit for bit; only a level whose records are not in
+order still raises the same NotImplementedError.  The default is kept for compatibility with tests that pin the earlier
+behaviour and is meant to flip later.
 ``get`` and ``get_as_array`` are host code over the file's spans.  The file is read once, when the object is made; its items go
 to the device on the first summary.  `chrom` may be str or bytes everywhere.
 """
@@ -34,8 +37,10 @@ def _bits32(value):
 class BigWigFile:
     """A "big binary indexed" file whose raw data is in wiggle format.  `file`: a file object opened in binary mode."""
 
-    def __init__(self, file=None):
+    def __init__(self, file=None, use_zoom=False):
         self._tracks = None
+        self._zoom_tracks = {}
+        self.use_zoom = bool(use_zoom)
         if file is not None:
             self.open(file)
 
@@ -50,12 +55,14 @@ class BigWigFile:
         self._spans = bigwig.read_spans_file(data=data)
         self._reductions = bigwig.zoom_reductions(data=data)
         self.zoom_levels = len(self._reductions)
+        self._levels = bigwig.read_zoom_file(data=data) if self.use_zoom else None
 
     def close(self):
         """Free the device copies of the items (they are made again on the next summary)."""
-        for t in (self._tracks or {}).values():
+        for t in list((self._tracks or {}).values()) + list(self._zoom_tracks.values()):
             t.close()
         self._tracks = None
+        self._zoom_tracks = {}
 
     @staticmethod
     def _name(chrom):
@@ -90,15 +97,32 @@ class BigWigFile:
 
     def summarize(self, chrom, start, end, summary_size):
         """`summary_size` data points over `chrom`:`start`-`end`: from full data where the reference would take them from
-        there, NotImplementedError where it would take a zoom level."""
+        there; where it would take a zoom level, from that level with `use_zoom`, else NotImplementedError."""
         start, end, summary_size = _bits32(start), _bits32(end), int(summary_size)
         chrom = self._name(chrom)
         if start >= end or chrom not in self._sizes:
             return None
         if self._picks_zoom(start, end, summary_size):
-            raise NotImplementedError("the reference answers this region from a zoom level, which is not implemented: "
-                                      "call summarize_from_full for the answer from full data")
+            if not self.use_zoom:
+                raise NotImplementedError("the reference answers this region from a zoom level, which is not implemented: "
+                                          "call summarize_from_full for the answer from full data")
+            return self._summarize_from_zoom(chrom, start, end, summary_size)
         return self.summarize_from_full(chrom, start, end, summary_size)
+
+    def _summarize_from_zoom(self, chrom, start, end, summary_size):
+        from bxmi.summary import NOT_ORDERED, ZoomTrack, pick_level, summarize_zoom
+
+        if end > 2147483647:
+            raise ValueError("regions beyond 2^31 - 1 are not supported")
+        level = pick_level(self._reductions, start, end, summary_size)
+        if (chrom, level) not in self._zoom_tracks:
+            arrays = self._levels[level][1][chrom]
+            why = bigwig.ordered_level(arrays)
+            if why:
+                raise NotImplementedError(NOT_ORDERED % why)
+            self._zoom_tracks[chrom, level] = ZoomTrack(arrays)
+        res = summarize_zoom([self._zoom_tracks[chrom, level]], [0], [start], [end], summary_size)
+        return SummarizedData(start, end, summary_size, [plane[0] for plane in res])
 
     def query(self, chrom, start, end, summary_size):
         """A list of `summary_size` dicts with the keys mean, max, min, coverage, std_dev (bbi_file.pyx:231-260)."""

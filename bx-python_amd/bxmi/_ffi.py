@@ -87,6 +87,11 @@ _SIGNATURES = {
     "bxmi_spans_info": [vp, _p(i64), _p(C.c_int)],
     "bxmi_spans_summarize": [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp],
     "bxmi_spans_summarize_dev": [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp],
+    "bxmi_zoom_create": [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, _p(vp)],
+    "bxmi_zoom_destroy": [vp],
+    "bxmi_zoom_info": [vp, _p(i64), _p(i64)],
+    "bxmi_zoom_summarize": [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp],
+    "bxmi_zoom_summarize_dev": [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp],
     "bxmi_bits_create": [i64, i64, _p(vp)],
     "bxmi_bits_destroy": [vp],
     "bxmi_bits_info": [vp, _p(i32), _p(i32), _p(i32)],

@@ -6,8 +6,15 @@ one device pass -- and the engine under ``bx.bbi.bigwig_file`` and ``bxmi.cli.bi
 ``SpanTrack`` is one chromosome's bigWig items (start, end, value) resident in HBM in file order (``bxmi_spans_*`` of
 include/bxmi.h).  ``summarize`` answers from host arrays, ``summarize_dev`` from device arrays; both give the reference's five
 arrays per region bit for bit: every bin is its ordered float64 chain over the items that overlap it, products and sums rounded
-separately.  ``stats`` derives mean, coverage and standard deviation as ``query`` does.  Zoom levels are not used: these are the
-answers from full data.
+separately.  ``stats`` derives mean, coverage and standard deviation as ``query`` does.  These are the answers from full data.
+
+``ZoomTrack`` is one chromosome's part of one zoom level (``bxmi_zoom_*``; bbi_file.pyx:296-432): ``summarize_zoom`` and
+``summarize_zoom_dev`` answer a batch from such tracks as the reference's ``ZoomLevel._summarize`` does, bit for bit -- float32
+accumulators fed by float64 products and sums.  ``pick_level`` is the reference's choice of a level, and ``TrackSet`` is a whole
+file on the device: its ``summarize`` answers a mixed batch as ``BigWigFile.summarize`` would, each row from the level the rule
+picks for it or from full data, in two device calls.  The drop-in ``bx.bbi.bigwig_file.BigWigFile`` and
+``bxmi.cli.bigwig_summary`` use zoom levels only when asked (``use_zoom=True``, ``-z``): their default is kept for compatibility
+with tests that pin the earlier behaviour, and is meant to flip later.
 """
 import collections
 import ctypes as C
@@ -120,3 +127,167 @@ def stats(summary, starts, ends, size):
     variance = torch.where(valid > 1, variance / (valid - 1), variance)
     std_dev = torch.sqrt(torch.where(variance < 0, torch.zeros_like(variance), variance))
     return mean, coverage, std_dev
+
+
+class ZoomTrack:
+    """One chromosome's part of one zoom level on the device: `arrays` is a bxmi.bigwig.ZoomArrays (records in load order and the
+    leaf entries that decide what a region loads).  Only an ORDERED level is accepted (bxmi.bigwig.ordered_level): anything else
+    raises BxmiError (EINVAL) naming the condition."""
+
+    def __init__(self, arrays):
+        _ffi.require_gpu()
+        a = arrays
+        rec = [as_i32(a.start), as_i32(a.end), np.ascontiguousarray(a.valid, dtype=np.uint32)]
+        rec += [np.ascontiguousarray(x, dtype=np.float32) for x in (a.min, a.max, a.sum, a.sumsq)]
+        leaf = [as_i32(a.leaf_lo), as_i32(a.leaf_hi)]
+        first = np.ascontiguousarray(a.leaf_first, dtype=np.int64)
+        if any(x.ndim != 1 or x.shape != rec[0].shape for x in rec) or leaf[0].shape != leaf[1].shape or first.shape != (len(leaf[0]) + 1,):
+            raise ValueError("seven record arrays of one length, leaf_lo and leaf_hi of one length, leaf_first one longer")
+        h = C.c_void_p()
+        call("bxmi_zoom_create", *[ptr(x) for x in rec], len(rec[0]), ptr(leaf[0]), ptr(leaf[1]), ptr(first), len(leaf[0]), C.byref(h))
+        self._h = h
+        n, n_leaves = C.c_int64(0), C.c_int64(0)
+        call("bxmi_zoom_info", self._h, C.byref(n), C.byref(n_leaves))
+        self.n, self.n_leaves = n.value, n_leaves.value
+
+    @classmethod
+    def from_bigwig(cls, path):
+        """{chrom: [ZoomTrack per level, in file order]} of a bigWig file; every level must be ordered."""
+        levels = bigwig.read_zoom_file(path)
+        return {chrom: [cls(per[chrom]) for _, per in levels] for chrom in (levels[0][1] if levels else bigwig.chroms(path))}
+
+    def close(self):
+        if self._h is not None:
+            _ffi.load().bxmi_zoom_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def summarize_zoom(tracks, track_of, starts, ends, size):
+    """ZoomLevel._summarize of regions [starts[i], ends[i]) from the ZoomTrack tracks[track_of[i]], `size` bins each -> Summary of
+    [n, size] float64 numpy arrays; valid_count is not a whole number here.  A bin without a record left is 0, NaN, NaN, 0, 0.
+    track_of[i] < 0 or starts[i] >= ends[i] -- where the reference returns None -- gives the empty row of `summarize`: 0, +inf,
+    -inf, 0, 0.  A negative coordinate or size < 1 raises BxmiError (EINVAL)."""
+    _ffi.require_gpu()
+    tracks = list(tracks)
+    t, s, e = as_i32(track_of), as_i32(starts), as_i32(ends)
+    if not (t.shape == s.shape == e.shape) or t.ndim != 1:
+        raise ValueError("track_of, starts and ends must be 1-d arrays of equal length")
+    size = int(size)
+    out = [np.empty((len(t), max(size, 0)), dtype=np.float64) for _ in range(5)]
+    call("bxmi_zoom_summarize", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), ptr(e), len(t), size, *[ptr(a) for a in out])
+    return Summary(*out)
+
+
+def summarize_zoom_dev(tracks, track_of, starts, ends, size, stream=None):
+    """`summarize_zoom` on device arrays, as `summarize_dev`: int32 torch tensors on the GPU in, float64 tensors out, queued on
+    torch's current stream (or `stream`).  It shares the library's track table with `summarize_dev`: one summary call of either kind
+    at a time per process may be in flight."""
+    import torch
+
+    tracks = list(tracks)
+    (track_of, starts, ends), n, dev, stream = _ffi.device_args("summarize_zoom_dev", "summarize_zoom", ("track_of", "starts", "ends"),
+                                                                (track_of, starts, ends), stream)
+    size = int(size)
+    out = [torch.empty((n, max(size, 0)), dtype=torch.float64, device=dev) for _ in range(5)]
+    call("bxmi_zoom_summarize_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), ends.data_ptr(), n, size,
+         *[a.data_ptr() for a in out], stream)
+    return Summary(*out)
+
+
+def pick_levels(reductions, starts, ends, size):
+    """The zoom level BBIFile.summarize takes for `size` bins over each [starts[i], ends[i]) (bbi_file.pyx:205-215, 281-294): int32
+    [n] of indices into `reductions` (the levels' reduction_level in file order, sorted or not), -1 for full data.  desired =
+    ((end - start) // size) // 2; no level when desired <= 1; else the level with the smallest desired - reduction >= 0, the
+    first in file order among equals."""
+    desired = ((np.asarray(ends, dtype=np.int64) - np.asarray(starts, dtype=np.int64)) // int(size)) // 2
+    level, best = np.full(len(desired), -1, dtype=np.int32), np.full(len(desired), np.iinfo(np.int64).max)
+    for k, r in enumerate(reductions):
+        diff = desired - int(r)
+        take = (desired > 1) & (diff >= 0) & (diff < best)
+        level[take], best[take] = k, diff[take]
+    return level
+
+
+def pick_level(reductions, start, end, size):
+    """`pick_levels` for one region: an index into `reductions`, or None for full data."""
+    k = int(pick_levels(reductions, [start], [end], size)[0])
+    return None if k < 0 else k
+
+
+NOT_ORDERED = ("the reference answers this region from a zoom level that is not ordered (%s), which is not implemented: "
+               "call summarize_from_full for the answer from full data")
+
+
+class TrackSet:
+    """A whole bigWig file on the device: every chromosome's items (SpanTrack) and its part of every zoom level (ZoomTrack; None in
+    place of a part that is not ordered).  `summarize` answers a batch as the reference's BigWigFile.summarize would, row by row."""
+
+    def __init__(self, spans, levels):
+        """spans: bigwig.read_spans_file's result; levels: bigwig.read_zoom_file's"""
+        self.chroms = list(spans)
+        self.reductions = [r for r, _ in levels]
+        self.spans = {chrom: SpanTrack(*spans[chrom]) for chrom in self.chroms}
+        self.not_ordered = {}
+        self.zoom = []  # one track per (chromosome, level), chromosome-major: track_of = chromosome * levels + level
+        for chrom in self.chroms:
+            for k, (_, per) in enumerate(levels):
+                why = bigwig.ordered_level(per[chrom])
+                if why:
+                    self.not_ordered[len(self.zoom)] = why
+                self.zoom.append(None if why else ZoomTrack(per[chrom]))
+
+    @classmethod
+    def from_bigwig(cls, path=None, data=None):
+        return cls(bigwig.read_spans_file(path, data=data), bigwig.read_zoom_file(path, data=data))
+
+    def close(self):
+        _ffi.close_all(list(self.spans.values()) + [t for t in self.zoom if t is not None])
+
+    def summarize(self, chroms, starts, ends, size, zoom=True):
+        """BigWigFile.summarize for a batch: `size` bins over chroms[i]:starts[i]-ends[i] -> Summary of [n, size] float64 arrays.
+        `chroms`: names, or an int array of positions in self.chroms (-1: unknown).  With `zoom`, a row for which the reference's
+        rule picks a level is answered from that level and the others from full data: ONE call of each kind, the zoom call's table
+        listing every (chromosome, level) track.  Without it every row comes from full data.  An unknown chromosome or start >= end
+        gives the empty row 0, +inf, -inf, 0, 0.  A row that needs a level which is not ordered raises NotImplementedError."""
+        chroms = np.asarray(chroms)
+        if chroms.dtype.kind in "iu":
+            track_of = as_i32(chroms)
+        else:
+            index = {chrom: k for k, chrom in enumerate(self.chroms)}
+            track_of = np.array([index.get(c, -1) for c in chroms.tolist()], dtype=np.int32)
+        s, e = as_i32(starts), as_i32(ends)
+        if not (track_of.shape == s.shape == e.shape) or s.ndim != 1:
+            raise ValueError("chroms, starts and ends must be 1-d arrays of equal length")
+        if len(track_of) and track_of.max() >= len(self.chroms):
+            raise ValueError("a chromosome position beyond the file's %d chromosomes" % len(self.chroms))
+        size = int(size)
+        if size < 1 or not zoom or not self.reductions:
+            return summarize(self.spans.values(), track_of, s, e, size)
+        level = pick_levels(self.reductions, s, e, size)
+        from_zoom = (level >= 0) & (track_of >= 0)  # (a row without a chromosome is the reference's None: the full call's empty row)
+        if not from_zoom.any():
+            return summarize(self.spans.values(), track_of, s, e, size)
+        rows = np.nonzero(from_zoom)[0]
+        zoom_track = track_of[rows] * len(self.reductions) + level[rows]
+        for t in np.unique(zoom_track):
+            if int(t) in self.not_ordered:
+                raise NotImplementedError(NOT_ORDERED % self.not_ordered[int(t)])
+        # (a handle array has no holes: the tracks that exist, renumbered)
+        kept = [k for k, t in enumerate(self.zoom) if t is not None]
+        renumber = np.full(len(self.zoom), -1, dtype=np.int32)
+        renumber[kept] = np.arange(len(kept), dtype=np.int32)
+        part = summarize_zoom([self.zoom[k] for k in kept], renumber[zoom_track], s[rows], e[rows], size)
+        if from_zoom.all():
+            return part
+        rest = np.nonzero(~from_zoom)[0]
+        full = summarize(self.spans.values(), track_of[rest], s[rest], e[rest], size)
+        out = [np.empty((len(s), size), dtype=np.float64) for _ in range(5)]
+        for o, a, b in zip(out, part, full):
+            o[rows], o[rest] = a, b
+        return Summary(*out)

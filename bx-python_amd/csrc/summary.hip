@@ -1,5 +1,6 @@
 // summary.hip -- span tracks (bxmi_spans_*): one chromosome's bigWig items in HBM, in file order, and their binned summaries over
-// batches of regions (kernels and semantics: summary.hpp).
+// batches of regions (kernels and semantics: summary.hpp); zoom tracks (bxmi_zoom_*): one chromosome's part of one zoom level and
+// the same summaries answered from its records (zoom_summary.hpp).
 //
 // No floating-point contraction anywhere in this unit: the chains of summary.hpp round every product and every sum separately,
 // as the reference's x86-64 build does (hipcc's default would fuse them into multiply-adds).  The pragma, not __dmul_rn /
@@ -12,6 +13,7 @@
 #include "common.hpp"
 #include "summary.hpp"
 #include "track_batch.hpp"
+#include "zoom_summary.hpp"
 
 using namespace bxmi;
 
@@ -69,20 +71,103 @@ extern "C" int bxmi_spans_info(const bxmi_spans_t *h, int64_t *n, int *ordered)
     return BXMI_OK;
 }
 
+// One chromosome's part of one zoom level (zoom_summary.hpp): seven record arrays and three leaf arrays.
+struct bxmi_zoom {
+    int64_t n = 0, n_leaves = 0;
+    DevBuf start, end, valid, mn, mx, sum, sumsq, leaf_lo, leaf_hi, leaf_first;
+    ZmTrack entry() const
+    {
+        return ZmTrack{start.as<int32_t>(), end.as<int32_t>(), valid.as<uint32_t>(), mn.as<float>(), mx.as<float>(), sum.as<float>(), sumsq.as<float>(),
+                       leaf_lo.as<int32_t>(), leaf_hi.as<int32_t>(), leaf_first.as<int64_t>(), n, n_leaves};
+    }
+};
+
+extern "C" int bxmi_zoom_create(const int32_t *start, const int32_t *end, const uint32_t *valid, const float *min, const float *max, const float *sum,
+                                const float *sumsq, int64_t n, const int32_t *leaf_lo, const int32_t *leaf_hi, const int64_t *leaf_first,
+                                int64_t n_leaves, bxmi_zoom_t **out)
+{
+    const char *who = "bxmi_zoom_create";
+    if (!out) return fail(BXMI_EINVAL, "%s: out is NULL", who);
+    *out = nullptr;
+    if (n < 0 || n_leaves < 0 || !leaf_first || (n > 0 && (!start || !end || !valid || !min || !max || !sum || !sumsq)) ||
+        (n_leaves > 0 && (!leaf_lo || !leaf_hi)))
+        return fail(BXMI_EINVAL, "%s: bad arguments", who);
+    // an ORDERED level, and leaves that partition the records: what the kernel's searches and its indexes rest on
+    for (int64_t i = 0; i < n; i++) {
+        if (start[i] < 0 || end[i] < 0)
+            return fail(BXMI_EINVAL, "%s: record %lld = [%d, %d) has a negative coordinate", who, (long long)i, (int)start[i], (int)end[i]);
+        if (start[i] > end[i]) return fail(BXMI_EINVAL, "%s: record %lld = [%d, %d) has start > end", who, (long long)i, (int)start[i], (int)end[i]);
+        if (i > 0 && start[i] < start[i - 1])
+            return fail(BXMI_EINVAL, "%s: record starts are not non-decreasing (record %lld: %d after %d)", who, (long long)i, (int)start[i], (int)start[i - 1]);
+        if (i > 0 && end[i] < end[i - 1])
+            return fail(BXMI_EINVAL, "%s: record ends are not non-decreasing (record %lld: %d after %d)", who, (long long)i, (int)end[i], (int)end[i - 1]);
+    }
+    if (leaf_first[0] != 0 || leaf_first[n_leaves] != n)
+        return fail(BXMI_EINVAL, "%s: leaf_first runs from %lld to %lld, not from 0 to n = %lld", who, (long long)leaf_first[0], (long long)leaf_first[n_leaves],
+                    (long long)n);
+    for (int64_t k = 0; k < n_leaves; k++) {
+        if (leaf_first[k + 1] < leaf_first[k]) return fail(BXMI_EINVAL, "%s: leaf_first is not non-decreasing at leaf %lld", who, (long long)k);
+        if (leaf_lo[k] < -1 || leaf_hi[k] < 0)
+            return fail(BXMI_EINVAL, "%s: leaf %lld = (%d, %d) has a negative coordinate", who, (long long)k, (int)leaf_lo[k], (int)leaf_hi[k]);
+        if (k > 0 && leaf_lo[k] < leaf_lo[k - 1])
+            return fail(BXMI_EINVAL, "%s: leaf_lo is not non-decreasing (leaf %lld: %d after %d)", who, (long long)k, (int)leaf_lo[k], (int)leaf_lo[k - 1]);
+        if (k > 0 && leaf_hi[k] < leaf_hi[k - 1])
+            return fail(BXMI_EINVAL, "%s: leaf_hi is not non-decreasing (leaf %lld: %d after %d)", who, (long long)k, (int)leaf_hi[k], (int)leaf_hi[k - 1]);
+    }
+    bxmi_zoom *h = new (std::nothrow) bxmi_zoom();
+    if (!h) return fail(BXMI_ENOMEM, "%s: host allocation failed", who);
+    h->n = n;
+    h->n_leaves = n_leaves;
+    struct Copy { DevBuf *to; const void *from; size_t bytes; };
+    const size_t rec = (size_t)n * 4, leaf = (size_t)n_leaves * 4;
+    const Copy copies[] = {{&h->start, start, rec}, {&h->end, end, rec}, {&h->valid, valid, rec}, {&h->mn, min, rec}, {&h->mx, max, rec},
+                           {&h->sum, sum, rec}, {&h->sumsq, sumsq, rec}, {&h->leaf_lo, leaf_lo, leaf}, {&h->leaf_hi, leaf_hi, leaf},
+                           {&h->leaf_first, leaf_first, (size_t)(n_leaves + 1) * 8}};
+    int rc = BXMI_OK;
+    for (const Copy &c : copies) {
+        if (rc == BXMI_OK) rc = c.to->reserve(c.bytes ? c.bytes : 8);
+        if (rc == BXMI_OK && c.bytes > 0) {
+            const hipError_t e = hipMemcpy(c.to->p, c.from, c.bytes, hipMemcpyHostToDevice);
+            if (e != hipSuccess) rc = fail(BXMI_EHIP, "%s: %s", who, hipGetErrorString(e));
+        }
+    }
+    if (rc != BXMI_OK) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_zoom_destroy(bxmi_zoom_t *h)
+{
+    delete h;
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_zoom_info(const bxmi_zoom_t *h, int64_t *n, int64_t *n_leaves)
+{
+    if (!h) return fail(BXMI_EINVAL, "bxmi_zoom_info: NULL handle");
+    if (n) *n = h->n;
+    if (n_leaves) *n_leaves = h->n_leaves;
+    return BXMI_OK;
+}
+
 // The track table and the staging of the host form belong to the library, not to a track (a call may name no track at all): one
 // summary call at a time per process may be in flight.
 namespace {
 constexpr int64_t SM_SLAB_CELLS = 1 << 23;  // the host form goes through the device in slabs of about this many (row, bin) cells
 
 struct SummaryBufs {
-    DevBuf table;                      // SmTrack[n_tracks + 1], the last one the spare entry
+    DevBuf table;                      // SmTrack or ZmTrack [n_tracks + 1] (the call's kind), the last one the spare entry
     DevBuf q_track, q_start, q_end;    // staging of the host form
     DevBuf r[5];
 };
 LibraryScratch<SummaryBufs> &g_summary = LibraryScratch<SummaryBufs>::leaked();
 }  // namespace
 
-static int summary_check(const char *who, bxmi_spans_t *const *tracks, int32_t n_tracks, const void *track_of, const void *start, const void *end,
+template <typename Handle>
+static int summary_check(const char *who, Handle *const *tracks, int32_t n_tracks, const void *track_of, const void *start, const void *end,
                          int64_t n, int32_t size, void *const *out)
 {
     BXMI_TRY(track_batch_check(who, "size", size, tracks, n_tracks, n));
@@ -100,38 +185,57 @@ static int summary_fill_table(SummaryBufs &S, bxmi_spans_t *const *tracks, int32
     return fill_track_table<SmTrack, 8>(S.table, n_tracks, [&](int k) { return tracks[k]->entry(); }, SmTrack{nullptr, nullptr, nullptr, 0, 1}, st);
 }
 
+static int summary_fill_table(SummaryBufs &S, bxmi_zoom_t *const *tracks, int32_t n_tracks, hipStream_t st)
+{
+    return fill_track_table<ZmTrack, 8>(S.table, n_tracks, [&](int k) { return tracks[k]->entry(); }, ZmTrack{}, st);
+}
+
+static void launch_rows(const SmTrack *table, int64_t m, int n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, int size,
+                        double *const *out, int64_t cell, hipStream_t st)
+{
+    hipLaunchKernelGGL(sm_summary_kernel, dim3((unsigned)m), dim3(SM_THREADS), 0, st, table, n_tracks, track_of, start, end, size, out[0] + cell,
+                       out[1] + cell, out[2] + cell, out[3] + cell, out[4] + cell);
+}
+
+static void launch_rows(const ZmTrack *table, int64_t m, int n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, int size,
+                        double *const *out, int64_t cell, hipStream_t st)
+{
+    hipLaunchKernelGGL(zm_summary_kernel, dim3((unsigned)m), dim3(ZM_THREADS), 0, st, table, n_tracks, track_of, start, end, size, out[0] + cell,
+                       out[1] + cell, out[2] + cell, out[3] + cell, out[4] + cell);
+}
+
+// Entry: SmTrack (full data) or ZmTrack (a zoom level) -- what S.table holds for this call
+template <typename Entry>
 static int summary_launch(SummaryBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, int64_t n,
                           int32_t size, double *const *out, hipStream_t st)
 {
     constexpr int64_t ROWS_PER_LAUNCH = 1 << 25;  // (a grid's threads are counted in 32 bits: 2^25 workgroups of 64)
     for (int64_t first = 0; first < n; first += ROWS_PER_LAUNCH) {
         const int64_t m = n - first < ROWS_PER_LAUNCH ? n - first : ROWS_PER_LAUNCH, cell = first * (int64_t)size;
-        hipLaunchKernelGGL(sm_summary_kernel, dim3((unsigned)m), dim3(SM_THREADS), 0, st, S.table.as<SmTrack>(), (int)n_tracks, track_of + first,
-                           start + first, end + first, (int)size, out[0] + cell, out[1] + cell, out[2] + cell, out[3] + cell, out[4] + cell);
+        launch_rows(S.table.as<Entry>(), m, (int)n_tracks, track_of + first, start + first, end + first, (int)size, out, cell, st);
         BXMI_LAUNCH_CHECK();
     }
     return BXMI_OK;
 }
 
-extern "C" int bxmi_spans_summarize_dev(bxmi_spans_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
-                                        const int32_t *end, int64_t n, int32_t size, double *valid, double *min, double *max, double *sum,
-                                        double *sumsq, void *stream)
+// The device form of both kinds of track: Entry is what the kernel reads for a Handle.
+template <typename Entry, typename Handle>
+static int summarize_dev(const char *who, Handle *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                         int64_t n, int32_t size, double *const *out, void *stream)
 {
-    const char *who = "bxmi_spans_summarize_dev";
-    double *const out[5] = {valid, min, max, sum, sumsq};
     BXMI_TRY(summary_check(who, tracks, n_tracks, track_of, start, end, n, size, reinterpret_cast<void *const *>(out)));
     if (n == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_summary.lock);
     BXMI_TRY(g_summary.enter());
     BXMI_TRY(summary_fill_table(g_summary.bufs, tracks, n_tracks, as_stream(stream)));
-    return summary_launch(g_summary.bufs, n_tracks, track_of, start, end, n, size, out, as_stream(stream));
+    return summary_launch<Entry>(g_summary.bufs, n_tracks, track_of, start, end, n, size, out, as_stream(stream));
 }
 
-extern "C" int bxmi_spans_summarize(bxmi_spans_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
-                                    int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq)
+// The host form of both kinds: through the device in slabs.
+template <typename Entry, typename Handle>
+static int summarize_host(const char *who, Handle *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                          int64_t n, int32_t size, double *const *out)
 {
-    const char *who = "bxmi_spans_summarize";
-    double *const out[5] = {valid, min, max, sum, sumsq};
     BXMI_TRY(summary_check(who, tracks, n_tracks, track_of, start, end, n, size, reinterpret_cast<void *const *>(out)));
     BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
     for (int64_t i = 0; i < n; i++)
@@ -161,10 +265,40 @@ extern "C" int bxmi_spans_summarize(bxmi_spans_t *const *tracks, int32_t n_track
         BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of + first, in_bytes, hipMemcpyHostToDevice, st));
         BXMI_HIP(hipMemcpyAsync(S.q_start.p, start + first, in_bytes, hipMemcpyHostToDevice, st));
         BXMI_HIP(hipMemcpyAsync(S.q_end.p, end + first, in_bytes, hipMemcpyHostToDevice, st));
-        BXMI_TRY(summary_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), S.q_end.as<int32_t>(), m, size, dev_out, st));
+        BXMI_TRY(summary_launch<Entry>(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), S.q_end.as<int32_t>(), m, size, dev_out, st));
         for (int k = 0; k < 5; k++)
             BXMI_HIP(hipMemcpyAsync(out[k] + first * (int64_t)size, dev_out[k], out_bytes, hipMemcpyDeviceToHost, st));
         BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
     }
     return BXMI_OK;
+}
+
+extern "C" int bxmi_spans_summarize_dev(bxmi_spans_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                        const int32_t *end, int64_t n, int32_t size, double *valid, double *min, double *max, double *sum,
+                                        double *sumsq, void *stream)
+{
+    double *const out[5] = {valid, min, max, sum, sumsq};
+    return summarize_dev<SmTrack>("bxmi_spans_summarize_dev", tracks, n_tracks, track_of, start, end, n, size, out, stream);
+}
+
+extern "C" int bxmi_spans_summarize(bxmi_spans_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                                    int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq)
+{
+    double *const out[5] = {valid, min, max, sum, sumsq};
+    return summarize_host<SmTrack>("bxmi_spans_summarize", tracks, n_tracks, track_of, start, end, n, size, out);
+}
+
+extern "C" int bxmi_zoom_summarize_dev(bxmi_zoom_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                       const int32_t *end, int64_t n, int32_t size, double *valid, double *min, double *max, double *sum,
+                                       double *sumsq, void *stream)
+{
+    double *const out[5] = {valid, min, max, sum, sumsq};
+    return summarize_dev<ZmTrack>("bxmi_zoom_summarize_dev", tracks, n_tracks, track_of, start, end, n, size, out, stream);
+}
+
+extern "C" int bxmi_zoom_summarize(bxmi_zoom_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                                   int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq)
+{
+    double *const out[5] = {valid, min, max, sum, sumsq};
+    return summarize_host<ZmTrack>("bxmi_zoom_summarize", tracks, n_tracks, track_of, start, end, n, size, out);
 }

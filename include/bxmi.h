@@ -24,6 +24,8 @@
  *   scripts/bed_bigwig_profile.py:27-41   totals += values; valid += ~isnan per site   -> bxmi_scores_profile*
  *   lib/bx/bbi/bbi_file.pyx:66-111,187-260, bigwig_file.pyx:93-108,176-185
  *                                BigWigFile.summarize_from_full / query over full data -> bxmi_spans_*
+ *   lib/bx/bbi/bbi_file.pyx:296-432, cirtree_file.pyx:5-20,49-105
+ *                                ZoomLevel._summarize: summarize / query from a zoom level -> bxmi_zoom_*
  *   (intersection.pyx has no C ABI of its own: its cdef classes are the
  *    interface, so the entry points below are what a Cython/ctypes shim of
  *    those classes binds; see INTEGRATION.md.)
@@ -442,6 +444,38 @@ int bxmi_spans_summarize(bxmi_spans_t *const *tracks, int32_t n_tracks, const in
  * [0, n_tracks) or a negative coordinate gives an empty row. */
 int bxmi_spans_summarize_dev(bxmi_spans_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
                              int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq, void *stream);
+
+/* ---- zoom tracks and the binned summaries answered from them  (lib/bx/bbi/bbi_file.pyx:296-432) ----------
+ * One bxmi_zoom_t is ONE chromosome's part of ONE zoom level of a bigWig file (bxmi.bigwig.read_zoom_file returns it): the n
+ * summary records -- [start[i], end[i]) with valid[i], min[i], max[i], sum[i], sumsq[i] -- IN LOAD ORDER, and the level's n_leaves
+ * leaf entries for that chromosome: leaf k covers the bases between leaf_lo[k] and leaf_hi[k] as the reference's overlap test sees
+ * them (-1: the entry starts on an earlier chromosome; 2^31-1: it ends on a later one) and holds records [leaf_first[k],
+ * leaf_first[k + 1]); leaf_first has n_leaves + 1 entries, from 0 to n.  Only an ORDERED level is accepted: record starts and record
+ * ends both non-decreasing, start <= end for every record, leaf_lo and leaf_hi both non-decreasing, no negative coordinate (a
+ * leaf_lo of -1 apart); anything else -> BXMI_EINVAL, the message naming the condition.  All of it is checked before the first
+ * device call. */
+typedef struct bxmi_zoom bxmi_zoom_t;
+int bxmi_zoom_create(const int32_t *start, const int32_t *end, const uint32_t *valid, const float *min, const float *max, const float *sum,
+                     const float *sumsq, int64_t n, const int32_t *leaf_lo, const int32_t *leaf_hi, const int64_t *leaf_first, int64_t n_leaves,
+                     bxmi_zoom_t **out);
+int bxmi_zoom_destroy(bxmi_zoom_t *h);
+int bxmi_zoom_info(const bxmi_zoom_t *h, int64_t *n, int64_t *n_leaves);
+/* ZoomLevel._summarize (bbi_file.pyx:355-432) for n regions [start[i], end[i]) of tracks[track_of[i]], `size` bins each; the bins
+ * are those of bxmi_spans_summarize.  A region loads the records of every leaf with start < leaf_hi and end > leaf_lo, in order.
+ * Per bin [b0, b1): the records at the front of that list that end at or before b0 are passed over; if none is left the bin is
+ * valid = sum = sumsq = 0, min = max = NaN; else min and max start from the front record's (whether or not it overlaps the bin)
+ * and the records are walked until one starts at or after b1, each with overlap > 0 adding
+ *   f = (float)((double)overlap / (end - start));  valid = (float)((double)valid + (double)rec.valid * (double)f), sum and sumsq
+ * likewise -- float accumulators, every product and sum rounded in double first, never fused -- and widening max / min (a NaN
+ * changes neither).  The five outputs are [n, size] float64 planes as for bxmi_spans_summarize, bit for bit the reference's;
+ * valid is NOT rounded to an integer.  track_of[i] < 0 or start[i] >= end[i] (the reference answers None) is the same EMPTY ROW:
+ * 0, +inf, -inf, 0, 0.  Arguments, errors, n == 0, the library's table and staging: as bxmi_spans_summarize, with which these
+ * calls share them -- one summary call of either kind at a time per process.  Host arrays; BLOCKS until the outputs are written. */
+int bxmi_zoom_summarize(bxmi_zoom_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                        int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq);
+/* Device variant, as bxmi_spans_summarize_dev. */
+int bxmi_zoom_summarize_dev(bxmi_zoom_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                            int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq, void *stream);
 
 /* ---- BED text -> SoA columns on the host (the step before the hot path) ------
  * Strict single-pass parser for what lib/bx/bitset_builders.py:33-46 and
