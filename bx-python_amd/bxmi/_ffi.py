@@ -92,6 +92,11 @@ _SIGNATURES = {
     "bxmi_zoom_info": [vp, _p(i64), _p(i64)],
     "bxmi_zoom_summarize": [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp],
     "bxmi_zoom_summarize_dev": [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp],
+    "bxmi_beds_create": [vp, vp, i64, _p(vp)],
+    "bxmi_beds_destroy": [vp],
+    "bxmi_beds_info": [vp, _p(i64), _p(C.c_int)],
+    "bxmi_beds_summarize": [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp],
+    "bxmi_beds_summarize_dev": [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp],
     "bxmi_bits_create": [i64, i64, _p(vp)],
     "bxmi_bits_destroy": [vp],
     "bxmi_bits_info": [vp, _p(i32), _p(i32), _p(i32)],

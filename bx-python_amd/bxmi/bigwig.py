@@ -27,11 +27,11 @@ CIRTREE_MAGIC = 0x2468ACE0
 BEDGRAPH, VARIABLE_STEP, FIXED_STEP = 1, 2, 3
 
 
-def byte_order(head):
-    """'<' or '>' when the first four bytes are the bigWig magic number in that order, else None."""
+def byte_order(head, magic=BIGWIG_MAGIC):
+    """'<' or '>' when the first four bytes are the bigWig magic number (or `magic`) in that order, else None."""
     if len(head) >= 4:
         for order in (">", "<"):
-            if struct.unpack(order + "I", head[:4])[0] == BIGWIG_MAGIC:
+            if struct.unpack(order + "I", head[:4])[0] == magic:
                 return order
     return None
 
@@ -41,16 +41,23 @@ def is_bigwig(path):
         return byte_order(f.read(4)) is not None
 
 
+_KIND = {BIGWIG_MAGIC: "bigWig", BIGBED_MAGIC: "bigBed"}
+
+
 class _Header:
-    def __init__(self, data):
-        order = byte_order(data)
+    """The 64-byte header of a file of the kind `magic` names (bigWig unless bxmi.bigbed asks for bigBed)."""
+
+    def __init__(self, data, magic=BIGWIG_MAGIC):
+        self.kind = _KIND[magic]
+        order = byte_order(data, magic)
         if order is None:
-            magic = data[:4]
-            if len(magic) == 4 and BIGBED_MAGIC in (struct.unpack(">I", magic)[0], struct.unpack("<I", magic)[0]):
-                raise ValueError("a bigBed file, not a bigWig file")
-            raise ValueError("not a bigWig file: bad magic number %r" % magic.hex())
+            found = data[:4]
+            other = BIGBED_MAGIC if magic == BIGWIG_MAGIC else BIGWIG_MAGIC
+            if byte_order(found, other) is not None:
+                raise ValueError("a %s file, not a %s file" % (_KIND[other], self.kind))
+            raise ValueError("not a %s file: bad magic number %r" % (self.kind, found.hex()))
         if len(data) < 64:
-            raise ValueError("not a bigWig file: the header is cut short")
+            raise ValueError("not a %s file: the header is cut short" % self.kind)
         self.order = order
         (self.version, self.zoom_levels, self.chrom_tree_offset, self.unzoomed_data_offset, self.unzoomed_index_offset, self.field_count,
          self.defined_field_count, self.as_offset, self.total_summary_offset, self.uncompress_buf_size) = struct.unpack_from(order + "HHQQQHHQQI", data, 4)
@@ -125,18 +132,21 @@ def _block_spans(block, order):
     return chrom_id, empty, empty, np.zeros(0, dtype=np.float32)
 
 
-def _read(path, data=None):
+def _read(path, data=None, magic=BIGWIG_MAGIC):
     if data is None:
         with open(path, "rb") as f:
             data = f.read()
-    return data, _Header(data)
+    return data, _Header(data, magic)
 
 
 def zoom_reductions(path=None, data=None):
     """[reduction_level] of the zoom headers (bbi_file.pyx:156-164: 24 bytes each from offset 64), in file order."""
-    data, h = _read(path, data)
+    return _zoom_reductions(*_read(path, data))
+
+
+def _zoom_reductions(data, h):
     if len(data) < 64 + 24 * h.zoom_levels:
-        raise ValueError("not a bigWig file: the zoom headers are cut short")
+        raise ValueError("not a %s file: the zoom headers are cut short" % h.kind)
     return [struct.unpack_from(h.order + "I", data, 64 + 24 * i)[0] for i in range(h.zoom_levels)]
 
 
@@ -228,9 +238,13 @@ def read_zoom_file(path=None, data=None):
     sumsq: float32; leaf_first: int64, n_leaves + 1 offsets.  Records of a chromosome in a leaf whose entry does not reach that
     chromosome can never be loaded and are left out, like leaves without a record of the chromosome.  Raises ValueError for a
     record beyond 2^31 - 1, a block that is not whole records, or an R-tree whose children leave their parents."""
-    data, h = _read(path, data)
+    return _read_zoom(*_read(path, data))
+
+
+def _read_zoom(data, h):
+    """read_zoom_file's body; bigBed zoom levels have the same format (bxmi.bigbed.read_zoom_file)"""
     if len(data) < 64 + 24 * h.zoom_levels:
-        raise ValueError("not a bigWig file: the zoom headers are cut short")
+        raise ValueError("not a %s file: the zoom headers are cut short" % h.kind)
     tree = _chrom_tree(data, h.chrom_tree_offset)
     rec = np.dtype([(k, h.order + t) for k, t in (("chrom", "u4"), ("start", "u4"), ("end", "u4"), ("valid", "u4"), ("min", "f4"), ("max", "f4"),
                                                   ("sum", "f4"), ("sumsq", "f4"))])

@@ -15,13 +15,19 @@ file on the device: its ``summarize`` answers a mixed batch as ``BigWigFile.summ
 picks for it or from full data, in two device calls.  The drop-in ``bx.bbi.bigwig_file.BigWigFile`` and
 ``bxmi.cli.bigwig_summary`` use zoom levels only when asked (``use_zoom=True``, ``-z``): their default is kept for compatibility
 with tests that pin the earlier behaviour, and is meant to flip later.
+
+``BedTrack`` is one chromosome's bigBed records (start, end) in file order (``bxmi_beds_*``; lib/bx/bbi/bigbed_file.pyx):
+``summarize_beds`` and ``summarize_beds_dev`` give ``BigBedFile.summarize_from_full`` -- the coverage of every bin by the records,
+each weighted as a bigWig item of value 1 -- bit for bit, at the cost of a region's own records although their ends are not in
+order.  ``BedSet`` is a whole bigBed file on the device, the counterpart of ``TrackSet``; it is the engine under
+``bx.bbi.bigbed_file`` and ``bxmi.cli.bigbed_summary``.
 """
 import collections
 import ctypes as C
 
 import numpy as np
 
-from . import _ffi, bigwig
+from . import _ffi, bigbed, bigwig
 from ._ffi import as_i32, call, ptr
 
 # [n, size] float64 each: rounded sum of weights, smallest and largest value (+inf / -inf for an empty bin), sum of value * weight,
@@ -93,6 +99,72 @@ def summarize_dev(tracks, track_of, starts, ends, size, stream=None):
     size = int(size)
     out = [torch.empty((n, max(size, 0)), dtype=torch.float64, device=dev) for _ in range(5)]
     call("bxmi_spans_summarize_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), ends.data_ptr(), n, size,
+         *[a.data_ptr() for a in out], stream)
+    return Summary(*out)
+
+
+class BedTrack:
+    """(start, end) records of one chromosome of a bigBed file on the device, in the order given (file order); no values: every
+    record counts 1.  `sorted`: the starts never descend, which holds in every real bigBed whatever its ends do; other tracks are
+    summarized by a slow general walk."""
+
+    def __init__(self, starts, ends):
+        _ffi.require_gpu()
+        s, e = as_i32(starts), as_i32(ends)
+        if s.shape != e.shape or s.ndim != 1:
+            raise ValueError("starts and ends must be 1-d arrays of equal length")
+        h = C.c_void_p()
+        call("bxmi_beds_create", ptr(s), ptr(e), len(s), C.byref(h))
+        self._h = h
+        n, is_sorted = C.c_int64(0), C.c_int(0)
+        call("bxmi_beds_info", self._h, C.byref(n), C.byref(is_sorted))
+        self.n, self.sorted = n.value, bool(is_sorted.value)
+
+    @classmethod
+    def from_bigbed(cls, path):
+        """{chrom: BedTrack} of a bigBed file, chromosomes without records included."""
+        return {chrom: cls(s, e) for chrom, (s, e, _) in bigbed.read_items_file(path).items()}
+
+    def close(self):
+        if self._h is not None:
+            _ffi.load().bxmi_beds_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def summarize_beds(tracks, track_of, starts, ends, size):
+    """BigBedFile.summarize_from_full of regions [starts[i], ends[i]) of the BedTrack tracks[track_of[i]], `size` bins each ->
+    Summary of [n, size] float64 numpy arrays: what `summarize` gives for the same records as items of value 1.  valid_count is
+    the rounded coverage chain, sum_data and sum_squares the chain itself, min_val and max_val 1 where a record overlaps the bin
+    (+inf / -inf elsewhere).  Empty rows and errors as `summarize`."""
+    _ffi.require_gpu()
+    tracks = list(tracks)
+    t, s, e = as_i32(track_of), as_i32(starts), as_i32(ends)
+    if not (t.shape == s.shape == e.shape) or t.ndim != 1:
+        raise ValueError("track_of, starts and ends must be 1-d arrays of equal length")
+    size = int(size)
+    out = [np.empty((len(t), max(size, 0)), dtype=np.float64) for _ in range(5)]
+    call("bxmi_beds_summarize", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), ptr(e), len(t), size, *[ptr(a) for a in out])
+    return Summary(*out)
+
+
+def summarize_beds_dev(tracks, track_of, starts, ends, size, stream=None):
+    """`summarize_beds` on device arrays, as `summarize_dev`: int32 torch tensors on the GPU in, float64 tensors out, queued on
+    torch's current stream (or `stream`).  It shares the library's track table with the other summaries: one summary call of any
+    kind at a time per process may be in flight."""
+    import torch
+
+    tracks = list(tracks)
+    (track_of, starts, ends), n, dev, stream = _ffi.device_args("summarize_beds_dev", "summarize_beds", ("track_of", "starts", "ends"),
+                                                                (track_of, starts, ends), stream)
+    size = int(size)
+    out = [torch.empty((n, max(size, 0)), dtype=torch.float64, device=dev) for _ in range(5)]
+    call("bxmi_beds_summarize_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), ends.data_ptr(), n, size,
          *[a.data_ptr() for a in out], stream)
     return Summary(*out)
 
@@ -224,15 +296,15 @@ NOT_ORDERED = ("the reference answers this region from a zoom level that is not 
                "call summarize_from_full for the answer from full data")
 
 
-class TrackSet:
-    """A whole bigWig file on the device: every chromosome's items (SpanTrack) and its part of every zoom level (ZoomTrack; None in
-    place of a part that is not ordered).  `summarize` answers a batch as the reference's BigWigFile.summarize would, row by row."""
+class _FileSet:
+    """What TrackSet and BedSet share: every chromosome's full data as one track (`self.full`: {chrom: track}, summarized by
+    `_summarize_full`) and its part of every zoom level (ZoomTrack; None in place of a part that is not ordered), and `summarize`,
+    which answers a batch as the reference's BBIFile.summarize would, row by row."""
 
-    def __init__(self, spans, levels):
-        """spans: bigwig.read_spans_file's result; levels: bigwig.read_zoom_file's"""
-        self.chroms = list(spans)
+    _summarize_full = None  # summarize or summarize_beds
+
+    def _set_levels(self, levels):
         self.reductions = [r for r, _ in levels]
-        self.spans = {chrom: SpanTrack(*spans[chrom]) for chrom in self.chroms}
         self.not_ordered = {}
         self.zoom = []  # one track per (chromosome, level), chromosome-major: track_of = chromosome * levels + level
         for chrom in self.chroms:
@@ -242,19 +314,16 @@ class TrackSet:
                     self.not_ordered[len(self.zoom)] = why
                 self.zoom.append(None if why else ZoomTrack(per[chrom]))
 
-    @classmethod
-    def from_bigwig(cls, path=None, data=None):
-        return cls(bigwig.read_spans_file(path, data=data), bigwig.read_zoom_file(path, data=data))
-
     def close(self):
-        _ffi.close_all(list(self.spans.values()) + [t for t in self.zoom if t is not None])
+        _ffi.close_all(list(self.full.values()) + [t for t in self.zoom if t is not None])
 
     def summarize(self, chroms, starts, ends, size, zoom=True):
-        """BigWigFile.summarize for a batch: `size` bins over chroms[i]:starts[i]-ends[i] -> Summary of [n, size] float64 arrays.
+        """BBIFile.summarize for a batch: `size` bins over chroms[i]:starts[i]-ends[i] -> Summary of [n, size] float64 arrays.
         `chroms`: names, or an int array of positions in self.chroms (-1: unknown).  With `zoom`, a row for which the reference's
         rule picks a level is answered from that level and the others from full data: ONE call of each kind, the zoom call's table
         listing every (chromosome, level) track.  Without it every row comes from full data.  An unknown chromosome or start >= end
         gives the empty row 0, +inf, -inf, 0, 0.  A row that needs a level which is not ordered raises NotImplementedError."""
+        summarize_full = type(self)._summarize_full
         chroms = np.asarray(chroms)
         if chroms.dtype.kind in "iu":
             track_of = as_i32(chroms)
@@ -268,11 +337,11 @@ class TrackSet:
             raise ValueError("a chromosome position beyond the file's %d chromosomes" % len(self.chroms))
         size = int(size)
         if size < 1 or not zoom or not self.reductions:
-            return summarize(self.spans.values(), track_of, s, e, size)
+            return summarize_full(self.full.values(), track_of, s, e, size)
         level = pick_levels(self.reductions, s, e, size)
         from_zoom = (level >= 0) & (track_of >= 0)  # (a row without a chromosome is the reference's None: the full call's empty row)
         if not from_zoom.any():
-            return summarize(self.spans.values(), track_of, s, e, size)
+            return summarize_full(self.full.values(), track_of, s, e, size)
         rows = np.nonzero(from_zoom)[0]
         zoom_track = track_of[rows] * len(self.reductions) + level[rows]
         for t in np.unique(zoom_track):
@@ -286,8 +355,43 @@ class TrackSet:
         if from_zoom.all():
             return part
         rest = np.nonzero(~from_zoom)[0]
-        full = summarize(self.spans.values(), track_of[rest], s[rest], e[rest], size)
+        full = summarize_full(self.full.values(), track_of[rest], s[rest], e[rest], size)
         out = [np.empty((len(s), size), dtype=np.float64) for _ in range(5)]
         for o, a, b in zip(out, part, full):
             o[rows], o[rest] = a, b
         return Summary(*out)
+
+
+class TrackSet(_FileSet):
+    """A whole bigWig file on the device: every chromosome's items (SpanTrack) and its part of every zoom level (ZoomTrack; None in
+    place of a part that is not ordered).  `summarize` answers a batch as the reference's BigWigFile.summarize would, row by row."""
+
+    _summarize_full = staticmethod(summarize)
+
+    def __init__(self, spans, levels):
+        """spans: bigwig.read_spans_file's result; levels: bigwig.read_zoom_file's"""
+        self.chroms = list(spans)
+        self.spans = self.full = {chrom: SpanTrack(*spans[chrom]) for chrom in self.chroms}
+        self._set_levels(levels)
+
+    @classmethod
+    def from_bigwig(cls, path=None, data=None):
+        return cls(bigwig.read_spans_file(path, data=data), bigwig.read_zoom_file(path, data=data))
+
+
+class BedSet(_FileSet):
+    """A whole bigBed file on the device, the counterpart of TrackSet: every chromosome's records (BedTrack) and its part of every
+    zoom level.  `summarize` answers a batch as the reference's BigBedFile.summarize would, row by row: from the level its rule picks
+    (`summarize_zoom`) or from the records (`summarize_beds`), one call of each kind."""
+
+    _summarize_full = staticmethod(summarize_beds)
+
+    def __init__(self, items, levels):
+        """items: bigbed.read_items_file's result; levels: bigbed.read_zoom_file's"""
+        self.chroms = list(items)
+        self.beds = self.full = {chrom: BedTrack(items[chrom][0], items[chrom][1]) for chrom in self.chroms}
+        self._set_levels(levels)
+
+    @classmethod
+    def from_bigbed(cls, path=None, data=None):
+        return cls(bigbed.read_items_file(path, data=data), bigbed.read_zoom_file(path, data=data))

@@ -1,17 +1,20 @@
 // summary.hip -- span tracks (bxmi_spans_*): one chromosome's bigWig items in HBM, in file order, and their binned summaries over
 // batches of regions (kernels and semantics: summary.hpp); zoom tracks (bxmi_zoom_*): one chromosome's part of one zoom level and
-// the same summaries answered from its records (zoom_summary.hpp).
+// the same summaries answered from its records (zoom_summary.hpp); bed tracks (bxmi_beds_*): one chromosome's bigBed records and
+// their coverage summaries (bed_summary.hpp).
 //
 // No floating-point contraction anywhere in this unit: the chains of summary.hpp round every product and every sum separately,
 // as the reference's x86-64 build does (hipcc's default would fuse them into multiply-adds).  The pragma, not __dmul_rn /
 // __dadd_rn, is what guarantees it: it covers every expression below, including the ones added later.
 #pragma clang fp contract(off)
 
+#include <memory>
 #include <mutex>
 #include <new>
 
 #include "common.hpp"
 #include "summary.hpp"
+#include "bed_summary.hpp"
 #include "track_batch.hpp"
 #include "zoom_summary.hpp"
 
@@ -153,13 +156,71 @@ extern "C" int bxmi_zoom_info(const bxmi_zoom_t *h, int64_t *n, int64_t *n_leave
     return BXMI_OK;
 }
 
+// One chromosome's bigBed records (bed_summary.hpp): starts and ends in file order, and the two running maxima of the ends.
+struct bxmi_beds {
+    int64_t n = 0;
+    int sorted = 1;
+    DevBuf start, end, reach, creach;
+    BdTrack entry() const { return BdTrack{start.as<int32_t>(), end.as<int32_t>(), reach.as<int32_t>(), creach.as<int32_t>(), n, sorted}; }
+};
+
+extern "C" int bxmi_beds_create(const int32_t *start, const int32_t *end, int64_t n, bxmi_beds_t **out)
+{
+    const char *who = "bxmi_beds_create";
+    if (!out) return fail(BXMI_EINVAL, "%s: out is NULL", who);
+    *out = nullptr;
+    if (n < 0 || (n > 0 && (!start || !end))) return fail(BXMI_EINVAL, "%s: bad arguments", who);
+    for (int64_t i = 0; i < n; i++)
+        if (start[i] < 0 || end[i] < 0)
+            return fail(BXMI_EINVAL, "%s: record %lld = [%d, %d) has a negative coordinate", who, (long long)i, (int)start[i], (int)end[i]);
+    std::unique_ptr<int32_t[]> reach(new (std::nothrow) int32_t[(size_t)(n > 0 ? 2 * n : 1)]);
+    bxmi_beds *h = new (std::nothrow) bxmi_beds();
+    if (!h || !reach) {
+        delete h;
+        return fail(BXMI_ENOMEM, "%s: host allocation failed", who);
+    }
+    h->n = n;
+    h->sorted = bd_build_reach(start, end, n, reach.get(), reach.get() + n);
+    struct Copy { DevBuf *to; const void *from; };
+    const Copy copies[] = {{&h->start, start}, {&h->end, end}, {&h->reach, reach.get()}, {&h->creach, reach.get() + n}};
+    const size_t bytes = (size_t)n * 4;
+    int rc = BXMI_OK;
+    for (const Copy &c : copies) {
+        if (rc == BXMI_OK) rc = c.to->reserve(bytes ? bytes : 4);
+        if (rc == BXMI_OK && bytes > 0) {
+            const hipError_t e = hipMemcpy(c.to->p, c.from, bytes, hipMemcpyHostToDevice);
+            if (e != hipSuccess) rc = fail(BXMI_EHIP, "%s: %s", who, hipGetErrorString(e));
+        }
+    }
+    if (rc != BXMI_OK) {
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_beds_destroy(bxmi_beds_t *h)
+{
+    delete h;
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_beds_info(const bxmi_beds_t *h, int64_t *n, int *sorted)
+{
+    if (!h) return fail(BXMI_EINVAL, "bxmi_beds_info: NULL handle");
+    if (n) *n = h->n;
+    if (sorted) *sorted = h->sorted;
+    return BXMI_OK;
+}
+
 // The track table and the staging of the host form belong to the library, not to a track (a call may name no track at all): one
 // summary call at a time per process may be in flight.
 namespace {
 constexpr int64_t SM_SLAB_CELLS = 1 << 23;  // the host form goes through the device in slabs of about this many (row, bin) cells
 
 struct SummaryBufs {
-    DevBuf table;                      // SmTrack or ZmTrack [n_tracks + 1] (the call's kind), the last one the spare entry
+    DevBuf table;                      // SmTrack, ZmTrack or BdTrack [n_tracks + 1] (the call's kind), the last one the spare entry
     DevBuf q_track, q_start, q_end;    // staging of the host form
     DevBuf r[5];
 };
@@ -190,6 +251,11 @@ static int summary_fill_table(SummaryBufs &S, bxmi_zoom_t *const *tracks, int32_
     return fill_track_table<ZmTrack, 8>(S.table, n_tracks, [&](int k) { return tracks[k]->entry(); }, ZmTrack{}, st);
 }
 
+static int summary_fill_table(SummaryBufs &S, bxmi_beds_t *const *tracks, int32_t n_tracks, hipStream_t st)
+{
+    return fill_track_table<BdTrack, 8>(S.table, n_tracks, [&](int k) { return tracks[k]->entry(); }, BdTrack{nullptr, nullptr, nullptr, nullptr, 0, 1}, st);
+}
+
 static void launch_rows(const SmTrack *table, int64_t m, int n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, int size,
                         double *const *out, int64_t cell, hipStream_t st)
 {
@@ -204,7 +270,14 @@ static void launch_rows(const ZmTrack *table, int64_t m, int n_tracks, const int
                        out[1] + cell, out[2] + cell, out[3] + cell, out[4] + cell);
 }
 
-// Entry: SmTrack (full data) or ZmTrack (a zoom level) -- what S.table holds for this call
+static void launch_rows(const BdTrack *table, int64_t m, int n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, int size,
+                        double *const *out, int64_t cell, hipStream_t st)
+{
+    hipLaunchKernelGGL(bd_summary_kernel, dim3((unsigned)m), dim3(BD_THREADS), 0, st, table, n_tracks, track_of, start, end, size, out[0] + cell,
+                       out[1] + cell, out[2] + cell, out[3] + cell, out[4] + cell);
+}
+
+// Entry: SmTrack (full data), ZmTrack (a zoom level) or BdTrack (bigBed records) -- what S.table holds for this call
 template <typename Entry>
 static int summary_launch(SummaryBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, int64_t n,
                           int32_t size, double *const *out, hipStream_t st)
@@ -218,7 +291,7 @@ static int summary_launch(SummaryBufs &S, int32_t n_tracks, const int32_t *track
     return BXMI_OK;
 }
 
-// The device form of both kinds of track: Entry is what the kernel reads for a Handle.
+// The device form of every kind of track: Entry is what the kernel reads for a Handle.
 template <typename Entry, typename Handle>
 static int summarize_dev(const char *who, Handle *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
                          int64_t n, int32_t size, double *const *out, void *stream)
@@ -231,7 +304,7 @@ static int summarize_dev(const char *who, Handle *const *tracks, int32_t n_track
     return summary_launch<Entry>(g_summary.bufs, n_tracks, track_of, start, end, n, size, out, as_stream(stream));
 }
 
-// The host form of both kinds: through the device in slabs.
+// The host form of every kind: through the device in slabs.
 template <typename Entry, typename Handle>
 static int summarize_host(const char *who, Handle *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
                           int64_t n, int32_t size, double *const *out)
@@ -301,4 +374,19 @@ extern "C" int bxmi_zoom_summarize(bxmi_zoom_t *const *tracks, int32_t n_tracks,
 {
     double *const out[5] = {valid, min, max, sum, sumsq};
     return summarize_host<ZmTrack>("bxmi_zoom_summarize", tracks, n_tracks, track_of, start, end, n, size, out);
+}
+
+extern "C" int bxmi_beds_summarize_dev(bxmi_beds_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                       const int32_t *end, int64_t n, int32_t size, double *valid, double *min, double *max, double *sum,
+                                       double *sumsq, void *stream)
+{
+    double *const out[5] = {valid, min, max, sum, sumsq};
+    return summarize_dev<BdTrack>("bxmi_beds_summarize_dev", tracks, n_tracks, track_of, start, end, n, size, out, stream);
+}
+
+extern "C" int bxmi_beds_summarize(bxmi_beds_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                                   int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq)
+{
+    double *const out[5] = {valid, min, max, sum, sumsq};
+    return summarize_host<BdTrack>("bxmi_beds_summarize", tracks, n_tracks, track_of, start, end, n, size, out);
 }

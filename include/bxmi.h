@@ -26,6 +26,8 @@
  *                                BigWigFile.summarize_from_full / query over full data -> bxmi_spans_*
  *   lib/bx/bbi/bbi_file.pyx:296-432, cirtree_file.pyx:5-20,49-105
  *                                ZoomLevel._summarize: summarize / query from a zoom level -> bxmi_zoom_*
+ *   lib/bx/bbi/bigbed_file.pyx:57-76,104-113
+ *                                BigBedFile.summarize_from_full / query over full data -> bxmi_beds_*
  *   (intersection.pyx has no C ABI of its own: its cdef classes are the
  *    interface, so the entry points below are what a Cython/ctypes shim of
  *    those classes binds; see INTEGRATION.md.)
@@ -475,6 +477,31 @@ int bxmi_zoom_summarize(bxmi_zoom_t *const *tracks, int32_t n_tracks, const int3
                         int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq);
 /* Device variant, as bxmi_spans_summarize_dev. */
 int bxmi_zoom_summarize_dev(bxmi_zoom_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                            int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq, void *stream);
+
+/* ---- bed tracks and their coverage summaries  (lib/bx/bbi/bigbed_file.pyx) ----------
+ * One bxmi_beds_t is ONE chromosome's bigBed records -- [start[i], end[i]) -- in HBM, IN FILE ORDER (bxmi.bigbed.read_items_file
+ * returns it).  There is no value array: the reference accumulates every record with the value 1.  bigBed records are sorted by
+ * start and their ends descend wherever features nest or overlap; creation also builds, on the host, the running maxima of the
+ * ends that the kernel searches and skips by (csrc/bed_summary.hpp).  A negative coordinate -> BXMI_EINVAL.  *sorted
+ * (bxmi_beds_info) = 1 when the starts never descend, as in every real bigBed: a region then costs its own records plus one test
+ * per chunk of records between the first record that reaches it and them; any other track is legal and takes a general walk over
+ * the whole track for every region. */
+typedef struct bxmi_beds bxmi_beds_t;
+int bxmi_beds_create(const int32_t *start, const int32_t *end, int64_t n, bxmi_beds_t **out);
+int bxmi_beds_destroy(bxmi_beds_t *h);
+int bxmi_beds_info(const bxmi_beds_t *h, int64_t *n, int *sorted);
+/* BigBedFile.summarize_from_full (bigbed_file.pyx:104-113) for n regions [start[i], end[i]) of tracks[track_of[i]], `size` bins each:
+ * bxmi_spans_summarize over the same records with every value 1.  The bins, the clipping and the weight w are those of
+ * bxmi_spans_summarize; per bin, over the records that overlap it IN FILE ORDER, acc += w in float64, one rounding per operation;
+ * then valid = acc rounded half to even, sum = sumsq = acc, min = max = 1 where a record overlaps the bin, else +inf and -inf.
+ * The five outputs are [n, size] float64 planes, bit for bit the reference's.  Empty rows, arguments, errors, n == 0, the
+ * library's table and staging: as bxmi_spans_summarize, with which these calls share them -- one summary call of any kind at a
+ * time per process.  Host arrays; BLOCKS until the outputs are written. */
+int bxmi_beds_summarize(bxmi_beds_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                        int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq);
+/* Device variant, as bxmi_spans_summarize_dev. */
+int bxmi_beds_summarize_dev(bxmi_beds_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
                             int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq, void *stream);
 
 /* ---- BED text -> SoA columns on the host (the step before the hot path) ------

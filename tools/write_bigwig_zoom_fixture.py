@@ -66,9 +66,16 @@ def rtree_bytes(order, leaves, fanout, at):
     return head + emit(root, at + 48)
 
 
-def write_bigwig_zoom(path, chroms, blocks, levels, compress=False, order="<"):
+def wiggle_block(order, block):
+    """((start chrom, start base, end chrom, end base), bytes) of one full-data block of a bigWig file"""
+    (chrom_id, first, last), raw = W.block_bytes(order, **block)
+    return (chrom_id, first, chrom_id, last), raw
+
+
+def write_bigwig_zoom(path, chroms, blocks, levels, compress=False, order="<", magic=W.BIGWIG_MAGIC, full_block=wiggle_block):
     """chroms, blocks: as write_bigwig_fixture.write_bigwig.  levels: [dict(reduction, records, per_block, fanout)] in file order,
-    records = [(chrom_id, start, end, valid_count, min, max, sum, sum_squares)] in file order."""
+    records = [(chrom_id, start, end, valid_count, min, max, sum, sum_squares)] in file order.  `magic` and `full_block` (what turns
+    one entry of `blocks` into its leaf range and its bytes) are what tools/write_bigbed_fixture.py replaces to write bigBed."""
     key_size = max(len(name) for name, _ in chroms)
     tree = struct.pack(order + "IIIIQQ", W.BPT_MAGIC, len(chroms), key_size, 8, len(chroms), 0)
     tree += struct.pack(order + "BBH", 1, 0, len(chroms))
@@ -89,8 +96,8 @@ def write_bigwig_zoom(path, chroms, blocks, levels, compress=False, order="<"):
 
     leaves = []
     for b in blocks:
-        (chrom_id, first, last), raw = W.block_bytes(order, **b)
-        leaves.append((chrom_id, first, chrom_id, last) + store(raw))
+        extent, raw = full_block(order, b)
+        leaves.append(extent + store(raw))
     index_offset = data_offset + len(body)
     body += rtree_bytes(order, leaves, max(len(leaves), 1), index_offset)
     zoom_headers = b""
@@ -107,7 +114,7 @@ def write_bigwig_zoom(path, chroms, blocks, levels, compress=False, order="<"):
         zoom_index_offset = data_offset + len(body)
         body += rtree_bytes(order, leaves, level["fanout"], zoom_index_offset)
         zoom_headers += struct.pack(order + "IIQQ", level["reduction"], 0, zoom_data_offset, zoom_index_offset)
-    header = struct.pack(order + "IHHQQQHHQQIQ", W.BIGWIG_MAGIC, 4, len(levels), chrom_tree_offset, data_offset, index_offset, 0, 0, 0, 0,
+    header = struct.pack(order + "IHHQQQHHQQIQ", magic, 4, len(levels), chrom_tree_offset, data_offset, index_offset, 0, 0, 0, 0,
                          biggest if compress else 0, 0)
     assert len(header) == 64
     with open(path, "wb") as f:
