@@ -9,7 +9,8 @@ level's ``reduction_level`` is at most that value); otherwise, BY DEFAULT, they 
 the zoom level its rule picks (bbi_file.pyx:296-432; bxmi.summary.ZoomTrack), bit for bit; only a level whose records are not in
 order still raises the same NotImplementedError.  The default is kept for compatibility with tests that pin the earlier
 behaviour and is meant to flip later.
-``get`` and ``get_as_array`` are host code over the file's spans.  The file is read once, when the object is made; its items go
+``get`` and ``get_as_array`` are host code over the file's spans; ``get_as_arrays`` answers a whole list of regions, each as
+``get_as_array`` would, in ONE device call (bxmi.summary.arrays).  The file is read once, when the object is made; its items go
 to the device on the first summary.  `chrom` may be str or bytes everywhere.
 """
 import numpy as np
@@ -166,3 +167,23 @@ class BigWigFile:
         for a, b, x in zip(*self._clipped(chrom, start, end)):
             out[a - start:b - start] = x
         return out
+
+    def get_as_arrays(self, chroms, starts, ends):
+        """`get_as_array` for every region `chroms[i]`:`starts[i]`-`ends[i]` in ONE device call: a list with one float32 array per
+        region, None where `get_as_array` answers None (start >= end, an unknown chromosome)."""
+        from bxmi.summary import arrays
+
+        names = [self._name(c) for c in chroms]
+        starts, ends = [_bits32(s) for s in starts], [_bits32(e) for e in ends]
+        if not len(names) == len(starts) == len(ends):
+            raise ValueError("chroms, starts and ends must have one length")
+        answered = [s < e and c in self._sizes for c, s, e in zip(names, starts, ends)]
+        if any(e > 2147483647 for e, ok in zip(ends, answered) if ok):
+            raise ValueError("regions beyond 2^31 - 1 are not supported")
+        order = sorted({c for c, ok in zip(names, answered) if ok})
+        track_of = [order.index(c) if ok else -1 for c, ok in zip(names, answered)]
+        # (a region that is not answered travels as an empty row)
+        values, offsets = arrays([self._track(c) for c in order], track_of, [s if ok else 0 for s, ok in zip(starts, answered)],
+                                 [e if ok else 0 for e, ok in zip(ends, answered)])
+        # (a copy per region, as get_as_array returns: no row keeps the batch alive or shares its memory)
+        return [values[offsets[i]:offsets[i + 1]].copy() if ok else None for i, ok in enumerate(answered)]

@@ -87,6 +87,8 @@ _SIGNATURES = {
     "bxmi_spans_info": [vp, _p(i64), _p(C.c_int)],
     "bxmi_spans_summarize": [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp],
     "bxmi_spans_summarize_dev": [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp],
+    "bxmi_spans_arrays": [vp, i32, vp, vp, i64, i32, vp, i64, vp],
+    "bxmi_spans_arrays_dev": [vp, i32, vp, vp, i64, i32, vp, i64, vp, vp],
     "bxmi_zoom_create": [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i64, _p(vp)],
     "bxmi_zoom_destroy": [vp],
     "bxmi_zoom_info": [vp, _p(i64), _p(i64)],

@@ -8,6 +8,11 @@ include/bxmi.h).  ``summarize`` answers from host arrays, ``summarize_dev`` from
 arrays per region bit for bit: every bin is its ordered float64 chain over the items that overlap it, products and sums rounded
 separately.  ``stats`` derives mean, coverage and standard deviation as ``query`` does.  These are the answers from full data.
 
+``arrays`` / ``matrix`` (``arrays_dev`` / ``matrix_dev`` on device arrays) are the UNREDUCED form, ``BigWigFile.get_as_array``
+(bigwig_file.pyx:122-137, 200-211) for a whole batch per call: every row's per-base float32 values, NaN where the file has no
+data, the later item winning where items overlap -- ragged rows one after another, or the site x base matrix [n, width] behind a
+base-resolution heatmap, which stays on the device with the ``_dev`` forms (``bxmi_spans_arrays*``).
+
 ``ZoomTrack`` is one chromosome's part of one zoom level (``bxmi_zoom_*``; bbi_file.pyx:296-432): ``summarize_zoom`` and
 ``summarize_zoom_dev`` answer a batch from such tracks as the reference's ``ZoomLevel._summarize`` does, bit for bit -- float32
 accumulators fed by float64 products and sums.  ``pick_level`` is the reference's choice of a level, and ``TrackSet`` is a whole
@@ -101,6 +106,82 @@ def summarize_dev(tracks, track_of, starts, ends, size, stream=None):
     call("bxmi_spans_summarize_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), ends.data_ptr(), n, size,
          *[a.data_ptr() for a in out], stream)
     return Summary(*out)
+
+
+def _rows_i32(track_of, starts, names):
+    t, s = as_i32(track_of), as_i32(starts)
+    if t.shape != s.shape or t.ndim != 1:
+        raise ValueError("%s must be 1-d arrays of equal length" % names)
+    return t, s
+
+
+def arrays(tracks, track_of, starts, ends):
+    """get_as_array of regions [starts[i], ends[i]) of tracks[track_of[i]] -> (values float32[total], offsets int64[n + 1]): row i
+    is values[offsets[i]:offsets[i + 1]], its per-base values -- NaN (numpy's) where no item covers the base, the value of the
+    LAST covering item in file order elsewhere, its bits unchanged.  A row with ends[i] <= starts[i] is empty; track_of[i] < 0
+    (unknown chromosome) is a NaN row; a base below 0 or at 2^31-1 and beyond holds no data.  One device pass over the OUTPUT: rows
+    of one base and rows of millions cost their bases."""
+    _ffi.require_gpu()
+    tracks = list(tracks)
+    t, s = _rows_i32(track_of, starts, "track_of, starts and ends")
+    e = as_i32(ends)
+    if e.shape != s.shape:
+        raise ValueError("track_of, starts and ends must be 1-d arrays of equal length")
+    offsets = np.zeros(len(s) + 1, dtype=np.int64)
+    np.cumsum(np.maximum(e.astype(np.int64) - s.astype(np.int64), 0), out=offsets[1:])
+    values = np.empty(int(offsets[-1]), dtype=np.float32)
+    call("bxmi_spans_arrays", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), len(t), 0, ptr(offsets), len(values), ptr(values))
+    return values, offsets
+
+
+def matrix(tracks, track_of, win_starts, width):
+    """get_as_array of the windows [win_starts[i], win_starts[i] + width) of tracks[track_of[i]] -> float32 [n, width]; values as
+    `arrays`.  width < 1 raises BxmiError (EINVAL)."""
+    _ffi.require_gpu()
+    tracks = list(tracks)
+    t, s = _rows_i32(track_of, win_starts, "track_of and win_starts")
+    width = int(width)
+    out = np.empty((len(t), max(width, 0)), dtype=np.float32)
+    call("bxmi_spans_arrays", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), len(t), width, None, out.size, ptr(out))
+    return out
+
+
+def arrays_dev(tracks, track_of, starts, ends, stream=None):
+    """`arrays` on device arrays: int32 torch tensors on the GPU in, (values float32[total], offsets int64[n + 1]) tensors out.  The
+    offsets are computed by torch on its current stream and `total` is read back to size the output -- ONE synchronisation; the
+    values are then queued on torch's current stream (or `stream`) and not waited for.  Unchecked entries as `summarize_dev`: a
+    track_of outside [0, len(tracks)) is a NaN row.  One summary call of any kind at a time per process may be in flight."""
+    import torch
+
+    tracks = list(tracks)
+    (track_of, starts, ends), n, dev, stream = _ffi.device_args("arrays_dev", "arrays", ("track_of", "starts", "ends"), (track_of, starts, ends), stream)
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        torch.cumsum((ends.to(torch.int64) - starts.to(torch.int64)).clamp_(min=0), 0, out=offsets[1:])
+    total = int(offsets[-1].item()) if n else 0
+    values = torch.empty(total, dtype=torch.float32, device=dev)
+    call("bxmi_spans_arrays_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), n, 0, offsets.data_ptr(), total,
+         values.data_ptr(), stream)
+    return values, offsets
+
+
+def matrix_dev(tracks, track_of, win_starts, width, stream=None, out=None):
+    """`matrix` on device arrays: int32 torch tensors on the GPU in, the float32 [n, width] tensor out -- `out` if given (contiguous
+    float32 [n, width] on the same device; 16-byte aligned it is written by 16-byte stores, otherwise element by element, with the
+    same result), else a new one.  Queued on torch's current stream (or `stream`), nothing is waited for: the matrix stays on the
+    device.  Unchecked entries and the one-call-at-a-time rule: as `arrays_dev`."""
+    import torch
+
+    tracks = list(tracks)
+    (track_of, win_starts), n, dev, stream = _ffi.device_args("matrix_dev", "matrix", ("track_of", "win_starts"), (track_of, win_starts), stream)
+    width = int(width)
+    if out is None:
+        out = torch.empty((n, max(width, 0)), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, width) or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous float32 [n, width] tensor on the device of the rows")
+    call("bxmi_spans_arrays_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), win_starts.data_ptr(), n, width, None, out.numel(),
+         out.data_ptr(), stream)
+    return out
 
 
 class BedTrack:
@@ -317,6 +398,20 @@ class _FileSet:
     def close(self):
         _ffi.close_all(list(self.full.values()) + [t for t in self.zoom if t is not None])
 
+    def _track_of(self, chroms):
+        """int32 positions in self.chroms of `chroms` (names, or an int array of such positions already), -1 for an unknown one"""
+        chroms = np.asarray(chroms)
+        if chroms.dtype.kind in "iu":
+            track_of = as_i32(chroms)
+        else:
+            index = {chrom: k for k, chrom in enumerate(self.chroms)}
+            track_of = np.array([index.get(c, -1) for c in chroms.tolist()], dtype=np.int32)
+        if track_of.ndim != 1:
+            raise ValueError("chroms, starts and ends must be 1-d arrays of equal length")
+        if len(track_of) and track_of.max() >= len(self.chroms):
+            raise ValueError("a chromosome position beyond the file's %d chromosomes" % len(self.chroms))
+        return track_of
+
     def summarize(self, chroms, starts, ends, size, zoom=True):
         """BBIFile.summarize for a batch: `size` bins over chroms[i]:starts[i]-ends[i] -> Summary of [n, size] float64 arrays.
         `chroms`: names, or an int array of positions in self.chroms (-1: unknown).  With `zoom`, a row for which the reference's
@@ -324,17 +419,10 @@ class _FileSet:
         listing every (chromosome, level) track.  Without it every row comes from full data.  An unknown chromosome or start >= end
         gives the empty row 0, +inf, -inf, 0, 0.  A row that needs a level which is not ordered raises NotImplementedError."""
         summarize_full = type(self)._summarize_full
-        chroms = np.asarray(chroms)
-        if chroms.dtype.kind in "iu":
-            track_of = as_i32(chroms)
-        else:
-            index = {chrom: k for k, chrom in enumerate(self.chroms)}
-            track_of = np.array([index.get(c, -1) for c in chroms.tolist()], dtype=np.int32)
+        track_of = self._track_of(chroms)
         s, e = as_i32(starts), as_i32(ends)
         if not (track_of.shape == s.shape == e.shape) or s.ndim != 1:
             raise ValueError("chroms, starts and ends must be 1-d arrays of equal length")
-        if len(track_of) and track_of.max() >= len(self.chroms):
-            raise ValueError("a chromosome position beyond the file's %d chromosomes" % len(self.chroms))
         size = int(size)
         if size < 1 or not zoom or not self.reductions:
             return summarize_full(self.full.values(), track_of, s, e, size)
@@ -377,6 +465,17 @@ class TrackSet(_FileSet):
     @classmethod
     def from_bigwig(cls, path=None, data=None):
         return cls(bigwig.read_spans_file(path, data=data), bigwig.read_zoom_file(path, data=data))
+
+    def arrays(self, chroms, starts, ends):
+        """BigWigFile.get_as_array for a mixed-chromosome batch in ONE call: (values float32[total], offsets int64[n + 1]) as
+        `arrays`.  `chroms` as in `summarize`; an unknown chromosome gives a NaN row (the reference answers None), start >= end an
+        empty one.  Always from full data: zoom levels hold no per-base values."""
+        return arrays(self.spans.values(), self._track_of(chroms), starts, ends)
+
+    def matrix(self, chroms, win_starts, width):
+        """The site x base matrix float32 [n, width] of the windows chroms[i]:win_starts[i]-(win_starts[i] + width) in ONE call, as
+        `matrix`; an unknown chromosome gives a NaN row."""
+        return matrix(self.spans.values(), self._track_of(chroms), win_starts, width)
 
 
 class BedSet(_FileSet):

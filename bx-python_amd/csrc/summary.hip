@@ -1,7 +1,7 @@
-// summary.hip -- span tracks (bxmi_spans_*): one chromosome's bigWig items in HBM, in file order, and their binned summaries over
-// batches of regions (kernels and semantics: summary.hpp); zoom tracks (bxmi_zoom_*): one chromosome's part of one zoom level and
-// the same summaries answered from its records (zoom_summary.hpp); bed tracks (bxmi_beds_*): one chromosome's bigBed records and
-// their coverage summaries (bed_summary.hpp).
+// summary.hip -- span tracks (bxmi_spans_*): one chromosome's bigWig items in HBM, in file order, their binned summaries over
+// batches of regions (kernels and semantics: summary.hpp) and their per-base values over batches of rows (span_arrays.hpp); zoom
+// tracks (bxmi_zoom_*): one chromosome's part of one zoom level and the same summaries answered from its records
+// (zoom_summary.hpp); bed tracks (bxmi_beds_*): one chromosome's bigBed records and their coverage summaries (bed_summary.hpp).
 //
 // No floating-point contraction anywhere in this unit: the chains of summary.hpp round every product and every sum separately,
 // as the reference's x86-64 build does (hipcc's default would fuse them into multiply-adds).  The pragma, not __dmul_rn /
@@ -15,6 +15,7 @@
 #include "common.hpp"
 #include "summary.hpp"
 #include "bed_summary.hpp"
+#include "span_arrays.hpp"
 #include "track_batch.hpp"
 #include "zoom_summary.hpp"
 
@@ -389,4 +390,99 @@ extern "C" int bxmi_beds_summarize(bxmi_beds_t *const *tracks, int32_t n_tracks,
 {
     double *const out[5] = {valid, min, max, sum, sumsq};
     return summarize_host<BdTrack>("bxmi_beds_summarize", tracks, n_tracks, track_of, start, end, n, size, out);
+}
+
+// ---- per-base arrays (span_arrays.hpp): BigWigFile.get_as_array for a batch of rows ----
+namespace {
+constexpr int64_t SA_SLAB = (int64_t)SA_TILE << 14;      // output elements per slab of the host form (64 MiB), whole tiles
+constexpr int64_t SA_TILES_PER_LAUNCH = 1 << 22;         // (a grid's threads are counted in 32 bits: 2^22 workgroups of 256)
+}  // namespace
+
+// what both forms check; `row_off` is only tested for being there
+static int arrays_check(const char *who, bxmi_spans_t *const *tracks, int32_t n_tracks, const void *track_of, const void *start, int64_t n,
+                        int32_t width, const void *row_off, int64_t total, const void *out)
+{
+    if (!row_off) {
+        BXMI_TRY(track_batch_check(who, "width", width, tracks, n_tracks, n));
+        if (total != n * (int64_t)width)
+            return fail(BXMI_EINVAL, "%s: total = %lld, but n * width = %lld", who, (long long)total, (long long)(n * (int64_t)width));
+    } else {
+        if (width != 0) return fail(BXMI_EINVAL, "%s: width = %d with row offsets, must be 0", who, (int)width);
+        BXMI_TRY(track_batch_check(who, "width", 1, tracks, n_tracks, n));
+        if (total < 0) return fail(BXMI_EINVAL, "%s: total = %lld is negative", who, (long long)total);
+    }
+    if ((n > 0 && (!track_of || !start)) || (n > 0 && total > 0 && !out)) return fail(BXMI_EINVAL, "%s: NULL array", who);
+    return BXMI_OK;
+}
+
+// output elements [o_first, o_first + count) of rows [row_base, row_base + n_rows); `out` is element o_first's address
+static int arrays_launch(SummaryBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n_rows, int64_t row_base,
+                         int32_t width, const int64_t *row_off, int64_t o_first, int64_t count, float *out, hipStream_t st)
+{
+    const int vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0;  // else the kernel stores element by element
+    constexpr int64_t PER_LAUNCH = SA_TILES_PER_LAUNCH * SA_TILE;
+    for (int64_t done = 0; done < count; done += PER_LAUNCH) {
+        const int64_t m = count - done < PER_LAUNCH ? count - done : PER_LAUNCH;
+        hipLaunchKernelGGL(sa_arrays_kernel, dim3((unsigned)div_up(m, SA_TILE)), dim3(SA_THREADS), 0, st, S.table.as<SmTrack>(), (int)n_tracks,
+                           track_of, start, n_rows, row_base, (int)width, row_off, o_first + done, m, out + done, vec);
+        BXMI_LAUNCH_CHECK();
+    }
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_spans_arrays_dev(bxmi_spans_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
+                                     int32_t width, const int64_t *row_off_or_null, int64_t total, float *out, void *stream)
+{
+    const char *who = "bxmi_spans_arrays_dev";
+    BXMI_TRY(arrays_check(who, tracks, n_tracks, track_of, start, n, width, row_off_or_null, total, out));
+    if (n == 0 || total == 0) return BXMI_OK;
+    std::lock_guard<std::mutex> hold(g_summary.lock);
+    BXMI_TRY(g_summary.enter());
+    BXMI_TRY(summary_fill_table(g_summary.bufs, tracks, n_tracks, as_stream(stream)));
+    return arrays_launch(g_summary.bufs, n_tracks, track_of, start, n, 0, width, row_off_or_null, 0, total, out, as_stream(stream));
+}
+
+extern "C" int bxmi_spans_arrays(bxmi_spans_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
+                                 int32_t width, const int64_t *row_off_or_null, int64_t total, float *out)
+{
+    const char *who = "bxmi_spans_arrays";
+    const int64_t *row_off = row_off_or_null;
+    BXMI_TRY(arrays_check(who, tracks, n_tracks, track_of, start, n, width, row_off, total, out));
+    if (row_off) {
+        if (row_off[0] != 0) return fail(BXMI_EINVAL, "%s: row_off[0] = %lld, must be 0", who, (long long)row_off[0]);
+        for (int64_t i = 0; i < n; i++) {
+            if (row_off[i + 1] < row_off[i]) return fail(BXMI_EINVAL, "%s: row_off descends at row %lld", who, (long long)i);
+            if (row_off[i + 1] - row_off[i] > 2147483647LL)
+                return fail(BXMI_EINVAL, "%s: row %lld has %lld elements, more than 2^31-1", who, (long long)i, (long long)(row_off[i + 1] - row_off[i]));
+        }
+        if (row_off[n] != total)
+            return fail(BXMI_EINVAL, "%s: row_off[n] = %lld, but total = %lld", who, (long long)row_off[n], (long long)total);
+    }
+    BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    if (n == 0 || total == 0) return BXMI_OK;
+    std::lock_guard<std::mutex> hold(g_summary.lock);
+    BXMI_TRY(g_summary.enter(true));
+    SummaryBufs &S = g_summary.bufs;
+    const hipStream_t st = g_summary.stream;
+    BXMI_TRY(summary_fill_table(S, tracks, n_tracks, st));
+    for (int64_t o0 = 0; o0 < total; o0 += SA_SLAB) {  // slabs of whole tiles; a row may lie in several
+        const int64_t count = total - o0 < SA_SLAB ? total - o0 : SA_SLAB;
+        const SaRows rows = sa_rows_of(row_off, n, width, o0, count);  // the slab's rows
+        const int64_t r0 = rows.r0, m = rows.m;
+        const size_t in_bytes = (size_t)m * sizeof(int32_t), off_bytes = (size_t)(m + 1) * sizeof(int64_t), out_bytes = (size_t)count * sizeof(float);
+        BXMI_TRY(S.q_track.reserve(in_bytes));
+        BXMI_TRY(S.q_start.reserve(in_bytes));
+        BXMI_TRY(S.r[0].reserve(out_bytes));
+        BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of + r0, in_bytes, hipMemcpyHostToDevice, st));
+        BXMI_HIP(hipMemcpyAsync(S.q_start.p, start + r0, in_bytes, hipMemcpyHostToDevice, st));
+        if (row_off) {  // (q_end holds the slab's offsets)
+            BXMI_TRY(S.q_end.reserve(off_bytes));
+            BXMI_HIP(hipMemcpyAsync(S.q_end.p, row_off + r0, off_bytes, hipMemcpyHostToDevice, st));
+        }
+        BXMI_TRY(arrays_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), m, r0, width, row_off ? S.q_end.as<int64_t>() : nullptr, o0,
+                               count, S.r[0].as<float>(), st));
+        BXMI_HIP(hipMemcpyAsync(out + o0, S.r[0].p, out_bytes, hipMemcpyDeviceToHost, st));
+        BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
+    }
+    return BXMI_OK;
 }

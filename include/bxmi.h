@@ -24,6 +24,8 @@
  *   scripts/bed_bigwig_profile.py:27-41   totals += values; valid += ~isnan per site   -> bxmi_scores_profile*
  *   lib/bx/bbi/bbi_file.pyx:66-111,187-260, bigwig_file.pyx:93-108,176-185
  *                                BigWigFile.summarize_from_full / query over full data -> bxmi_spans_*
+ *   lib/bx/bbi/bigwig_file.pyx:122-137,200-211
+ *                                BigWigFile.get_as_array, a batch of regions per call   -> bxmi_spans_arrays*
  *   lib/bx/bbi/bbi_file.pyx:296-432, cirtree_file.pyx:5-20,49-105
  *                                ZoomLevel._summarize: summarize / query from a zoom level -> bxmi_zoom_*
  *   lib/bx/bbi/bigbed_file.pyx:57-76,104-113
@@ -446,6 +448,32 @@ int bxmi_spans_summarize(bxmi_spans_t *const *tracks, int32_t n_tracks, const in
  * [0, n_tracks) or a negative coordinate gives an empty row. */
 int bxmi_spans_summarize_dev(bxmi_spans_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
                              int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq, void *stream);
+
+/* BigWigFile.get_as_array (bigwig_file.pyx:122-137, 200-211) for a batch of n rows: row i has L_i float32 elements, element j the
+ * value of tracks[track_of[i]] at position p = start[i] + j (taken in 64 bits): value[k] of the LARGEST k in file order with
+ * start[k] <= p < end[k] -- the reference assigns item after item, so where items overlap the later one wins -- its 32 bits copied
+ * unchanged (a NaN value keeps its payload).  The element is NaN, bit pattern 0x7FC00000 as numpy's, where no item covers p, where p
+ * is outside [0, 2^31-1), where track_of[i] is outside [0, n_tracks) and where the track is empty.  Zero-length and inverted items
+ * cover nothing.  The rows lie one after another in `out`, which has `total` elements:
+ *   row_off_or_null == NULL: width >= 1, every row has `width` elements and total must be n * width -- the matrix [n, width];
+ *   else: width must be 0, row_off has n + 1 entries and row i is out[row_off[i] .. row_off[i + 1]).  It must start at 0, never
+ *   descend and end at `total`, and no row may be longer than 2^31-1: else BXMI_EINVAL, the message naming the condition.
+ * n outside [0, 2^31-1], n_tracks < 0, a track_of[i] >= n_tracks -> BXMI_EINVAL (a negative track_of[i] names no track: a NaN row;
+ * a negative start[i] is legal).  n == 0 or total == 0 succeeds without a launch.  The work is cut into tiles of the OUTPUT, not
+ * into rows (csrc/span_arrays.hpp): rows of one base and rows of millions cost their bases.  An ordered track costs a row's own
+ * items; any other track is legal and walks the whole track for every piece of a row.  The table and the staging are those of
+ * bxmi_spans_summarize: one summary call of any kind -- these calls included -- at a time per process.  Host arrays; goes through
+ * the device in slabs of output and BLOCKS until `out` is written. */
+int bxmi_spans_arrays(bxmi_spans_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                      const int64_t *row_off_or_null, int64_t total, float *out);
+/* Device variant: `tracks` stays a host array of handles; track_of, start, row_off and out are device pointers of natural
+ * alignment.  Where `out` is 16-byte aligned every group of 4 elements is written by one 16-byte store; any other float-aligned
+ * `out` is written element by element: the same result, more slowly.  Stream-ordered on `stream`, no host synchronisation.  The
+ * entries cannot be checked without one: a track_of[i] outside [0, n_tracks) gives a NaN row, and row_off is the caller's to get
+ * right (whatever it holds, nothing outside out[0 .. total) is written and nothing outside the n rows is read; but offsets that
+ * do not cover out, such as row_off[n] < total, make every element left over a piece of its own with its own searches: very slow). */
+int bxmi_spans_arrays_dev(bxmi_spans_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                          const int64_t *row_off_or_null, int64_t total, float *out, void *stream);
 
 /* ---- zoom tracks and the binned summaries answered from them  (lib/bx/bbi/bbi_file.pyx:296-432) ----------
  * One bxmi_zoom_t is ONE chromosome's part of ONE zoom level of a bigWig file (bxmi.bigwig.read_zoom_file returns it): the n

@@ -1,0 +1,201 @@
+"""
+A NumPy restatement of the reference's ``BigWigFile.get_as_array`` (lib/bx/bbi/bigwig_file.pyx:122-137, 200-211, under the clipping of
+:82-88) over span tracks -- the model the device path (bxmi_spans_arrays*) is compared with, itself pinned to the reference's recorded
+arrays by tests/test_arrays_model_golden.py -- and the inputs the CPU and GPU tests of that path share.
+
+  * a region starts as float32 NaN (numpy's: 0x7FC00000); every item of the track, IN FILE ORDER, is clipped to the region,
+    dropped when nothing is left, and assigned to its bases: where items overlap the later one wins;
+  * values are moved as 32-bit words, so an item's own NaN keeps its bits;
+  * a row of a batch is the region [start, start + length) of tracks[track_of] (-1: no track, all NaN); positions below 0 hold no
+    data, and none at or beyond 2^31-1 can (an item ends there at the latest).
+"""
+import os
+import re
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+with open(os.path.join(ROOT, "bx-python_amd", "csrc", "span_arrays.hpp")) as _f:
+    _text = _f.read()
+THREADS = int(re.search(r"constexpr int SA_THREADS = (\d+);", _text).group(1))
+assert re.search(r"constexpr int SA_TILE = 4 \* SA_THREADS;", _text)
+TILE = 4 * THREADS
+CHUNK = int(re.search(r"constexpr int SA_CHUNK = (\d+);", _text).group(1))
+
+NAN_BITS = 0x7FC00000
+EMPTY_TRACK = (np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32))
+
+
+def region(track, start, end):
+    """get_as_array of [start, end) over one track (starts, ends, values), or None for no track: float32[max(end - start, 0)]"""
+    start, end = int(start), int(end)
+    out = np.full(max(end - start, 0), NAN_BITS, dtype=np.uint32)
+    if track is not None and len(out):
+        s, e, v = np.asarray(track[0], dtype=np.int64), np.asarray(track[1], dtype=np.int64), track[2]
+        bits = np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
+        for k in np.nonzero((e > start) & (s < end))[0]:  # (the others clip to nothing)
+            a, b = max(int(s[k]), start), min(int(e[k]), end)
+            if a >= b:
+                continue
+            out[a - start:b - start] = bits[k]
+    return out.view(np.float32)
+
+
+def lengths_of(starts, ends):
+    return np.maximum(np.asarray(ends, dtype=np.int64) - np.asarray(starts, dtype=np.int64), 0)
+
+
+def arrays(tracks, track_of, starts, ends):
+    """(values float32[total], offsets int64[n + 1]): the rows' regions one after another; a row with end <= start is empty"""
+    offsets = np.concatenate([[0], np.cumsum(lengths_of(starts, ends))]).astype(np.int64)
+    rows = [region(tracks[t] if t >= 0 else None, s, max(int(e), int(s))) for t, s, e in zip(track_of, starts, ends)]
+    return (np.concatenate(rows) if rows else np.zeros(0, np.float32)), offsets
+
+
+def matrix(tracks, track_of, win_starts, width):
+    """float32[n, width]: row i is the region [win_starts[i], win_starts[i] + width)"""
+    rows = [region(tracks[t] if t >= 0 else None, s, int(s) + int(width)) for t, s in zip(track_of, win_starts)]
+    return np.stack(rows) if rows else np.zeros((0, int(width)), np.float32)
+
+
+def same_bytes(got, want):
+    got, want = np.asarray(got), np.asarray(want)
+    return got.dtype == np.float32 and got.shape == want.shape and got.tobytes() == want.tobytes()
+
+
+def assert_same(got, want, what):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.dtype == np.float32 and got.shape == want.shape, (what, got.dtype, got.shape, want.shape)
+    if got.tobytes() != want.tobytes():
+        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
+        raise AssertionError((what, len(bad), bad[:4].tolist(), [hex(int(got.view(np.uint32)[tuple(b)])) for b in bad[:4]],
+                              [hex(int(want.view(np.uint32)[tuple(b)])) for b in bad[:4]]))
+
+
+# ------------------------------------------------------------ tracks --
+def unit_track(n=4 * CHUNK + 128, first=7):
+    """one base per item: item k = [first + k, first + k + 1); a region of r bases inside it meets exactly r items"""
+    k = np.arange(n, dtype=np.int32)
+    return first + k, first + k + 1, (np.sin(k.astype(np.float64)) * 3.0).astype(np.float32)
+
+
+def overlap_track():
+    """ORDERED (starts and ends never descend) with overlapping items: equal starts with growing ends, zero-length items, an item
+    that ends where the next starts, items whose values are NaNs with a payload"""
+    s = np.array([3, 3, 3, 10, 10, 20, 25, 25, 30, 40, 40, 41, 60, 60], dtype=np.int32)
+    e = np.array([5, 8, 12, 12, 15, 25, 25, 30, 40, 40, 41, 50, 60, 90], dtype=np.int32)
+    v = np.arange(1, len(s) + 1, dtype=np.float32) * np.float32(0.5)
+    bits = v.view(np.uint32).copy()
+    bits[4], bits[11] = 0x7FC00001, 0xFFA00000  # a quiet NaN with a payload, a negative signalling one
+    return s, e, bits.view(np.float32)
+
+
+def random_track(rng, n_items, ordered=True):
+    """items of 1-40 bases, touching, overlapping the next or a little apart (ordered), or overlapping and shuffled (not)"""
+    lengths = rng.integers(1, 41, size=n_items)
+    gaps = np.where(rng.random(n_items) < 0.3, rng.integers(0, 30, size=n_items), 0)
+    starts = np.cumsum(lengths + gaps) - lengths
+    values = (rng.standard_normal(n_items) * np.exp2(rng.integers(-12, 13, size=n_items))).astype(np.float32)
+    values[rng.random(n_items) < 0.02] = np.nan
+    ends = starts + lengths
+    if ordered:
+        ends = np.maximum.accumulate(ends + np.where(rng.random(n_items) < 0.2, rng.integers(0, 30, size=n_items), 0))  # some reach into the next
+    else:
+        starts = np.maximum(starts - rng.integers(0, 25, size=n_items), 0)
+        ends = starts + lengths + rng.integers(0, 60, size=n_items)
+        perm = rng.permutation(n_items)
+        starts, ends, values = starts[perm], ends[perm], values[perm]
+    return starts.astype(np.int32), ends.astype(np.int32), values
+
+
+def is_ordered(track):
+    s, e, _ = track
+    return bool(np.all(np.diff(s) >= 0) and np.all(np.diff(e) >= 0))
+
+
+_cache = {}
+
+
+def tracks():
+    """the tracks of the seeded cases: 0 ordered with overlaps (2000 items), 1 the unit track, 2 the overlap track, 3 not ordered (300
+    items), 4 the unit track reversed (not ordered), 5 empty"""
+    if "tracks" not in _cache:
+        rng = np.random.default_rng(41)
+        unit = unit_track()
+        _cache["tracks"] = [random_track(rng, 2000), unit, overlap_track(), random_track(rng, 300, ordered=False),
+                            tuple(a[::-1].copy() for a in unit), EMPTY_TRACK]
+        assert [is_ordered(t) for t in _cache["tracks"]] == [True, True, True, False, False, True]
+    return _cache["tracks"]
+
+
+EDGE_LENGTHS = (1, 2, 3, 5, TILE - 1, TILE, TILE + 1, 3 * TILE + 7)
+CHUNK_RUNS = (CHUNK - 1, CHUNK, CHUNK + 1, 3 * CHUNK + 5)
+
+
+def ragged_case():
+    """(tracks, track_of, starts, ends, (values, offsets) of the model): every length of EDGE_LENGTHS on every track and without
+    one (-1), shuffled, with empty rows (end == start, end < start) between full ones -- rows start off a 4-element boundary, and a
+    thread's 4 elements span 4 rows in the run of one-base rows at the front; windows from -5 and from 2^31 - 10; then
+    the runs of CHUNK_RUNS items, each in ONE segment: the three short ones share a tile, the long one begins the next (asserted)"""
+    if "ragged" not in _cache:
+        rng = np.random.default_rng(42)
+        ts = tracks()
+        reach = [int(t[1].max()) if len(t[1]) else 100 for t in ts]
+        rows = []
+        for t in list(range(len(ts))) + [-1]:
+            for length in EDGE_LENGTHS:
+                s = int(rng.integers(0, max(reach[t] - length // 2, 1))) if t >= 0 else 5
+                rows.append((t, s, s + length))
+        rows.append((2, 0, 95))
+        order = rng.permutation(len(rows))
+        mixed = [(2, p, p + 1) for p in (4, 11, 24, 26, 41, 45, 60, 89)]  # 8 rows of one base: some thread's 4 elements are 4 rows
+        for k in order:
+            mixed.append(rows[k])
+            if rng.random() < 0.3:
+                mixed.append((int(rng.integers(-1, len(ts))), 50, 50 - int(rng.integers(0, 3))))  # an empty row
+        mixed += [(0, -5, 40), (2, -5, 4), (1, 2 ** 31 - 10, 2 ** 31 - 1), (0, -3, -1), (0, -20, 0)]
+        assert sum(CHUNK_RUNS[:3]) <= TILE and CHUNK_RUNS[3] <= TILE
+        first = 7 + 11  # (inside the unit track)
+
+        def total():
+            return int(sum(max(e - s, 0) for _, s, e in mixed))
+
+        # a NaN row up to the next tile boundary, the three short runs in that tile, another up to the next, the long run
+        mixed.append((-1, 0, (-total()) % TILE))
+        run_rows = list(range(len(mixed), len(mixed) + 3))
+        mixed += [(1, first + k, first + k + r) for k, r in enumerate(CHUNK_RUNS[:3])]
+        mixed.append((-1, 0, (-total()) % TILE))
+        run_rows.append(len(mixed))
+        mixed.append((1, first + 3, first + 3 + CHUNK_RUNS[3]))
+        mixed += [(4, first, first + CHUNK + 1)]  # the reversed unit track: the general path over more than one chunk of items
+        track_of, starts, ends = (np.array(c, dtype=np.int32) for c in zip(*mixed))
+        want = arrays(ts, track_of, starts, ends)
+        # every run is ONE segment: its first and last output element lie in the same tile, and it meets that many items
+        for i, run in zip(run_rows, CHUNK_RUNS):
+            lo, hi = int(want[1][i]), int(want[1][i + 1])
+            assert hi - lo == run and lo // TILE == (hi - 1) // TILE and track_of[i] == 1, (i, run, lo, hi)
+            assert not np.isnan(want[0][lo:hi]).any()
+        assert len(mixed) < 400
+        _cache["ragged"] = (ts, track_of, starts, ends, want)
+    return _cache["ragged"]
+
+
+MATRIX_WIDTHS = (1, 3, 100, TILE, TILE + 1)
+
+
+def matrix_case(width):
+    """(tracks, track_of, win_starts, the model's [n, width]): windows on every track and on none, some from below 0 and some past
+    the data; 300 rows of the small widths, 24 of the two around a tile"""
+    key = ("matrix", width)
+    if key not in _cache:
+        rng = np.random.default_rng(1000 + width)
+        ts = tracks()
+        n = 300 if width <= 100 else 24
+        track_of = rng.integers(-1, len(ts), size=n).astype(np.int32)
+        reach = np.array([int(t[1].max()) if len(t[1]) else 100 for t in ts] + [100])[track_of]
+        starts = (rng.random(n) * (reach + 40)).astype(np.int64) - 20
+        starts[:2] = (-5, 2 ** 31 - 10)
+        track_of[:2] = (0, 1)
+        starts = starts.astype(np.int32)
+        _cache[key] = (ts, track_of, starts, matrix(ts, track_of, starts, width))
+    return _cache[key]

@@ -1,0 +1,378 @@
+"""
+Per-base bigWig arrays on the device (bxmi_spans_arrays*, bxmi.summary.arrays / matrix / arrays_dev / matrix_dev, TrackSet.arrays /
+matrix, bx.bbi.bigwig_file.BigWigFile.get_as_arrays, bxmi.cli.bigwig_matrix) against the ``get_as_array`` results recorded from the
+reference (tests/golden/arrays and tests/golden/profile/*.regions.npy) and, beyond them, against tests/arrays_model.py -- itself
+pinned to those recordings by tests/test_arrays_model_golden.py.  Every comparison is of bytes: a NaN must have the recorded bits.
+"""
+import io
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import arrays_model as M
+import profile_model
+from test_arrays_model_golden import ALL_FILES, PROFILE, PROFILE_MANIFEST, all_recorded, path_of, spans
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the _dev entry point this file drives by its C name (tests/test_device_entry_points_abi.py)
+DEV_ENTRY_POINTS = ("bxmi_spans_arrays_dev",)
+EINVAL = 1
+WIDTHS = (1, 10, 64)  # of the matrices cut from the recorded regions
+SENTINEL = 0xDEADBEEF
+
+
+def batch_of(name):
+    """(chromosome order, chromosome names, track_of, starts, ends, recorded arrays or None) of all recorded regions of a file"""
+    order = list(spans(name))
+    cases = all_recorded(name)
+    chroms = [c for (c, _, _), _ in cases]
+    return (order, chroms, [order.index(c) if c in order else -1 for c in chroms], [s for (_, s, _), _ in cases], [e for (_, _, e), _ in cases],
+            [a for _, a in cases])
+
+
+def check_rows(values, offsets, starts, ends, recorded, what):
+    """a ragged answer against the recordings: the reference's None is an empty row where start >= end, a NaN row for an unknown
+    chromosome"""
+    assert values.dtype == np.float32 and offsets.dtype == np.int64 and len(offsets) == len(recorded) + 1 and offsets[0] == 0
+    assert offsets[-1] == len(values)
+    for i, want in enumerate(recorded):
+        got = values[offsets[i]:offsets[i + 1]]
+        if want is None:
+            want = np.full(max(ends[i] - starts[i], 0), M.NAN_BITS, dtype=np.uint32).view(np.float32)
+        M.assert_same(got, want, (what, i))
+
+
+# ------------------------------------------------------------ every recorded case, through every layer --
+@pytest.mark.parametrize("name", ALL_FILES)
+def test_arrays_and_matrix_give_the_recorded_arrays(name):
+    """all regions of a file in ONE ragged call; then, as matrices, the first `width` bases of the regions that have them"""
+    from bxmi import summary
+
+    tracks = summary.SpanTrack.from_bigwig(path_of(name))
+    order, _, track_of, starts, ends, recorded = batch_of(name)
+    values, offsets = summary.arrays([tracks[c] for c in order], track_of, starts, ends)
+    check_rows(values, offsets, starts, ends, recorded, name)
+    for width in WIDTHS:
+        rows = [i for i, a in enumerate(recorded) if a is not None and len(a) >= width]
+        got = summary.matrix([tracks[c] for c in order], [track_of[i] for i in rows], [starts[i] for i in rows], width)
+        M.assert_same(got, np.stack([recorded[i][:width] for i in rows]), (name, width))
+    for chrom, t in tracks.items():
+        assert t.n == len(spans(name)[chrom][0]) and t.ordered == M.is_ordered(spans(name)[chrom])
+        t.close()
+
+
+@pytest.mark.parametrize("name", ALL_FILES)
+def test_track_set_answers_a_mixed_batch(name):
+    from bxmi import summary
+
+    file_tracks = summary.TrackSet.from_bigwig(path_of(name))
+    order, chroms, track_of, starts, ends, recorded = batch_of(name)
+    try:
+        assert file_tracks.chroms == order
+        check_rows(*file_tracks.arrays(chroms + ["chrNone"], starts + [3], ends + [8]), starts + [3], ends + [8], recorded + [None], (name, "names"))
+        check_rows(*file_tracks.arrays(track_of, starts, ends), starts, ends, recorded, (name, "positions"))
+        rows = [i for i, a in enumerate(recorded) if a is not None and len(a) >= 10]
+        got = file_tracks.matrix([chroms[i] for i in rows] + ["chrNone"], [starts[i] for i in rows] + [0], 10)
+        want = np.stack([recorded[i][:10] for i in rows] + [np.full(10, M.NAN_BITS, dtype=np.uint32).view(np.float32)])
+        M.assert_same(got, want, (name, "matrix"))
+        with pytest.raises(ValueError):
+            file_tracks.matrix([len(order)], [0], 4)
+    finally:
+        file_tracks.close()
+
+
+@pytest.mark.parametrize("name", ALL_FILES)
+def test_drop_in_get_as_arrays(name):
+    import bx.bbi.bigwig_file as drop_in
+
+    _, chroms, _, starts, ends, recorded = batch_of(name)
+    with open(path_of(name), "rb") as f:
+        bw = drop_in.BigWigFile(f)
+    got = bw.get_as_arrays([c.encode() if k % 2 else c for k, c in enumerate(chroms)], starts, ends)
+    assert len(got) == len(recorded)
+    for i, (g, want) in enumerate(zip(got, recorded)):
+        if want is None:
+            assert g is None, (name, i)
+        else:
+            M.assert_same(g, want, (name, i))
+            assert g.base is None  # an array of its own, as get_as_array returns
+            M.assert_same(bw.get_as_array(chroms[i], starts[i], ends[i]), want, (name, i, "the host method"))
+    assert bw.get_as_arrays([], [], []) == []
+    with pytest.raises(OverflowError):
+        bw.get_as_arrays([chroms[0]], [-1], [5])
+    bw.close()
+
+
+def windows_in(recorded, starts, padding):
+    """the recorded regions that hold 2 * padding bases, as BED rows whose centred window is the region's head"""
+    rows = [i for i, a in enumerate(recorded) if a is not None and len(a) >= 2 * padding]
+    return rows, [(starts[i], starts[i] + 2 * padding) for i in rows]
+
+
+def text_of(chrom, start, end, values):
+    return "\t".join([chrom, str(start), str(end)] + ["%.9g" % x for x in values]) + "\n"
+
+
+@pytest.mark.parametrize("name", ALL_FILES)
+def test_command_line_prints_and_saves_the_recorded_values(name, tmp_path):
+    from bxmi.cli import bigwig_matrix
+
+    _, chroms, _, starts, _, recorded = batch_of(name)
+    for padding in (1, 5, 32):
+        rows, bed_rows = windows_in(recorded, starts, padding)
+        if not rows:
+            continue
+        bed = "# sites\n" + "".join("%s\t%d\t%d\n" % (chroms[i], s, e) for i, (s, e) in zip(rows, bed_rows)) + "chrNone\t7\t9\n"
+        out = io.StringIO()
+        bigwig_matrix.main([path_of(name), str(padding)], stdin=io.StringIO(bed), out=out)
+        nan_row = np.full(2 * padding, np.nan, dtype=np.float32)
+        want = "".join(text_of(chroms[i], s, e, recorded[i][:2 * padding]) for i, (s, e) in zip(rows, bed_rows)) + text_of("chrNone", 7, 9, nan_row)
+        assert out.getvalue() == want, (name, padding)
+        saved = str(tmp_path / ("m%d.npy" % padding))
+        bigwig_matrix.main([path_of(name), str(padding), "-o", saved], stdin=io.StringIO(bed), out=out)
+        M.assert_same(np.load(saved), np.stack([recorded[i][:2 * padding] for i in rows] + [nan_row]), (name, padding, "saved"))
+        plain = str(tmp_path / ("plain%d" % padding))  # (the name as given, no suffix added)
+        bigwig_matrix.main([path_of(name), str(padding), "-o", plain], stdin=io.StringIO(bed), out=out)
+        assert os.path.exists(plain) and open(plain, "rb").read() == open(saved, "rb").read()
+
+
+def test_command_line_as_a_process():
+    name = "nan.bw"
+    _, chroms, _, starts, _, recorded = batch_of(name)
+    rows, bed_rows = windows_in(recorded, starts, 3)
+    bed = "".join("%s\t%d\t%d\n" % (chroms[i], s, e) for i, (s, e) in zip(rows, bed_rows))
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "bx-python_amd")] + os.environ.get("PYTHONPATH", "").split(os.pathsep)))
+    cmd = [sys.executable, "-m", "bxmi.cli.bigwig_matrix", path_of(name), "3"]
+    got = subprocess.run(cmd, input=bed, env=env, check=True, stdout=subprocess.PIPE, universal_newlines=True, timeout=300).stdout
+    assert got == "".join(text_of(chroms[i], s, e, recorded[i][:6]) for i, (s, e) in zip(rows, bed_rows)) and "nan" in got
+
+
+# ------------------------------------------------------------ consistency with the site profiles --
+@pytest.mark.parametrize("case", PROFILE_MANIFEST["profiles"], ids=lambda c: c["name"])
+def test_matrix_columns_add_up_to_the_recorded_profile(case):
+    """the profile is the matrix reduced: its columns summed in row order in float64 (NaN -> +0.0) and its non-NaN counts are the
+    reference's recorded totals and valid counts, bit for bit"""
+    from bxmi import summary
+
+    tracks = summary.SpanTrack.from_bigwig(os.path.join(PROFILE, case["scores"]))
+    order = list(tracks)
+    chroms, win_starts, width = profile_model.centred_windows(profile_model.bed_rows(os.path.join(PROFILE, case["bed"])), case["padding"])
+    got = summary.matrix(tracks.values(), [order.index(c) if c in order else -1 for c in chroms], win_starts, width)
+    assert got.shape == (case["rows"], 2 * case["padding"])
+    totals, valid = np.zeros(width, dtype=np.float64), np.zeros(width, dtype=np.int32)
+    for row in got:
+        has = ~np.isnan(row)
+        totals += np.where(has, row, np.float32(0.0))
+        valid += has
+    want_totals, want_valid = np.load(os.path.join(PROFILE, case["totals"])), np.load(os.path.join(PROFILE, case["valid"]))
+    assert valid.dtype == want_valid.dtype and valid.tobytes() == want_valid.tobytes()
+    assert totals.tobytes() == want_totals.tobytes()
+    _ffi_close(tracks)
+
+
+def _ffi_close(tracks):
+    for t in tracks.values():
+        t.close()
+
+
+# ------------------------------------------------------------ the edge shapes, against the model --
+def test_ragged_rows_of_every_length():
+    """EDGE_LENGTHS on ordered, overlapping, unordered and empty tracks and on none, empty rows between them, windows from -5 and
+    from 2^31 - 10, segments of CHUNK - 1 ... 3 CHUNK + 5 items"""
+    from bxmi import summary
+
+    tracks, track_of, starts, ends, (want, want_offsets) = M.ragged_case()
+    lengths = set(M.lengths_of(starts, ends).tolist())
+    assert set(M.EDGE_LENGTHS) | set(M.CHUNK_RUNS) | {0} <= lengths and -1 in track_of and starts.min() == -20 and starts.max() == 2 ** 31 - 10
+    dev = [summary.SpanTrack(*t) for t in tracks]
+    assert [t.ordered for t in dev] == [M.is_ordered(t) for t in tracks]
+    values, offsets = summary.arrays(dev, track_of, starts, ends)
+    assert np.array_equal(offsets, want_offsets)
+    M.assert_same(values, want, "ragged")
+    for t in dev:
+        t.close()
+
+
+@pytest.mark.parametrize("width", M.MATRIX_WIDTHS)
+def test_matrix_of_every_width(width):
+    from bxmi import summary
+
+    tracks, track_of, starts, want = M.matrix_case(width)
+    dev = [summary.SpanTrack(*t) for t in tracks]
+    M.assert_same(summary.matrix(dev, track_of, starts, width), want, width)
+    for t in dev:
+        t.close()
+
+
+def test_host_form_goes_through_more_than_one_slab():
+    """17 rows of 2^20 + 3 bases: more than the 2^24 output elements of one slab, which ends inside a row"""
+    from bxmi import summary
+
+    track = M.unit_track()
+    width, n = (1 << 20) + 3, 17
+    starts = np.arange(n, dtype=np.int32) * 37 - 5
+    want = np.full((n, width), M.NAN_BITS, dtype=np.uint32)
+    head = M.matrix([track], np.zeros(n, dtype=np.int32), starts, 2048)  # (the track ends below 2048)
+    want[:, :2048] = head.view(np.uint32)
+    t = summary.SpanTrack(*track)
+    got = summary.matrix([t], np.zeros(n, dtype=np.int32), starts, width)
+    M.assert_same(got, want.view(np.float32), "slabs")
+    t.close()
+
+
+def test_ragged_host_form_goes_through_more_than_one_slab():
+    """ragged rows of 1 to 2^21 bases, 18.9 M output elements: the slab of 2^24 ends inside a row, and the second slab is given
+    only its own rows and offsets"""
+    from bxmi import summary
+
+    track = M.unit_track()
+    lengths = np.array([5, (1 << 21) + 1, 0, 1, (1 << 21) - 7, 3, (1 << 21) + 2, 0, (1 << 21), 1000, (1 << 21) + 9, 2, (1 << 21) - 1, (1 << 21) + 5,
+                        (1 << 21), 77, (1 << 21) + 3, 4], dtype=np.int64)
+    assert lengths.sum() > (1 << 24) + (1 << 20) and (1 << 24) not in np.cumsum(lengths)
+    starts = (np.arange(len(lengths), dtype=np.int32) * 53) % 1100 - 5
+    ends = (starts + lengths).astype(np.int32)
+    offsets = np.concatenate([[0], np.cumsum(lengths)])
+    want = np.full(int(offsets[-1]), M.NAN_BITS, dtype=np.uint32)
+    for i, (s, n) in enumerate(zip(starts, lengths)):  # (the track ends below 2048)
+        head = min(int(n), 2048)
+        want[offsets[i]:offsets[i] + head] = M.region(track, s, int(s) + head).view(np.uint32)
+    t = summary.SpanTrack(*track)
+    values, got_offsets = summary.arrays([t], np.zeros(len(lengths), dtype=np.int32), starts, ends)
+    assert np.array_equal(got_offsets, offsets)
+    M.assert_same(values, want.view(np.float32), "ragged slabs")
+    t.close()
+
+
+def arrays_dev_raw(tracks, track_of, starts, offsets, lead, tail=64):
+    """bxmi_spans_arrays_dev on arrays in device memory, on the null stream, `out` `lead` elements into an allocation filled with
+    SENTINEL -> the whole allocation as uint32"""
+    from bxmi import _ffi as ffi
+
+    total = int(offsets[-1])
+    rows = [ffi.DeviceArray.from_numpy(np.ascontiguousarray(a)) for a in (track_of, starts, offsets)]
+    out = ffi.DeviceArray.from_numpy(np.full(lead + total + tail, SENTINEL, dtype=np.uint32))
+    assert out.ptr % 16 == 0
+    ffi.call("bxmi_spans_arrays_dev", ffi.handles(tracks), len(tracks), rows[0].ptr, rows[1].ptr, len(track_of), 0, rows[2].ptr, total,
+             out.ptr + 4 * lead, None)
+    ffi.call("bxmi_synchronize", None)
+    words = out.to_numpy(np.uint32, lead + total + tail)
+    for a in rows + [out]:
+        a.free()
+    return words
+
+
+@pytest.mark.parametrize("lead", (64, 65, 66, 67))
+def test_nothing_outside_the_rows_is_written(lead):
+    """a guard band of sentinel values on both sides of `out`, which is 16-byte aligned (lead 64: 16-byte stores) or 4, 8, 12
+    bytes past such a boundary (element by element): the same values, the bands untouched"""
+    from bxmi import summary
+
+    tracks, track_of, starts, ends, (want, offsets) = M.ragged_case()
+    dev = [summary.SpanTrack(*t) for t in tracks]
+    # (one row more, naming the track behind the last: the device form cannot refuse it, it is a NaN row)
+    words = arrays_dev_raw(dev, np.append(track_of, len(dev)).astype(np.int32), np.append(starts, 3).astype(np.int32),
+                           np.append(offsets, offsets[-1] + 9), lead)
+    total = len(want) + 9
+    assert (words[:lead] == SENTINEL).all() and (words[lead + total:] == SENTINEL).all()
+    M.assert_same(words[lead:lead + len(want)].view(np.float32), want, lead)
+    assert (words[lead + len(want):lead + total] == M.NAN_BITS).all()
+    for t in dev:
+        t.close()
+
+
+def test_no_rows_and_bad_arguments():
+    from bxmi import _ffi as ffi
+    from bxmi import summary
+
+    t = summary.SpanTrack([0, 10], [10, 20], [1.0, 2.0])
+    values, offsets = summary.arrays([t], [], [], [])
+    assert values.shape == (0,) and values.dtype == np.float32 and offsets.tolist() == [0]
+    assert summary.matrix([t], [], [], 7).shape == (0, 7)
+    values, offsets = summary.arrays([], [-1, -1], [0, 5], [3, 5])  # no tracks at all: NaN rows
+    assert offsets.tolist() == [0, 3, 3] and (values.view(np.uint32) == M.NAN_BITS).all()
+    assert summary.matrix([t], [0], [8], 4).tolist() == [[1.0, 1.0, 2.0, 2.0]]
+    for call, word in ((lambda: summary.matrix([t], [0], [0], 0), "width"), (lambda: summary.matrix([t], [1], [0], 2), "track_of[0]"),
+                       (lambda: summary.arrays([], [0], [0], [4]), "track_of[0]")):
+        with pytest.raises(ffi.BxmiError) as e:
+            call()
+        assert e.value.code == EINVAL and word in str(e.value), str(e.value)
+    with pytest.raises(ValueError):
+        summary.arrays([t], [0, 0], [0], [4])
+    t.close()
+
+
+# ------------------------------------------------------------ device entry point --
+def test_arrays_dev_and_matrix_dev_on_torch_tensors():
+    """arrays_dev / matrix_dev on torch tensors -- the ragged edge case and two matrix widths on input slices that start 4 bytes
+    into their allocation, torch's current stream and a stream of the caller's, matrix_dev into a tensor sliced off a 16-byte
+    boundary, rows the device form cannot refuse, an empty batch -- in a process of its own: torch brings its own HIP runtime,
+    which the rest of the suite keeps out of the test process"""
+    code = r'''
+import sys, numpy as np, torch
+sys.path.insert(0, sys.argv[1])
+sys.path.insert(0, sys.argv[2])
+import arrays_model as M
+from bxmi import summary
+
+def dev_i32(a, pad):
+    return torch.from_numpy(np.concatenate([[7] * pad, a]).astype(np.int32)).cuda()[pad:]
+
+tracks, track_of, starts, ends, (want, want_offsets) = M.ragged_case()
+dev = [summary.SpanTrack(*t) for t in tracks]
+d = [dev_i32(track_of, 1), dev_i32(starts, 3), dev_i32(ends, 1)]
+assert all(x.data_ptr() % 16 for x in d)
+values, offsets = summary.arrays_dev(dev, *d)
+torch.cuda.synchronize()
+assert values.is_cuda and values.dtype == torch.float32 and offsets.dtype == torch.int64
+assert np.array_equal(offsets.cpu().numpy(), want_offsets)
+M.assert_same(values.cpu().numpy(), want, "arrays_dev, current stream")
+side = torch.cuda.Stream()
+with torch.cuda.stream(side):
+    values, _ = summary.arrays_dev(dev, *d)
+side.synchronize()
+M.assert_same(values.cpu().numpy(), want, "arrays_dev, side stream")
+
+for width in (3, M.TILE + 1):
+    tracks_m, track_of_m, starts_m, want_m = M.matrix_case(width)
+    assert tracks_m is tracks
+    rows = [dev_i32(track_of_m, 1), dev_i32(starts_m, 2)]
+    got = summary.matrix_dev(dev, *rows, width)
+    torch.cuda.synchronize()
+    assert got.is_cuda and tuple(got.shape) == want_m.shape
+    M.assert_same(got.cpu().numpy(), want_m, ("matrix_dev", width))
+    M.assert_same(summary.matrix(dev, track_of_m, starts_m, width), want_m, ("matrix", width))
+    # on a side stream, into a tensor sliced off a 16-byte boundary, sentinels around it
+    n = len(track_of_m)
+    for lead in (1, 2, 3, 4):
+        whole = torch.full((lead + n * width + 5,), -7.0, dtype=torch.float32, device="cuda")
+        out = whole[lead:lead + n * width].view(n, width)
+        assert (out.data_ptr() % 16 != 0) == (lead != 4)
+        torch.cuda.synchronize()
+        res = summary.matrix_dev(dev, *rows, width, stream=side.cuda_stream, out=out)
+        side.synchronize()
+        assert res is out
+        M.assert_same(out.cpu().numpy(), want_m, ("matrix_dev into a slice", width, lead))
+        edge = whole.cpu().numpy()
+        assert (edge[:lead] == -7.0).all() and (edge[lead + n * width:] == -7.0).all()
+
+# entries the device form cannot refuse are NaN rows: a track index beyond the list
+odd = summary.matrix_dev(dev, dev_i32(np.array([len(dev), 2, -3]), 0), dev_i32(np.array([3, 3, 3]), 0), 6, stream=side.cuda_stream)
+side.synchronize()
+odd = odd.cpu().numpy()
+nan_row = np.full(6, M.NAN_BITS, dtype=np.uint32).view(np.float32)
+M.assert_same(odd, np.stack([nan_row, M.region(tracks[2], 3, 9), nan_row]), "rows without a track")
+values, offsets = summary.arrays_dev(dev, d[0][:0], d[1][:0], d[2][:0], stream=side.cuda_stream)
+assert tuple(values.shape) == (0,) and offsets.tolist() == [0]
+assert tuple(summary.matrix_dev(dev, d[0][:0], d[1][:0], 5).shape) == (0, 5)
+for t in dev:
+    t.close()
+print("arrays_dev ok")
+'''
+    p = subprocess.run([sys.executable, "-c", code, os.path.join(ROOT, "bx-python_amd"), os.path.join(ROOT, "tests")],
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "arrays_dev ok" in p.stdout, (p.stdout[-1000:], p.stderr[-3000:])
