@@ -40,31 +40,27 @@ from ._ffi import as_i32, call, ptr
 Summary = collections.namedtuple("Summary", "valid_count min_val max_val sum_data sum_squares")
 
 
-class SpanTrack:
-    """(start, end, value) items of one chromosome on the device, in the order given (file order).  `ordered`: starts and ends are
-    both non-decreasing, which every real bigWig is; other tracks are summarized by a slow general path."""
+class _Track:
+    """What the three kinds of track share: the handle `_h` that `_create` makes and `close` (or the collector) gives back to
+    the library's `_destroy`."""
 
-    def __init__(self, starts, ends, values):
-        _ffi.require_gpu()
-        s, e = as_i32(starts), as_i32(ends)
-        v = np.ascontiguousarray(values, dtype=np.float32)
-        if not (s.shape == e.shape == v.shape) or s.ndim != 1:
-            raise ValueError("starts, ends and values must be 1-d arrays of equal length")
+    _destroy = None  # the C symbol
+    _h = None
+
+    def _create(self, symbol, *args):
         h = C.c_void_p()
-        call("bxmi_spans_create", ptr(s), ptr(e), ptr(v), len(s), C.byref(h))
+        call(symbol, *args, C.byref(h))
         self._h = h
-        n, ordered = C.c_int64(0), C.c_int(0)
-        call("bxmi_spans_info", self._h, C.byref(n), C.byref(ordered))
-        self.n, self.ordered = n.value, bool(ordered.value)
 
-    @classmethod
-    def from_bigwig(cls, path):
-        """{chrom: SpanTrack} of a bigWig file, chromosomes without data included."""
-        return {chrom: cls(*spans) for chrom, spans in bigwig.read_spans_file(path).items()}
+    def _info(self, symbol, *ctypes):
+        """the values `symbol` reports about the handle"""
+        out = [c(0) for c in ctypes]
+        call(symbol, self._h, *[C.byref(o) for o in out])
+        return [o.value for o in out]
 
     def close(self):
         if self._h is not None:
-            _ffi.load().bxmi_spans_destroy(self._h)
+            getattr(_ffi.load(), self._destroy)(self._h)
             self._h = None
 
     def __del__(self):
@@ -74,19 +70,64 @@ class SpanTrack:
             pass
 
 
+def _rows_i32(names, *columns):
+    """the columns of a batch as int32 arrays: 1-d and of one length, or ValueError naming them"""
+    cols = [as_i32(c) for c in columns]
+    if cols[0].ndim != 1 or any(c.shape != cols[0].shape for c in cols):
+        raise ValueError("%s must be 1-d arrays of equal length" % names)
+    return cols
+
+
+def _summarize(symbol, tracks, track_of, starts, ends, size):
+    """the host form of every kind: `symbol` is the C entry point"""
+    _ffi.require_gpu()
+    tracks = list(tracks)
+    t, s, e = _rows_i32("track_of, starts and ends", track_of, starts, ends)
+    size = int(size)
+    out = [np.empty((len(t), max(size, 0)), dtype=np.float64) for _ in range(5)]
+    call(symbol, _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), ptr(e), len(t), size, *[ptr(a) for a in out])
+    return Summary(*out)
+
+
+def _summarize_dev(symbol, name, tracks, track_of, starts, ends, size, stream):
+    """the device form of every kind: `name` is the public function's, for _ffi.device_args' messages"""
+    import torch
+
+    tracks = list(tracks)
+    (track_of, starts, ends), n, dev, stream = _ffi.device_args(name + "_dev", name, ("track_of", "starts", "ends"), (track_of, starts, ends), stream)
+    size = int(size)
+    out = [torch.empty((n, max(size, 0)), dtype=torch.float64, device=dev) for _ in range(5)]
+    call(symbol, _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), ends.data_ptr(), n, size, *[a.data_ptr() for a in out], stream)
+    return Summary(*out)
+
+
+class SpanTrack(_Track):
+    """(start, end, value) items of one chromosome on the device, in the order given (file order).  `ordered`: starts and ends are
+    both non-decreasing, which every real bigWig is; other tracks are summarized by a slow general path."""
+
+    _destroy = "bxmi_spans_destroy"
+
+    def __init__(self, starts, ends, values):
+        _ffi.require_gpu()
+        s, e = as_i32(starts), as_i32(ends)
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        if not (s.shape == e.shape == v.shape) or s.ndim != 1:
+            raise ValueError("starts, ends and values must be 1-d arrays of equal length")
+        self._create("bxmi_spans_create", ptr(s), ptr(e), ptr(v), len(s))
+        n, ordered = self._info("bxmi_spans_info", C.c_int64, C.c_int)
+        self.n, self.ordered = n, bool(ordered)
+
+    @classmethod
+    def from_bigwig(cls, path):
+        """{chrom: SpanTrack} of a bigWig file, chromosomes without data included."""
+        return {chrom: cls(*spans) for chrom, spans in bigwig.read_spans_file(path).items()}
+
+
 def summarize(tracks, track_of, starts, ends, size):
     """summarize_from_full of regions [starts[i], ends[i]) of tracks[track_of[i]], `size` bins each -> Summary of [n, size] float64
     numpy arrays.  track_of[i] < 0 (unknown chromosome) or starts[i] >= ends[i] -- where the reference returns None -- gives an
     empty row: 0, +inf, -inf, 0, 0.  A negative coordinate or size < 1 raises BxmiError (EINVAL)."""
-    _ffi.require_gpu()
-    tracks = list(tracks)
-    t, s, e = as_i32(track_of), as_i32(starts), as_i32(ends)
-    if not (t.shape == s.shape == e.shape) or t.ndim != 1:
-        raise ValueError("track_of, starts and ends must be 1-d arrays of equal length")
-    size = int(size)
-    out = [np.empty((len(t), max(size, 0)), dtype=np.float64) for _ in range(5)]
-    call("bxmi_spans_summarize", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), ptr(e), len(t), size, *[ptr(a) for a in out])
-    return Summary(*out)
+    return _summarize("bxmi_spans_summarize", tracks, track_of, starts, ends, size)
 
 
 def summarize_dev(tracks, track_of, starts, ends, size, stream=None):
@@ -96,23 +137,7 @@ def summarize_dev(tracks, track_of, starts, ends, size, stream=None):
     is rewritten by every call on that call's stream: ONE summary call at a time per process may be in flight on the device.  Calls
     on one stream follow each other; before a call on another stream, or with other tracks from another thread, wait for the one
     before it."""
-    import torch
-
-    tracks = list(tracks)
-    (track_of, starts, ends), n, dev, stream = _ffi.device_args("summarize_dev", "summarize", ("track_of", "starts", "ends"),
-                                                                (track_of, starts, ends), stream)
-    size = int(size)
-    out = [torch.empty((n, max(size, 0)), dtype=torch.float64, device=dev) for _ in range(5)]
-    call("bxmi_spans_summarize_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), ends.data_ptr(), n, size,
-         *[a.data_ptr() for a in out], stream)
-    return Summary(*out)
-
-
-def _rows_i32(track_of, starts, names):
-    t, s = as_i32(track_of), as_i32(starts)
-    if t.shape != s.shape or t.ndim != 1:
-        raise ValueError("%s must be 1-d arrays of equal length" % names)
-    return t, s
+    return _summarize_dev("bxmi_spans_summarize_dev", "summarize", tracks, track_of, starts, ends, size, stream)
 
 
 def arrays(tracks, track_of, starts, ends):
@@ -123,10 +148,7 @@ def arrays(tracks, track_of, starts, ends):
     of one base and rows of millions cost their bases."""
     _ffi.require_gpu()
     tracks = list(tracks)
-    t, s = _rows_i32(track_of, starts, "track_of, starts and ends")
-    e = as_i32(ends)
-    if e.shape != s.shape:
-        raise ValueError("track_of, starts and ends must be 1-d arrays of equal length")
+    t, s, e = _rows_i32("track_of, starts and ends", track_of, starts, ends)
     offsets = np.zeros(len(s) + 1, dtype=np.int64)
     np.cumsum(np.maximum(e.astype(np.int64) - s.astype(np.int64), 0), out=offsets[1:])
     values = np.empty(int(offsets[-1]), dtype=np.float32)
@@ -139,7 +161,7 @@ def matrix(tracks, track_of, win_starts, width):
     `arrays`.  width < 1 raises BxmiError (EINVAL)."""
     _ffi.require_gpu()
     tracks = list(tracks)
-    t, s = _rows_i32(track_of, win_starts, "track_of and win_starts")
+    t, s = _rows_i32("track_of and win_starts", track_of, win_starts)
     width = int(width)
     out = np.empty((len(t), max(width, 0)), dtype=np.float32)
     call("bxmi_spans_arrays", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), len(t), width, None, out.size, ptr(out))
@@ -184,38 +206,24 @@ def matrix_dev(tracks, track_of, win_starts, width, stream=None, out=None):
     return out
 
 
-class BedTrack:
+class BedTrack(_Track):
     """(start, end) records of one chromosome of a bigBed file on the device, in the order given (file order); no values: every
     record counts 1.  `sorted`: the starts never descend, which holds in every real bigBed whatever its ends do; other tracks are
     summarized by a slow general walk."""
 
+    _destroy = "bxmi_beds_destroy"
+
     def __init__(self, starts, ends):
         _ffi.require_gpu()
-        s, e = as_i32(starts), as_i32(ends)
-        if s.shape != e.shape or s.ndim != 1:
-            raise ValueError("starts and ends must be 1-d arrays of equal length")
-        h = C.c_void_p()
-        call("bxmi_beds_create", ptr(s), ptr(e), len(s), C.byref(h))
-        self._h = h
-        n, is_sorted = C.c_int64(0), C.c_int(0)
-        call("bxmi_beds_info", self._h, C.byref(n), C.byref(is_sorted))
-        self.n, self.sorted = n.value, bool(is_sorted.value)
+        s, e = _rows_i32("starts and ends", starts, ends)
+        self._create("bxmi_beds_create", ptr(s), ptr(e), len(s))
+        n, is_sorted = self._info("bxmi_beds_info", C.c_int64, C.c_int)
+        self.n, self.sorted = n, bool(is_sorted)
 
     @classmethod
     def from_bigbed(cls, path):
         """{chrom: BedTrack} of a bigBed file, chromosomes without records included."""
         return {chrom: cls(s, e) for chrom, (s, e, _) in bigbed.read_items_file(path).items()}
-
-    def close(self):
-        if self._h is not None:
-            _ffi.load().bxmi_beds_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def summarize_beds(tracks, track_of, starts, ends, size):
@@ -223,31 +231,14 @@ def summarize_beds(tracks, track_of, starts, ends, size):
     Summary of [n, size] float64 numpy arrays: what `summarize` gives for the same records as items of value 1.  valid_count is
     the rounded coverage chain, sum_data and sum_squares the chain itself, min_val and max_val 1 where a record overlaps the bin
     (+inf / -inf elsewhere).  Empty rows and errors as `summarize`."""
-    _ffi.require_gpu()
-    tracks = list(tracks)
-    t, s, e = as_i32(track_of), as_i32(starts), as_i32(ends)
-    if not (t.shape == s.shape == e.shape) or t.ndim != 1:
-        raise ValueError("track_of, starts and ends must be 1-d arrays of equal length")
-    size = int(size)
-    out = [np.empty((len(t), max(size, 0)), dtype=np.float64) for _ in range(5)]
-    call("bxmi_beds_summarize", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), ptr(e), len(t), size, *[ptr(a) for a in out])
-    return Summary(*out)
+    return _summarize("bxmi_beds_summarize", tracks, track_of, starts, ends, size)
 
 
 def summarize_beds_dev(tracks, track_of, starts, ends, size, stream=None):
     """`summarize_beds` on device arrays, as `summarize_dev`: int32 torch tensors on the GPU in, float64 tensors out, queued on
     torch's current stream (or `stream`).  It shares the library's track table with the other summaries: one summary call of any
     kind at a time per process may be in flight."""
-    import torch
-
-    tracks = list(tracks)
-    (track_of, starts, ends), n, dev, stream = _ffi.device_args("summarize_beds_dev", "summarize_beds", ("track_of", "starts", "ends"),
-                                                                (track_of, starts, ends), stream)
-    size = int(size)
-    out = [torch.empty((n, max(size, 0)), dtype=torch.float64, device=dev) for _ in range(5)]
-    call("bxmi_beds_summarize_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), ends.data_ptr(), n, size,
-         *[a.data_ptr() for a in out], stream)
-    return Summary(*out)
+    return _summarize_dev("bxmi_beds_summarize_dev", "summarize_beds", tracks, track_of, starts, ends, size, stream)
 
 
 def stats(summary, starts, ends, size):
@@ -282,10 +273,12 @@ def stats(summary, starts, ends, size):
     return mean, coverage, std_dev
 
 
-class ZoomTrack:
+class ZoomTrack(_Track):
     """One chromosome's part of one zoom level on the device: `arrays` is a bxmi.bigwig.ZoomArrays (records in load order and the
     leaf entries that decide what a region loads).  Only an ORDERED level is accepted (bxmi.bigwig.ordered_level): anything else
     raises BxmiError (EINVAL) naming the condition."""
+
+    _destroy = "bxmi_zoom_destroy"
 
     def __init__(self, arrays):
         _ffi.require_gpu()
@@ -296,12 +289,8 @@ class ZoomTrack:
         first = np.ascontiguousarray(a.leaf_first, dtype=np.int64)
         if any(x.ndim != 1 or x.shape != rec[0].shape for x in rec) or leaf[0].shape != leaf[1].shape or first.shape != (len(leaf[0]) + 1,):
             raise ValueError("seven record arrays of one length, leaf_lo and leaf_hi of one length, leaf_first one longer")
-        h = C.c_void_p()
-        call("bxmi_zoom_create", *[ptr(x) for x in rec], len(rec[0]), ptr(leaf[0]), ptr(leaf[1]), ptr(first), len(leaf[0]), C.byref(h))
-        self._h = h
-        n, n_leaves = C.c_int64(0), C.c_int64(0)
-        call("bxmi_zoom_info", self._h, C.byref(n), C.byref(n_leaves))
-        self.n, self.n_leaves = n.value, n_leaves.value
+        self._create("bxmi_zoom_create", *[ptr(x) for x in rec], len(rec[0]), ptr(leaf[0]), ptr(leaf[1]), ptr(first), len(leaf[0]))
+        self.n, self.n_leaves = self._info("bxmi_zoom_info", C.c_int64, C.c_int64)
 
     @classmethod
     def from_bigwig(cls, path):
@@ -309,48 +298,20 @@ class ZoomTrack:
         levels = bigwig.read_zoom_file(path)
         return {chrom: [cls(per[chrom]) for _, per in levels] for chrom in (levels[0][1] if levels else bigwig.chroms(path))}
 
-    def close(self):
-        if self._h is not None:
-            _ffi.load().bxmi_zoom_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def summarize_zoom(tracks, track_of, starts, ends, size):
     """ZoomLevel._summarize of regions [starts[i], ends[i]) from the ZoomTrack tracks[track_of[i]], `size` bins each -> Summary of
     [n, size] float64 numpy arrays; valid_count is not a whole number here.  A bin without a record left is 0, NaN, NaN, 0, 0.
     track_of[i] < 0 or starts[i] >= ends[i] -- where the reference returns None -- gives the empty row of `summarize`: 0, +inf,
     -inf, 0, 0.  A negative coordinate or size < 1 raises BxmiError (EINVAL)."""
-    _ffi.require_gpu()
-    tracks = list(tracks)
-    t, s, e = as_i32(track_of), as_i32(starts), as_i32(ends)
-    if not (t.shape == s.shape == e.shape) or t.ndim != 1:
-        raise ValueError("track_of, starts and ends must be 1-d arrays of equal length")
-    size = int(size)
-    out = [np.empty((len(t), max(size, 0)), dtype=np.float64) for _ in range(5)]
-    call("bxmi_zoom_summarize", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), ptr(e), len(t), size, *[ptr(a) for a in out])
-    return Summary(*out)
+    return _summarize("bxmi_zoom_summarize", tracks, track_of, starts, ends, size)
 
 
 def summarize_zoom_dev(tracks, track_of, starts, ends, size, stream=None):
     """`summarize_zoom` on device arrays, as `summarize_dev`: int32 torch tensors on the GPU in, float64 tensors out, queued on
     torch's current stream (or `stream`).  It shares the library's track table with `summarize_dev`: one summary call of either kind
     at a time per process may be in flight."""
-    import torch
-
-    tracks = list(tracks)
-    (track_of, starts, ends), n, dev, stream = _ffi.device_args("summarize_zoom_dev", "summarize_zoom", ("track_of", "starts", "ends"),
-                                                                (track_of, starts, ends), stream)
-    size = int(size)
-    out = [torch.empty((n, max(size, 0)), dtype=torch.float64, device=dev) for _ in range(5)]
-    call("bxmi_zoom_summarize_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), ends.data_ptr(), n, size,
-         *[a.data_ptr() for a in out], stream)
-    return Summary(*out)
+    return _summarize_dev("bxmi_zoom_summarize_dev", "summarize_zoom", tracks, track_of, starts, ends, size, stream)
 
 
 def pick_levels(reductions, starts, ends, size):

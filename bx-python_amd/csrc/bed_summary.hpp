@@ -43,7 +43,7 @@ namespace bxmi {
 constexpr int BD_CHUNK = 256;   // records staged in LDS at a time (3 KiB per workgroup); chunks are aligned to multiples of it
 constexpr int BD_THREADS = 64;  // one wave per region
 
-// which lanes of the wave hold `p` (the host build of tests/cpp/bed_summary_kernel_host.cpp supplies its own)
+// which lanes of the wave hold `p` (the host build of tests/cpp/kernel_host.hpp supplies its own)
 #ifndef BD_BALLOT
 #define BD_BALLOT(p) __ballot(p)
 #endif
@@ -69,15 +69,11 @@ inline int bd_build_reach(const int32_t *start, const int32_t *end, int64_t n, i
     return sorted;
 }
 
-// One record against one bin [b0, b1) of the region [s, e): sm_item's weight (the ov == n shortcut included) for a value of 1.
+// One record against one bin [b0, b1) of the region [s, e): an item of value 1, by the weight of summary.hpp.
 __device__ __forceinline__ void bd_item(double &acc, int st, int en, int s, int e, int b0, int b1)
 {
-    const int cs = st > s ? st : s, ce = en < e ? en : e;
-    if (cs >= ce) return;
-    const int ov = (ce < b1 ? ce : b1) - (cs > b0 ? cs : b0);
-    if (ov <= 0) return;
-    const int n = ce - cs;
-    acc += ov == n ? (double)n : (double)n * ((double)ov / (double)n);
+    double w;
+    if (sm_weight(w, st, en, s, e, b0, b1)) acc += w;
 }
 
 __global__ __launch_bounds__(BD_THREADS) void bd_summary_kernel(const BdTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
@@ -88,13 +84,10 @@ __global__ __launch_bounds__(BD_THREADS) void bd_summary_kernel(const BdTrack *_
     __shared__ int32_t l_st[BD_CHUNK], l_en[BD_CHUNK], l_creach[BD_CHUNK];
     const int64_t row = blockIdx.x;
     const int lane = (int)threadIdx.x;
-    const int t = track_of[row], s = start[row], e = end[row];
-    const bool has = t >= 0 && t < n_tracks && s >= 0 && s < e;
-    const BdTrack tr = table[has ? t : n_tracks];  // (the spare entry: no records)
+    const auto [tr, s, e, has, step] = sm_row(table, n_tracks, track_of, start, end, row, size);
     const int32_t BX_GLOBAL *t_st = as_global(tr.start), *t_en = as_global(tr.end);
     const int32_t BX_GLOBAL *t_reach = as_global(tr.reach), *t_creach = as_global(tr.creach);
     const bool sorted = tr.sorted != 0;
-    const int step = has ? (e - s) / size : 0;
     // the region's records: [lo, hi)
     int64_t lo = 0, hi = 0;
     if (step > 0 && tr.n > 0) {
@@ -105,12 +98,8 @@ __global__ __launch_bounds__(BD_THREADS) void bd_summary_kernel(const BdTrack *_
         }
     }
     const int64_t out0 = row * (int64_t)size;
-    for (int64_t g0 = 0; g0 < size; g0 += 64) {  // (64-bit: g0 + 64 may pass 2^31 for a size near it)
-        const int64_t g1 = g0 + 64 < size ? g0 + 64 : size;  // bins [g0, g1)
-        const int64_t bin = g0 + lane;
-        const bool ok = bin < g1;
-        // (s + step * bin <= e for bin <= size: the result fits an int)
-        const int b0 = ok ? (int)(s + (int64_t)step * bin) : 0, b1 = ok ? b0 + step : 0;
+    for (int64_t g0 = 0; g0 < size; g0 += 64) {
+        const auto [g1, bin, ok, b0, b1] = sm_group(g0, size, lane, s, step);  // bins [g0, g1), this lane's [b0, b1)
         double acc = 0.0;
         if (hi > lo) {
             const int gb0 = (int)(s + (int64_t)step * g0);  // the group's first base

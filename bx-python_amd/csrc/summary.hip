@@ -8,6 +8,7 @@
 // __dadd_rn, is what guarantees it: it covers every expression below, including the ones added later.
 #pragma clang fp contract(off)
 
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -21,43 +22,85 @@
 
 using namespace bxmi;
 
+// Every kind of handle names what its summaries run on: Entry (what the kernel reads for a track; entry() makes it, and an empty
+// handle's entry() is the SPARE entry of the table), the kernel and its thread count.  The code below the creates is written once
+// for all kinds and takes everything from the handle type.
 struct bxmi_spans {
+    using Entry = SmTrack;
+    static constexpr auto kernel = sm_summary_kernel;
+    static constexpr int THREADS = SM_THREADS;
     int64_t n = 0;
     int ordered = 1;
     DevBuf start, end, value;
-    SmTrack entry() const { return SmTrack{start.as<int32_t>(), end.as<int32_t>(), value.as<float>(), n, ordered}; }
+    Entry entry() const { return SmTrack{start.as<int32_t>(), end.as<int32_t>(), value.as<float>(), n, ordered}; }
 };
+
+// One chromosome's part of one zoom level (zoom_summary.hpp): seven record arrays and three leaf arrays.
+struct bxmi_zoom {
+    using Entry = ZmTrack;
+    static constexpr auto kernel = zm_summary_kernel;
+    static constexpr int THREADS = ZM_THREADS;
+    int64_t n = 0, n_leaves = 0;
+    DevBuf start, end, valid, mn, mx, sum, sumsq, leaf_lo, leaf_hi, leaf_first;
+    Entry entry() const
+    {
+        return ZmTrack{start.as<int32_t>(), end.as<int32_t>(), valid.as<uint32_t>(), mn.as<float>(), mx.as<float>(), sum.as<float>(), sumsq.as<float>(),
+                       leaf_lo.as<int32_t>(), leaf_hi.as<int32_t>(), leaf_first.as<int64_t>(), n, n_leaves};
+    }
+};
+
+// One chromosome's bigBed records (bed_summary.hpp): starts and ends in file order, and the two running maxima of the ends.
+struct bxmi_beds {
+    using Entry = BdTrack;
+    static constexpr auto kernel = bd_summary_kernel;
+    static constexpr int THREADS = BD_THREADS;
+    int64_t n = 0;
+    int sorted = 1;
+    DevBuf start, end, reach, creach;
+    Entry entry() const { return BdTrack{start.as<int32_t>(), end.as<int32_t>(), reach.as<int32_t>(), creach.as<int32_t>(), n, sorted}; }
+};
+
+// `what` ("item", "record", "region") i = [start[i], end[i]): none may have a negative coordinate
+static int no_negative(const char *who, const char *what, const int32_t *start, const int32_t *end, int64_t n)
+{
+    for (int64_t i = 0; i < n; i++)
+        if (start[i] < 0 || end[i] < 0)
+            return fail(BXMI_EINVAL, "%s: %s %lld = [%d, %d) has a negative coordinate", who, what, (long long)i, (int)start[i], (int)end[i]);
+    return BXMI_OK;
+}
+
+// A new handle's arrays: every buffer is reserved (never zero bytes) and filled from the host; the first failure ends it.
+struct Upload {
+    DevBuf *to;
+    const void *from;
+    size_t bytes;
+};
+static int upload(const char *who, std::initializer_list<Upload> copies)
+{
+    for (const Upload &c : copies) {
+        BXMI_TRY(c.to->reserve(c.bytes ? c.bytes : 8));
+        if (c.bytes == 0) continue;
+        const hipError_t e = hipMemcpy(c.to->p, c.from, c.bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(BXMI_EHIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    return BXMI_OK;
+}
 
 extern "C" int bxmi_spans_create(const int32_t *start, const int32_t *end, const float *value, int64_t n, bxmi_spans_t **out)
 {
-    if (!out) return fail(BXMI_EINVAL, "bxmi_spans_create: out is NULL");
+    const char *who = "bxmi_spans_create";
+    if (!out) return fail(BXMI_EINVAL, "%s: out is NULL", who);
     *out = nullptr;
-    if (n < 0 || (n > 0 && (!start || !end || !value))) return fail(BXMI_EINVAL, "bxmi_spans_create: bad arguments");
-    int ordered = 1;
-    for (int64_t i = 0; i < n; i++) {
-        if (start[i] < 0 || end[i] < 0)
-            return fail(BXMI_EINVAL, "bxmi_spans_create: item %lld = [%d, %d) has a negative coordinate", (long long)i, (int)start[i], (int)end[i]);
-        if (i > 0 && (start[i] < start[i - 1] || end[i] < end[i - 1])) ordered = 0;
-    }
-    bxmi_spans *h = new (std::nothrow) bxmi_spans();
-    if (!h) return fail(BXMI_ENOMEM, "bxmi_spans_create: host allocation failed");
+    if (n < 0 || (n > 0 && (!start || !end || !value))) return fail(BXMI_EINVAL, "%s: bad arguments", who);
+    BXMI_TRY(no_negative(who, "item", start, end, n));
+    std::unique_ptr<bxmi_spans> h(new (std::nothrow) bxmi_spans());
+    if (!h) return fail(BXMI_ENOMEM, "%s: host allocation failed", who);
     h->n = n;
-    h->ordered = ordered;
+    for (int64_t i = 1; i < n; i++)
+        if (start[i] < start[i - 1] || end[i] < end[i - 1]) h->ordered = 0;
     const size_t bytes = (size_t)n * 4;
-    int rc = h->start.reserve(bytes ? bytes : 4);
-    if (rc == BXMI_OK) rc = h->end.reserve(bytes ? bytes : 4);
-    if (rc == BXMI_OK) rc = h->value.reserve(bytes ? bytes : 4);
-    if (rc == BXMI_OK && n > 0) {
-        hipError_t e = hipMemcpy(h->start.p, start, bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(h->end.p, end, bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(h->value.p, value, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) rc = fail(BXMI_EHIP, "bxmi_spans_create: %s", hipGetErrorString(e));
-    }
-    if (rc != BXMI_OK) {
-        delete h;
-        return rc;
-    }
-    *out = h;
+    BXMI_TRY(upload(who, {{&h->start, start, bytes}, {&h->end, end, bytes}, {&h->value, value, bytes}}));
+    *out = h.release();
     return BXMI_OK;
 }
 
@@ -75,17 +118,6 @@ extern "C" int bxmi_spans_info(const bxmi_spans_t *h, int64_t *n, int *ordered)
     return BXMI_OK;
 }
 
-// One chromosome's part of one zoom level (zoom_summary.hpp): seven record arrays and three leaf arrays.
-struct bxmi_zoom {
-    int64_t n = 0, n_leaves = 0;
-    DevBuf start, end, valid, mn, mx, sum, sumsq, leaf_lo, leaf_hi, leaf_first;
-    ZmTrack entry() const
-    {
-        return ZmTrack{start.as<int32_t>(), end.as<int32_t>(), valid.as<uint32_t>(), mn.as<float>(), mx.as<float>(), sum.as<float>(), sumsq.as<float>(),
-                       leaf_lo.as<int32_t>(), leaf_hi.as<int32_t>(), leaf_first.as<int64_t>(), n, n_leaves};
-    }
-};
-
 extern "C" int bxmi_zoom_create(const int32_t *start, const int32_t *end, const uint32_t *valid, const float *min, const float *max, const float *sum,
                                 const float *sumsq, int64_t n, const int32_t *leaf_lo, const int32_t *leaf_hi, const int64_t *leaf_first,
                                 int64_t n_leaves, bxmi_zoom_t **out)
@@ -96,10 +128,9 @@ extern "C" int bxmi_zoom_create(const int32_t *start, const int32_t *end, const 
     if (n < 0 || n_leaves < 0 || !leaf_first || (n > 0 && (!start || !end || !valid || !min || !max || !sum || !sumsq)) ||
         (n_leaves > 0 && (!leaf_lo || !leaf_hi)))
         return fail(BXMI_EINVAL, "%s: bad arguments", who);
+    BXMI_TRY(no_negative(who, "record", start, end, n));
     // an ORDERED level, and leaves that partition the records: what the kernel's searches and its indexes rest on
     for (int64_t i = 0; i < n; i++) {
-        if (start[i] < 0 || end[i] < 0)
-            return fail(BXMI_EINVAL, "%s: record %lld = [%d, %d) has a negative coordinate", who, (long long)i, (int)start[i], (int)end[i]);
         if (start[i] > end[i]) return fail(BXMI_EINVAL, "%s: record %lld = [%d, %d) has start > end", who, (long long)i, (int)start[i], (int)end[i]);
         if (i > 0 && start[i] < start[i - 1])
             return fail(BXMI_EINVAL, "%s: record starts are not non-decreasing (record %lld: %d after %d)", who, (long long)i, (int)start[i], (int)start[i - 1]);
@@ -118,28 +149,15 @@ extern "C" int bxmi_zoom_create(const int32_t *start, const int32_t *end, const 
         if (k > 0 && leaf_hi[k] < leaf_hi[k - 1])
             return fail(BXMI_EINVAL, "%s: leaf_hi is not non-decreasing (leaf %lld: %d after %d)", who, (long long)k, (int)leaf_hi[k], (int)leaf_hi[k - 1]);
     }
-    bxmi_zoom *h = new (std::nothrow) bxmi_zoom();
+    std::unique_ptr<bxmi_zoom> h(new (std::nothrow) bxmi_zoom());
     if (!h) return fail(BXMI_ENOMEM, "%s: host allocation failed", who);
     h->n = n;
     h->n_leaves = n_leaves;
-    struct Copy { DevBuf *to; const void *from; size_t bytes; };
     const size_t rec = (size_t)n * 4, leaf = (size_t)n_leaves * 4;
-    const Copy copies[] = {{&h->start, start, rec}, {&h->end, end, rec}, {&h->valid, valid, rec}, {&h->mn, min, rec}, {&h->mx, max, rec},
-                           {&h->sum, sum, rec}, {&h->sumsq, sumsq, rec}, {&h->leaf_lo, leaf_lo, leaf}, {&h->leaf_hi, leaf_hi, leaf},
-                           {&h->leaf_first, leaf_first, (size_t)(n_leaves + 1) * 8}};
-    int rc = BXMI_OK;
-    for (const Copy &c : copies) {
-        if (rc == BXMI_OK) rc = c.to->reserve(c.bytes ? c.bytes : 8);
-        if (rc == BXMI_OK && c.bytes > 0) {
-            const hipError_t e = hipMemcpy(c.to->p, c.from, c.bytes, hipMemcpyHostToDevice);
-            if (e != hipSuccess) rc = fail(BXMI_EHIP, "%s: %s", who, hipGetErrorString(e));
-        }
-    }
-    if (rc != BXMI_OK) {
-        delete h;
-        return rc;
-    }
-    *out = h;
+    BXMI_TRY(upload(who, {{&h->start, start, rec}, {&h->end, end, rec}, {&h->valid, valid, rec}, {&h->mn, min, rec}, {&h->mx, max, rec},
+                          {&h->sum, sum, rec}, {&h->sumsq, sumsq, rec}, {&h->leaf_lo, leaf_lo, leaf}, {&h->leaf_hi, leaf_hi, leaf},
+                          {&h->leaf_first, leaf_first, (size_t)(n_leaves + 1) * 8}}));
+    *out = h.release();
     return BXMI_OK;
 }
 
@@ -157,47 +175,21 @@ extern "C" int bxmi_zoom_info(const bxmi_zoom_t *h, int64_t *n, int64_t *n_leave
     return BXMI_OK;
 }
 
-// One chromosome's bigBed records (bed_summary.hpp): starts and ends in file order, and the two running maxima of the ends.
-struct bxmi_beds {
-    int64_t n = 0;
-    int sorted = 1;
-    DevBuf start, end, reach, creach;
-    BdTrack entry() const { return BdTrack{start.as<int32_t>(), end.as<int32_t>(), reach.as<int32_t>(), creach.as<int32_t>(), n, sorted}; }
-};
-
 extern "C" int bxmi_beds_create(const int32_t *start, const int32_t *end, int64_t n, bxmi_beds_t **out)
 {
     const char *who = "bxmi_beds_create";
     if (!out) return fail(BXMI_EINVAL, "%s: out is NULL", who);
     *out = nullptr;
     if (n < 0 || (n > 0 && (!start || !end))) return fail(BXMI_EINVAL, "%s: bad arguments", who);
-    for (int64_t i = 0; i < n; i++)
-        if (start[i] < 0 || end[i] < 0)
-            return fail(BXMI_EINVAL, "%s: record %lld = [%d, %d) has a negative coordinate", who, (long long)i, (int)start[i], (int)end[i]);
+    BXMI_TRY(no_negative(who, "record", start, end, n));
     std::unique_ptr<int32_t[]> reach(new (std::nothrow) int32_t[(size_t)(n > 0 ? 2 * n : 1)]);
-    bxmi_beds *h = new (std::nothrow) bxmi_beds();
-    if (!h || !reach) {
-        delete h;
-        return fail(BXMI_ENOMEM, "%s: host allocation failed", who);
-    }
+    std::unique_ptr<bxmi_beds> h(new (std::nothrow) bxmi_beds());
+    if (!h || !reach) return fail(BXMI_ENOMEM, "%s: host allocation failed", who);
     h->n = n;
     h->sorted = bd_build_reach(start, end, n, reach.get(), reach.get() + n);
-    struct Copy { DevBuf *to; const void *from; };
-    const Copy copies[] = {{&h->start, start}, {&h->end, end}, {&h->reach, reach.get()}, {&h->creach, reach.get() + n}};
     const size_t bytes = (size_t)n * 4;
-    int rc = BXMI_OK;
-    for (const Copy &c : copies) {
-        if (rc == BXMI_OK) rc = c.to->reserve(bytes ? bytes : 4);
-        if (rc == BXMI_OK && bytes > 0) {
-            const hipError_t e = hipMemcpy(c.to->p, c.from, bytes, hipMemcpyHostToDevice);
-            if (e != hipSuccess) rc = fail(BXMI_EHIP, "%s: %s", who, hipGetErrorString(e));
-        }
-    }
-    if (rc != BXMI_OK) {
-        delete h;
-        return rc;
-    }
-    *out = h;
+    BXMI_TRY(upload(who, {{&h->start, start, bytes}, {&h->end, end, bytes}, {&h->reach, reach.get(), bytes}, {&h->creach, reach.get() + n, bytes}}));
+    *out = h.release();
     return BXMI_OK;
 }
 
@@ -226,95 +218,69 @@ struct SummaryBufs {
     DevBuf r[5];
 };
 LibraryScratch<SummaryBufs> &g_summary = LibraryScratch<SummaryBufs>::leaked();
+
+struct Planes {  // the five outputs of a summary, in the order of include/bxmi.h
+    double *p[5];
+};
 }  // namespace
 
 template <typename Handle>
 static int summary_check(const char *who, Handle *const *tracks, int32_t n_tracks, const void *track_of, const void *start, const void *end,
-                         int64_t n, int32_t size, void *const *out)
+                         int64_t n, int32_t size, const Planes &out)
 {
     BXMI_TRY(track_batch_check(who, "size", size, tracks, n_tracks, n));
     if (n > 0) {
         if (!track_of || !start || !end) return fail(BXMI_EINVAL, "%s: NULL array", who);
         for (int k = 0; k < 5; k++)
-            if (!out[k]) return fail(BXMI_EINVAL, "%s: NULL output array", who);
+            if (!out.p[k]) return fail(BXMI_EINVAL, "%s: NULL output array", who);
     }
     return BXMI_OK;
 }
 
-// S.table for this call's tracks, 8 per launch; the spare entry has no items
-static int summary_fill_table(SummaryBufs &S, bxmi_spans_t *const *tracks, int32_t n_tracks, hipStream_t st)
+// S.table for this call's tracks, 8 per launch; the spare entry (an empty handle's) has no items
+template <typename Handle>
+static int summary_fill_table(SummaryBufs &S, Handle *const *tracks, int32_t n_tracks, hipStream_t st)
 {
-    return fill_track_table<SmTrack, 8>(S.table, n_tracks, [&](int k) { return tracks[k]->entry(); }, SmTrack{nullptr, nullptr, nullptr, 0, 1}, st);
+    return fill_track_table<typename Handle::Entry, 8>(S.table, n_tracks, [&](int k) { return tracks[k]->entry(); }, Handle().entry(), st);
 }
 
-static int summary_fill_table(SummaryBufs &S, bxmi_zoom_t *const *tracks, int32_t n_tracks, hipStream_t st)
-{
-    return fill_track_table<ZmTrack, 8>(S.table, n_tracks, [&](int k) { return tracks[k]->entry(); }, ZmTrack{}, st);
-}
-
-static int summary_fill_table(SummaryBufs &S, bxmi_beds_t *const *tracks, int32_t n_tracks, hipStream_t st)
-{
-    return fill_track_table<BdTrack, 8>(S.table, n_tracks, [&](int k) { return tracks[k]->entry(); }, BdTrack{nullptr, nullptr, nullptr, nullptr, 0, 1}, st);
-}
-
-static void launch_rows(const SmTrack *table, int64_t m, int n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, int size,
-                        double *const *out, int64_t cell, hipStream_t st)
-{
-    hipLaunchKernelGGL(sm_summary_kernel, dim3((unsigned)m), dim3(SM_THREADS), 0, st, table, n_tracks, track_of, start, end, size, out[0] + cell,
-                       out[1] + cell, out[2] + cell, out[3] + cell, out[4] + cell);
-}
-
-static void launch_rows(const ZmTrack *table, int64_t m, int n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, int size,
-                        double *const *out, int64_t cell, hipStream_t st)
-{
-    hipLaunchKernelGGL(zm_summary_kernel, dim3((unsigned)m), dim3(ZM_THREADS), 0, st, table, n_tracks, track_of, start, end, size, out[0] + cell,
-                       out[1] + cell, out[2] + cell, out[3] + cell, out[4] + cell);
-}
-
-static void launch_rows(const BdTrack *table, int64_t m, int n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, int size,
-                        double *const *out, int64_t cell, hipStream_t st)
-{
-    hipLaunchKernelGGL(bd_summary_kernel, dim3((unsigned)m), dim3(BD_THREADS), 0, st, table, n_tracks, track_of, start, end, size, out[0] + cell,
-                       out[1] + cell, out[2] + cell, out[3] + cell, out[4] + cell);
-}
-
-// Entry: SmTrack (full data), ZmTrack (a zoom level) or BdTrack (bigBed records) -- what S.table holds for this call
-template <typename Entry>
+// Handle: the kind of track S.table was filled for
+template <typename Handle>
 static int summary_launch(SummaryBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, int64_t n,
-                          int32_t size, double *const *out, hipStream_t st)
+                          int32_t size, const Planes &out, hipStream_t st)
 {
     constexpr int64_t ROWS_PER_LAUNCH = 1 << 25;  // (a grid's threads are counted in 32 bits: 2^25 workgroups of 64)
     for (int64_t first = 0; first < n; first += ROWS_PER_LAUNCH) {
         const int64_t m = n - first < ROWS_PER_LAUNCH ? n - first : ROWS_PER_LAUNCH, cell = first * (int64_t)size;
-        launch_rows(S.table.as<Entry>(), m, (int)n_tracks, track_of + first, start + first, end + first, (int)size, out, cell, st);
+        hipLaunchKernelGGL(Handle::kernel, dim3((unsigned)m), dim3(Handle::THREADS), 0, st, S.table.as<typename Handle::Entry>(), (int)n_tracks,
+                           track_of + first, start + first, end + first, (int)size, out.p[0] + cell, out.p[1] + cell, out.p[2] + cell, out.p[3] + cell,
+                           out.p[4] + cell);
         BXMI_LAUNCH_CHECK();
     }
     return BXMI_OK;
 }
 
-// The device form of every kind of track: Entry is what the kernel reads for a Handle.
-template <typename Entry, typename Handle>
+// The device form of every kind of track.
+template <typename Handle>
 static int summarize_dev(const char *who, Handle *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
-                         int64_t n, int32_t size, double *const *out, void *stream)
+                         int64_t n, int32_t size, const Planes &out, void *stream)
 {
-    BXMI_TRY(summary_check(who, tracks, n_tracks, track_of, start, end, n, size, reinterpret_cast<void *const *>(out)));
+    BXMI_TRY(summary_check(who, tracks, n_tracks, track_of, start, end, n, size, out));
     if (n == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_summary.lock);
     BXMI_TRY(g_summary.enter());
     BXMI_TRY(summary_fill_table(g_summary.bufs, tracks, n_tracks, as_stream(stream)));
-    return summary_launch<Entry>(g_summary.bufs, n_tracks, track_of, start, end, n, size, out, as_stream(stream));
+    return summary_launch<Handle>(g_summary.bufs, n_tracks, track_of, start, end, n, size, out, as_stream(stream));
 }
 
 // The host form of every kind: through the device in slabs.
-template <typename Entry, typename Handle>
+template <typename Handle>
 static int summarize_host(const char *who, Handle *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
-                          int64_t n, int32_t size, double *const *out)
+                          int64_t n, int32_t size, const Planes &out)
 {
-    BXMI_TRY(summary_check(who, tracks, n_tracks, track_of, start, end, n, size, reinterpret_cast<void *const *>(out)));
+    BXMI_TRY(summary_check(who, tracks, n_tracks, track_of, start, end, n, size, out));
     BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
-    for (int64_t i = 0; i < n; i++)
-        if (start[i] < 0 || end[i] < 0)
-            return fail(BXMI_EINVAL, "%s: region %lld = [%d, %d) has a negative coordinate", who, (long long)i, (int)start[i], (int)end[i]);
+    BXMI_TRY(no_negative(who, "region", start, end, n));
     if (n == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_summary.lock);
     BXMI_TRY(g_summary.enter(true));
@@ -327,10 +293,10 @@ static int summarize_host(const char *who, Handle *const *tracks, int32_t n_trac
     BXMI_TRY(S.q_track.reserve(rows));
     BXMI_TRY(S.q_start.reserve(rows));
     BXMI_TRY(S.q_end.reserve(rows));
-    double *dev_out[5];
+    Planes dev_out;
     for (int k = 0; k < 5; k++) {
         BXMI_TRY(S.r[k].reserve(cells));
-        dev_out[k] = S.r[k].as<double>();
+        dev_out.p[k] = S.r[k].as<double>();
     }
     BXMI_TRY(summary_fill_table(S, tracks, n_tracks, st));
     for (int64_t first = 0; first < n; first += slab) {
@@ -339,9 +305,9 @@ static int summarize_host(const char *who, Handle *const *tracks, int32_t n_trac
         BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of + first, in_bytes, hipMemcpyHostToDevice, st));
         BXMI_HIP(hipMemcpyAsync(S.q_start.p, start + first, in_bytes, hipMemcpyHostToDevice, st));
         BXMI_HIP(hipMemcpyAsync(S.q_end.p, end + first, in_bytes, hipMemcpyHostToDevice, st));
-        BXMI_TRY(summary_launch<Entry>(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), S.q_end.as<int32_t>(), m, size, dev_out, st));
+        BXMI_TRY(summary_launch<Handle>(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), S.q_end.as<int32_t>(), m, size, dev_out, st));
         for (int k = 0; k < 5; k++)
-            BXMI_HIP(hipMemcpyAsync(out[k] + first * (int64_t)size, dev_out[k], out_bytes, hipMemcpyDeviceToHost, st));
+            BXMI_HIP(hipMemcpyAsync(out.p[k] + first * (int64_t)size, dev_out.p[k], out_bytes, hipMemcpyDeviceToHost, st));
         BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
     }
     return BXMI_OK;
@@ -351,45 +317,39 @@ extern "C" int bxmi_spans_summarize_dev(bxmi_spans_t *const *tracks, int32_t n_t
                                         const int32_t *end, int64_t n, int32_t size, double *valid, double *min, double *max, double *sum,
                                         double *sumsq, void *stream)
 {
-    double *const out[5] = {valid, min, max, sum, sumsq};
-    return summarize_dev<SmTrack>("bxmi_spans_summarize_dev", tracks, n_tracks, track_of, start, end, n, size, out, stream);
+    return summarize_dev("bxmi_spans_summarize_dev", tracks, n_tracks, track_of, start, end, n, size, {{valid, min, max, sum, sumsq}}, stream);
 }
 
 extern "C" int bxmi_spans_summarize(bxmi_spans_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
                                     int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq)
 {
-    double *const out[5] = {valid, min, max, sum, sumsq};
-    return summarize_host<SmTrack>("bxmi_spans_summarize", tracks, n_tracks, track_of, start, end, n, size, out);
+    return summarize_host("bxmi_spans_summarize", tracks, n_tracks, track_of, start, end, n, size, {{valid, min, max, sum, sumsq}});
 }
 
 extern "C" int bxmi_zoom_summarize_dev(bxmi_zoom_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
                                        const int32_t *end, int64_t n, int32_t size, double *valid, double *min, double *max, double *sum,
                                        double *sumsq, void *stream)
 {
-    double *const out[5] = {valid, min, max, sum, sumsq};
-    return summarize_dev<ZmTrack>("bxmi_zoom_summarize_dev", tracks, n_tracks, track_of, start, end, n, size, out, stream);
+    return summarize_dev("bxmi_zoom_summarize_dev", tracks, n_tracks, track_of, start, end, n, size, {{valid, min, max, sum, sumsq}}, stream);
 }
 
 extern "C" int bxmi_zoom_summarize(bxmi_zoom_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
                                    int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq)
 {
-    double *const out[5] = {valid, min, max, sum, sumsq};
-    return summarize_host<ZmTrack>("bxmi_zoom_summarize", tracks, n_tracks, track_of, start, end, n, size, out);
+    return summarize_host("bxmi_zoom_summarize", tracks, n_tracks, track_of, start, end, n, size, {{valid, min, max, sum, sumsq}});
 }
 
 extern "C" int bxmi_beds_summarize_dev(bxmi_beds_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
                                        const int32_t *end, int64_t n, int32_t size, double *valid, double *min, double *max, double *sum,
                                        double *sumsq, void *stream)
 {
-    double *const out[5] = {valid, min, max, sum, sumsq};
-    return summarize_dev<BdTrack>("bxmi_beds_summarize_dev", tracks, n_tracks, track_of, start, end, n, size, out, stream);
+    return summarize_dev("bxmi_beds_summarize_dev", tracks, n_tracks, track_of, start, end, n, size, {{valid, min, max, sum, sumsq}}, stream);
 }
 
 extern "C" int bxmi_beds_summarize(bxmi_beds_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
                                    int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq)
 {
-    double *const out[5] = {valid, min, max, sum, sumsq};
-    return summarize_host<BdTrack>("bxmi_beds_summarize", tracks, n_tracks, track_of, start, end, n, size, out);
+    return summarize_host("bxmi_beds_summarize", tracks, n_tracks, track_of, start, end, n, size, {{valid, min, max, sum, sumsq}});
 }
 
 // ---- per-base arrays (span_arrays.hpp): BigWigFile.get_as_array for a batch of rows ----

@@ -49,16 +49,60 @@ struct SmAcc {
     double valid, mn, mx, sum, sumsq;
 };
 
+// A kernel's row: region [s, e) of the track whose table entry is `tr`; `has`: the row names a track and a region, else it is an
+// EMPTY ROW and `tr` the spare entry (nothing in it); step: bases per bin.
+template <typename Entry>
+struct SmRow {
+    Entry tr;
+    int s, e;
+    bool has;
+    int step;
+};
+template <typename Entry>
+__device__ __forceinline__ SmRow<Entry> sm_row(const Entry *table, int n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                                               int64_t row, int size)
+{
+    const int t = track_of[row], s = start[row], e = end[row];
+    const bool has = t >= 0 && t < n_tracks && s >= 0 && s < e;
+    const Entry tr = table[has ? t : n_tracks];
+    return SmRow<Entry>{tr, s, e, has, has ? (e - s) / size : 0};
+}
+
+// Bins [g0, g1) of a row, 64 at a time, lane = bin: this lane's bin is [b0, b1) where `ok`.  (g0 is 64-bit in the kernels' loops:
+// g0 + 64 may pass 2^31 for a size near it; s + step * bin <= e for bin <= size, so the bases fit an int.)
+struct SmGroup {
+    int64_t g1, bin;
+    bool ok;
+    int b0, b1;
+};
+__device__ __forceinline__ SmGroup sm_group(int64_t g0, int size, int lane, int s, int step)
+{
+    const int64_t g1 = g0 + 64 < size ? g0 + 64 : size;
+    const int64_t bin = g0 + lane;
+    const bool ok = bin < g1;
+    const int b0 = ok ? (int)(s + (int64_t)step * bin) : 0;
+    return SmGroup{g1, bin, ok, b0, ok ? b0 + step : 0};
+}
+
+// The weight w of the item [st, en) in the bin [b0, b1) of the region [s, e); false when the item, clipped to the region, does not
+// overlap the bin.  The one place where a weight is computed: bigWig items (sm_item) and bigBed records (bd_item) share its bits.
+__device__ __forceinline__ bool sm_weight(double &w, int st, int en, int s, int e, int b0, int b1)
+{
+    const int cs = st > s ? st : s, ce = en < e ? en : e;
+    if (cs >= ce) return false;
+    const int ov = (ce < b1 ? ce : b1) - (cs > b0 ? cs : b0);
+    if (ov <= 0) return false;
+    const int n = ce - cs;
+    // (x / x == 1.0 exactly, so an item inside the bin weighs (double)n without the division: the same bits)
+    w = ov == n ? (double)n : (double)n * ((double)ov / (double)n);
+    return true;
+}
+
 // One item against one bin [b0, b1) of the region [s, e): the body of accumulate_interval_value (bbi_file.pyx:90-111).
 __device__ __forceinline__ void sm_item(SmAcc &a, int st, int en, float val, int s, int e, int b0, int b1)
 {
-    const int cs = st > s ? st : s, ce = en < e ? en : e;
-    if (cs >= ce) return;
-    const int ov = (ce < b1 ? ce : b1) - (cs > b0 ? cs : b0);
-    if (ov <= 0) return;
-    const int n = ce - cs;
-    // (x / x == 1.0 exactly, so an item inside the bin weighs (double)n without the division: the same bits)
-    const double w = ov == n ? (double)n : (double)n * ((double)ov / (double)n);
+    double w;
+    if (!sm_weight(w, st, en, s, e, b0, b1)) return;
     const double v = (double)val;
     a.valid += w;
     a.sum += v * w;
@@ -78,6 +122,17 @@ __device__ __forceinline__ int64_t sm_first_above(const int32_t BX_GLOBAL *keys,
     return lo;
 }
 
+// first index in [lo, hi) whose key is >= x (keys non-decreasing)
+__device__ __forceinline__ int64_t zm_first_at_least(const int32_t BX_GLOBAL *keys, int64_t lo, int64_t hi, int x)
+{
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] >= x) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
 __global__ __launch_bounds__(SM_THREADS) void sm_summary_kernel(const SmTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
                                                                 const int32_t *__restrict__ start, const int32_t *__restrict__ end, int size,
                                                                 double *__restrict__ o_valid, double *__restrict__ o_min, double *__restrict__ o_max,
@@ -87,13 +142,10 @@ __global__ __launch_bounds__(SM_THREADS) void sm_summary_kernel(const SmTrack *_
     __shared__ float l_val[SM_CHUNK];
     const int64_t row = blockIdx.x;
     const int lane = (int)threadIdx.x;
-    const int t = track_of[row], s = start[row], e = end[row];
-    const bool has = t >= 0 && t < n_tracks && s >= 0 && s < e;
-    const SmTrack tr = table[has ? t : n_tracks];  // (the spare entry: no items)
+    const auto [tr, s, e, has, step] = sm_row(table, n_tracks, track_of, start, end, row, size);
     const int32_t BX_GLOBAL *t_st = as_global(tr.start), *t_en = as_global(tr.end);
     const float BX_GLOBAL *t_val = as_global(tr.value);
     const bool ordered = tr.ordered != 0;
-    const int step = has ? (e - s) / size : 0;
     // the region's items: [lo, hi)
     int64_t lo = 0, hi = 0;
     if (step > 0 && tr.n > 0) {
@@ -104,12 +156,8 @@ __global__ __launch_bounds__(SM_THREADS) void sm_summary_kernel(const SmTrack *_
         }
     }
     const int64_t out0 = row * (int64_t)size;
-    for (int64_t g0 = 0; g0 < size; g0 += 64) {  // (64-bit: g0 + 64 may pass 2^31 for a size near it)
-        const int64_t g1 = g0 + 64 < size ? g0 + 64 : size;  // bins [g0, g1)
-        const int64_t bin = g0 + lane;
-        const bool ok = bin < g1;
-        // (s + step * bin <= e for bin <= size: the result fits an int)
-        const int b0 = ok ? (int)(s + (int64_t)step * bin) : 0, b1 = ok ? b0 + step : 0;
+    for (int64_t g0 = 0; g0 < size; g0 += 64) {
+        const auto [g1, bin, ok, b0, b1] = sm_group(g0, size, lane, s, step);  // bins [g0, g1), this lane's [b0, b1)
         SmAcc a{0.0, __builtin_inf(), -__builtin_inf(), 0.0, 0.0};
         if (hi > lo) {
             int64_t glo = lo, ghi = hi;

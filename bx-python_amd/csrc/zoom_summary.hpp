@@ -60,17 +60,6 @@ __device__ __forceinline__ float zm_add(float acc, double field, float factor)
     return (float)((double)acc + product);
 }
 
-// first index in [lo, hi) whose key is >= x (keys non-decreasing)
-__device__ __forceinline__ int64_t zm_first_at_least(const int32_t BX_GLOBAL *keys, int64_t lo, int64_t hi, int x)
-{
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] >= x) hi = mid;
-        else lo = mid + 1;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(ZM_THREADS) void zm_summary_kernel(const ZmTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
                                                                 const int32_t *__restrict__ start, const int32_t *__restrict__ end, int size,
                                                                 double *__restrict__ o_valid, double *__restrict__ o_min, double *__restrict__ o_max,
@@ -81,13 +70,10 @@ __global__ __launch_bounds__(ZM_THREADS) void zm_summary_kernel(const ZmTrack *_
     __shared__ float l_mn[ZM_CHUNK], l_mx[ZM_CHUNK], l_sum[ZM_CHUNK], l_sumsq[ZM_CHUNK];
     const int64_t row = blockIdx.x;
     const int lane = (int)threadIdx.x;
-    const int t = track_of[row], s = start[row], e = end[row];
-    const bool has = t >= 0 && t < n_tracks && s >= 0 && s < e;
-    const ZmTrack tr = table[has ? t : n_tracks];  // (the spare entry: no records, no leaves)
+    const auto [tr, s, e, has, step] = sm_row(table, n_tracks, track_of, start, end, row, size);
     const int32_t BX_GLOBAL *t_st = as_global(tr.start), *t_en = as_global(tr.end);
     const uint32_t BX_GLOBAL *t_valid = as_global(tr.valid);
     const float BX_GLOBAL *t_mn = as_global(tr.mn), *t_mx = as_global(tr.mx), *t_sum = as_global(tr.sum), *t_sumsq = as_global(tr.sumsq);
-    const int step = has ? (e - s) / size : 0;
     // the records the region loads: [lo, hi), those of the leaves with s < leaf_hi and e > leaf_lo
     int64_t lo = 0, hi = 0;
     if (has && tr.n_leaves > 0) {
@@ -102,12 +88,8 @@ __global__ __launch_bounds__(ZM_THREADS) void zm_summary_kernel(const ZmTrack *_
     }
     const double nan = __builtin_nan("");
     const int64_t out0 = row * (int64_t)size;
-    for (int64_t g0 = 0; g0 < size; g0 += 64) {  // (64-bit: g0 + 64 may pass 2^31 for a size near it)
-        const int64_t g1 = g0 + 64 < size ? g0 + 64 : size;  // bins [g0, g1)
-        const int64_t bin = g0 + lane;
-        const bool ok = bin < g1;
-        // (s + step * bin <= e for bin <= size: the result fits an int)
-        const int b0 = ok ? (int)(s + (int64_t)step * bin) : 0, b1 = ok ? b0 + step : 0;
+    for (int64_t g0 = 0; g0 < size; g0 += 64) {
+        const auto [g1, bin, ok, b0, b1] = sm_group(g0, size, lane, s, step);  // bins [g0, g1), this lane's [b0, b1)
         float valid = 0.0f, sum = 0.0f, sumsq = 0.0f, mn = 0.0f, mx = 0.0f;
         bool any = false;
         int64_t front = hi;

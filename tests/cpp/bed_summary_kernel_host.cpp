@@ -1,5 +1,5 @@
 // bd_summary_kernel of bx-python_amd/csrc/bed_summary.hpp run on the host, its text compiled as it stands, the way
-// summary_kernel_host.cpp runs sm_summary_kernel: a workgroup is 64 host threads that meet at a barrier where the kernel calls
+// summary_kernel_host.cpp runs sm_summary_kernel over kernel_host.hpp: a workgroup is 64 host threads that meet at a barrier where the kernel calls
 // __syncthreads(), LDS is a static array, workgroups run one after another.  What this checks is everything in the kernel that is
 // not the GPU's arithmetic: the searches on reach[], the aligned chunks and the ones that are skipped, which records a lane walks,
 // the carried accumulator, every index (build it with -fsanitize=address,undefined).  Compile with -ffp-contract=off.
@@ -9,81 +9,10 @@
 // usage: bed_summary_kernel_host IN OUT
 //   IN:  int32 n_tracks, n, size; per track int32 records, then start[], end[] (int32); then track_of[n], start[n], end[n] (int32)
 //   OUT: five float64 planes [n, size]: valid, min, max, sum, sumsq; then int32 sorted[n_tracks]
-#include <atomic>
-#include <condition_variable>
-#include <cstdint>
-#include <cstdio>
-#include <mutex>
-#include <thread>
-#include <vector>
-
-struct Dim {
-    unsigned x;
-};
-static thread_local Dim threadIdx;
-static thread_local Dim blockIdx;
-
-class Barrier {
-    std::mutex m;
-    std::condition_variable cv;
-    int waiting = 0, count;
-    unsigned long generation = 0;
-
-  public:
-    explicit Barrier(int n) : count(n) {}
-    void wait()
-    {
-        std::unique_lock<std::mutex> lock(m);
-        const unsigned long g = generation;
-        if (++waiting == count) {
-            waiting = 0;
-            generation++;
-            cv.notify_all();
-        } else {
-            cv.wait(lock, [&] { return generation != g; });
-        }
-    }
-};
-static Barrier g_barrier(64);
-static void __syncthreads() { g_barrier.wait(); }
-
-// __ballot for the 64 host threads: everyone votes into the slot of this call, meets at the barrier and reads it.  Three slots
-// in turn: the one cleared after call k's barrier was read for the last time before it and is voted into only after call k + 1's.
-static std::atomic<unsigned long long> g_votes[3];
-static thread_local unsigned long g_ballots = 0;
-static unsigned long long host_ballot(bool p)
-{
-    const unsigned long k = g_ballots++;
-    if (p) g_votes[k % 3].fetch_or(1ull << threadIdx.x);
-    g_barrier.wait();
-    const unsigned long long all = g_votes[k % 3].load();
-    if (threadIdx.x == 0) g_votes[(k + 2) % 3].store(0);
-    return all;
-}
-#define BD_BALLOT(p) host_ballot(p)
-
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(...)
-#define __restrict__
-#define __shared__ static
-#define BX_GLOBAL
-template <typename T>
-T *as_global(T *p)
-{
-    return p;
-}
+#include "kernel_host.hpp"
 #include "summary.hpp"
 #include "bed_summary.hpp"
 using namespace bxmi;
-
-template <typename T>
-static bool read_n(FILE *f, std::vector<T> &v, size_t n)
-{
-    v.resize(n);
-    return n == 0 || fread(v.data(), sizeof(T), n, f) == n;
-}
 
 // reach[] and creach[] by their definitions, and `sorted`, against bd_build_reach
 static bool builder_agrees(int64_t n, unsigned seed)
@@ -146,24 +75,8 @@ int main(int argc, char **argv)
     std::vector<int32_t> track_of, start, end;
     if (!read_n(f, track_of, n) || !read_n(f, start, n) || !read_n(f, end, n)) return 2;
     fclose(f);
-    std::vector<double> out[5];
-    for (auto &o : out) o.assign((size_t)n * size, -777.0);  // (a cell the kernel does not write shows)
-    std::vector<std::thread> lanes;
-    for (int lane = 0; lane < 64; lane++)
-        lanes.emplace_back([&, lane] {
-            threadIdx.x = lane;
-            for (int row = 0; row < n; row++) {
-                blockIdx.x = row;
-                bd_summary_kernel(table.data(), n_tracks, track_of.data(), start.data(), end.data(), size, out[0].data(), out[1].data(), out[2].data(),
-                                  out[3].data(), out[4].data());
-                g_barrier.wait();  // the next workgroup reuses the LDS
-            }
-        });
-    for (auto &t : lanes) t.join();
     f = fopen(argv[2], "wb");
-    if (!f) return 2;
-    for (auto &o : out)
-        if (fwrite(o.data(), sizeof(double), o.size(), f) != o.size()) return 2;
+    if (!f || !run_summary(bd_summary_kernel, table, track_of, start, end, size, f)) return 2;
     if (n_tracks > 0 && fwrite(sorted.data(), sizeof(int32_t), sorted.size(), f) != sorted.size()) return 2;
     fclose(f);
     puts("bed summary kernel host ok");

@@ -1,4 +1,4 @@
-// sa_arrays_kernel of bx-python_amd/csrc/span_arrays.hpp run on the host, its text compiled as it stands: a workgroup is SA_THREADS
+// sa_arrays_kernel of bx-python_amd/csrc/span_arrays.hpp run on the host, its text compiled as it stands over kernel_host.hpp: a workgroup is SA_THREADS
 // host threads that meet at a barrier where the kernel calls __syncthreads(), LDS is a static array, workgroups run one after
 // another.  What this checks is everything in the kernel: which row an output element belongs to, the segments of a tile, the
 // searches for a segment's run, the chunks, which staged item wins, every index and every store (build it with
@@ -11,55 +11,8 @@
 //        slab_tiles: > 0 cuts the output into launches of that many tiles, each given only its own rows, cut by sa_rows_of as the
 //        host form of bxmi_spans_arrays cuts them
 //   OUT: uint32 [GUARD + total + GUARD]: the guard bands as they were filled (0xDEADBEEF) unless the kernel wrote there
-#include <atomic>
-#include <condition_variable>
-#include <cstdint>
-#include <cstdio>
-#include <mutex>
-#include <thread>
-#include <vector>
+#include "kernel_host.hpp"
 
-struct Dim {
-    unsigned x;
-};
-static thread_local Dim threadIdx;
-static thread_local Dim blockIdx;
-
-class Barrier {
-    std::mutex m;
-    std::condition_variable cv;
-    int waiting = 0, count;
-    unsigned long generation = 0;
-
-  public:
-    explicit Barrier(int n) : count(n) {}
-    void wait()
-    {
-        std::unique_lock<std::mutex> lock(m);
-        const unsigned long g = generation;
-        if (++waiting == count) {
-            waiting = 0;
-            generation++;
-            cv.notify_all();
-        } else {
-            cv.wait(lock, [&] { return generation != g; });
-        }
-    }
-};
-
-#define __global__
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#define __launch_bounds__(...)
-#define __restrict__
-#define __shared__ static
-#define BX_GLOBAL
-template <typename T>
-T *as_global(T *p)
-{
-    return p;
-}
 static std::atomic<bool> g_aligned_store_seen{false}, g_misaligned_vector_store{false};
 static void store_int4(int32_t *p, int a, int b, int c, int d)
 {
@@ -67,19 +20,8 @@ static void store_int4(int32_t *p, int a, int b, int c, int d)
     g_aligned_store_seen = true;
     p[0] = a, p[1] = b, p[2] = c, p[3] = d;
 }
-static void __syncthreads();
 #include "span_arrays.hpp"
 using namespace bxmi;
-
-static Barrier g_barrier(SA_THREADS);
-static void __syncthreads() { g_barrier.wait(); }
-
-template <typename T>
-static bool read_n(FILE *f, std::vector<T> &v, size_t n)
-{
-    v.resize(n);
-    return n == 0 || fread(v.data(), sizeof(T), n, f) == n;
-}
 
 constexpr size_t GUARD = 64;
 
@@ -127,18 +69,10 @@ int main(int argc, char **argv)
         std::vector<int64_t> s_off;
         if (ragged) s_off.assign(row_off.begin() + r0, row_off.begin() + r0 + m + 1);
         const unsigned tiles = (unsigned)((count + SA_TILE - 1) / SA_TILE);
-        std::vector<std::thread> lanes;
-        for (int lane = 0; lane < SA_THREADS; lane++)
-            lanes.emplace_back([&, lane] {
-                threadIdx.x = lane;
-                for (unsigned b = 0; b < tiles; b++) {
-                    blockIdx.x = b;
-                    sa_arrays_kernel(table.data(), n_tracks, s_track.data(), s_start.data(), m, r0, width, ragged ? s_off.data() : nullptr, o0, count,
-                                     out + o0, vec);
-                    g_barrier.wait();  // the next workgroup reuses the LDS
-                }
-            });
-        for (auto &t : lanes) t.join();
+        run_grid(SA_THREADS, tiles, [&] {
+            sa_arrays_kernel(table.data(), n_tracks, s_track.data(), s_start.data(), m, r0, width, ragged ? s_off.data() : nullptr, o0, count, out + o0,
+                             vec);
+        });
     }
     if (g_misaligned_vector_store || (!vec && g_aligned_store_seen)) return 4;
     f = fopen(argv[2], "wb");

@@ -251,6 +251,93 @@ def test_track_table_is_reused_by_a_call_with_fewer_tracks():
         t.close()
 
 
+# ------------------------------------------------------------ the kinds of track share the table --
+def kinds_case():
+    """(9 span tracks, 2 zoom level parts, 17 bed tracks; per kind the 6 rows' track_of; starts, ends; window starts): tracks of at
+    most CHUNK + 7 items -- a whole one goes through LDS in two chunks -- one per kind with 0 items, one span track not ordered;
+    every batch has a row without a track (-1)"""
+    from bxmi.bigwig import ZoomArrays
+
+    rng = np.random.default_rng(9)
+    top = CHUNK + 7
+
+    def span(n, back=False):
+        k = np.arange(n, dtype=np.int32)
+        s, e, v = 2 + 3 * k, 3 + 3 * k + k % 3, rng.standard_normal(n).astype(np.float32)
+        return (s[::-1].copy(), e[::-1].copy(), v) if back else (s, e, v)
+
+    def level(n):
+        k = np.arange(n, dtype=np.int32)
+        sums = rng.standard_normal(n).astype(np.float32)
+        first = np.append(np.arange(0, n, 5, dtype=np.int64), n) if n else np.zeros(1, np.int64)
+        return ZoomArrays(3 * k, 3 * k + 3, (1 + k % 3).astype(np.uint32), sums - 1, sums + 1, sums, sums * sums,
+                          (3 * first[:-1]).astype(np.int32), (3 * first[1:]).astype(np.int32), first)
+
+    def bed(n):
+        k = np.arange(n, dtype=np.int32)
+        return 3 * k, 3 * k + 1 + (7 * k) % 11  # (ends that descend: records that nest)
+
+    spans_ = [span(top), span(0), span(1), span(5), span(64), span(100, back=True), span(CHUNK), span(3), span(top)]
+    zooms = [level(top), level(0)]
+    beds = [bed(n) for n in (top, 0, 1, 2, 3, 5, 8, 13, 21, 34, 55, 64, 65, 89, 144, CHUNK, top)]
+    starts = np.array([0, 1, 5, 0, 7, 3 * CHUNK - 30], dtype=np.int32)
+    ends = np.array([3 * top + 5, 200, 50, 900, 7 + 65 * 4 + 3, 3 * CHUNK + 40], dtype=np.int32)
+    track_of = {"spans": [0, 8, -1, 1, 5, 6], "zoom": [0, 0, -1, 1, 0, 0], "beds": [16, 0, -1, 1, 14, 15], "one": [0, -1, 0, 0, -1, 0]}
+    windows = np.array([0, 3 * CHUNK - 2, -3, 100, 7, 50], dtype=np.int32)
+    return spans_, zooms, beds, {k: np.array(v, dtype=np.int32) for k, v in track_of.items()}, starts, ends, windows
+
+
+def test_kinds_share_the_table_back_to_back():
+    """the library's one track table is rewritten by every call with entries of that call's kind, which differ in size: spans (9
+    tracks: a pack of 8 and one more), zoom (2), beds (17), the per-base matrix over the 9 span tracks, spans again (1 track) --
+    one call after the other, once through the host forms and once through the device forms queued on ONE stream with nothing
+    waited for in between.  Every answer is the model's, byte for byte"""
+    import arrays_model
+    import bed_cases
+    import zoom_model
+    from bxmi import _ffi as ffi
+    from bxmi import summary
+
+    spans_, zooms, beds, track_of, starts, ends, windows = kinds_case()
+    width, n = 5, len(starts)
+    dev = {"spans": [summary.SpanTrack(*t) for t in spans_], "zoom": [summary.ZoomTrack(z) for z in zooms],
+           "beds": [summary.BedTrack(*t) for t in beds]}
+    dev["one"] = dev["spans"][:1]
+    symbols = {"spans": "bxmi_spans_summarize_dev", "zoom": "bxmi_zoom_summarize_dev", "beds": "bxmi_beds_summarize_dev", "one": "bxmi_spans_summarize_dev"}
+    want_matrix = arrays_model.matrix(spans_, track_of["spans"], windows, width)
+    for size in (3, 65):  # one group of bins, and two
+        want = {"spans": M.summarize(spans_, track_of["spans"], starts, ends, size),
+                "zoom": zoom_model.summarize(zooms, track_of["zoom"], starts, ends, size),
+                "beds": bed_cases.model(beds, track_of["beds"], starts, ends, size),
+                "one": M.summarize(spans_[:1], track_of["one"], starts, ends, size)}
+        # the host forms
+        assert_planes(summary.summarize(dev["spans"], track_of["spans"], starts, ends, size), want["spans"], ("host", "spans", size))
+        assert_planes(summary.summarize_zoom(dev["zoom"], track_of["zoom"], starts, ends, size), want["zoom"], ("host", "zoom", size))
+        assert_planes(summary.summarize_beds(dev["beds"], track_of["beds"], starts, ends, size), want["beds"], ("host", "beds", size))
+        arrays_model.assert_same(summary.matrix(dev["spans"], track_of["spans"], windows, width), want_matrix, ("host", "matrix", size))
+        assert_planes(summary.summarize(dev["one"], track_of["one"], starts, ends, size), want["one"], ("host", "one span track", size))
+        # the device forms: everything allocated and copied first, then the five calls queued on the null stream, then one wait
+        d_rows = {k: ffi.DeviceArray.from_numpy(v) for k, v in track_of.items()}
+        d_starts, d_ends, d_windows = (ffi.DeviceArray.from_numpy(a) for a in (starts, ends, windows))
+        d_planes = {k: [ffi.DeviceArray(8 * n * size) for _ in range(5)] for k in symbols}
+        d_matrix = ffi.DeviceArray(4 * n * width)
+        for k in ("spans", "zoom", "beds", "matrix", "one"):
+            if k == "matrix":
+                ffi.call("bxmi_spans_arrays_dev", ffi.handles(dev["spans"]), len(dev["spans"]), d_rows["spans"].ptr, d_windows.ptr, n, width, None,
+                         n * width, d_matrix.ptr, None)
+            else:
+                ffi.call(symbols[k], ffi.handles(dev[k]), len(dev[k]), d_rows[k].ptr, d_starts.ptr, d_ends.ptr, n, size,
+                         *[a.ptr for a in d_planes[k]], None)
+        ffi.call("bxmi_synchronize", None)
+        for k in symbols:
+            assert_planes([a.to_numpy(np.float64, n * size).reshape(n, size) for a in d_planes[k]], want[k], ("device", k, size))
+        arrays_model.assert_same(d_matrix.to_numpy(np.float32, n * width).reshape(n, width), want_matrix, ("device", "matrix", size))
+        for a in list(d_rows.values()) + [d_starts, d_ends, d_windows, d_matrix] + [a for planes in d_planes.values() for a in planes]:
+            a.free()
+    for t in dev["spans"] + dev["zoom"] + dev["beds"]:
+        t.close()
+
+
 # ------------------------------------------------------------ device entry point --
 def test_summarize_dev_equals_summarize_and_the_recorded_arrays():
     """summarize_dev on torch tensors -- every recorded case, a seeded batch on slices that start 4 bytes into their allocation,

@@ -5,45 +5,35 @@ of the GPU tests: ragged batches whose rows start anywhere in a thread's 4 eleme
 the chunk size, ordered tracks with overlapping items, tracks that are not ordered, rows without a track, windows from below 0 and
 at the end of int32, an output off a 16-byte boundary, and the output cut into slabs as the host form cuts it.  This is the
 kernel's logic and indexing; tests/test_gpu_arrays.py checks the same cases on the device."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import kernel_host
 import arrays_model as M
 from test_arrays_model_golden import ALL_FILES, all_recorded, spans
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD = 64
 
 
 @pytest.fixture(scope="module")
 def kernel(tmp_path_factory):
-    work = tmp_path_factory.mktemp("span_arrays_kernel_host")
-    exe = str(work / "span_arrays_kernel_host")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I" + os.path.join(ROOT, "bx-python_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "span_arrays_kernel_host.cpp"), "-o", exe])
+    program = kernel_host.build(tmp_path_factory, "span_arrays_kernel_host", "span arrays kernel host ok")
 
     def run(tracks, track_of, starts, width=0, offsets=None, misalign=0, slab_tiles=0):
         """-> float32[total]; the guard bands are checked here"""
         n = len(track_of)
         total = int(offsets[-1]) if offsets is not None else n * width
-        src, dst = str(work / "in.bin"), str(work / "out.bin")
-        with open(src, "wb") as f:
+
+        def write_in(f):
             np.array([len(tracks), n, width, offsets is not None, misalign, slab_tiles], dtype=np.int32).tofile(f)
             np.array([total], dtype=np.int64).tofile(f)
             for s, e, v in tracks:
-                np.array([len(s), M.is_ordered((s, e, v))], dtype=np.int32).tofile(f)
-                for a, dtype in ((s, np.int32), (e, np.int32), (v, np.float32)):
-                    np.ascontiguousarray(a, dtype=dtype).tofile(f)
-            for a in (track_of, starts):
-                np.ascontiguousarray(a, dtype=np.int32).tofile(f)
+                kernel_host.write_arrays(f, ([len(s), M.is_ordered((s, e, v))], np.int32), (s, np.int32), (e, np.int32), (v, np.float32))
+            kernel_host.write_arrays(f, (track_of, np.int32), (starts, np.int32))
             if offsets is not None:
-                np.ascontiguousarray(offsets, dtype=np.int64).tofile(f)
-        out = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0 and out.stdout.strip().endswith("span arrays kernel host ok"), (out.returncode, out.stdout[-500:], out.stderr[-3000:])
-        words = np.fromfile(dst, dtype=np.uint32)
+                kernel_host.write_arrays(f, (offsets, np.int64))
+
+        words = np.fromfile(program(write_in), dtype=np.uint32)
         assert len(words) == total + 2 * GUARD
         assert (words[:GUARD] == 0xDEADBEEF).all() and (words[GUARD + total:] == 0xDEADBEEF).all(), "written outside the output"
         return words[GUARD:GUARD + total].view(np.float32)

@@ -3,40 +3,28 @@
 reference result, the model's answer on the seeded batches of the GPU tests (ordered, not ordered and empty tracks, rows without a
 track, regions at the end of int32) and on runs around the chunk size.  This is the kernel's logic and indexing, not the GPU's
 arithmetic: tests/test_gpu_summary.py checks the same cases on the device."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import kernel_host
 import summary_model as M
 from summary_cases import CHUNK, assert_planes, chunk_track, differential_case, empty_planes
 from test_summary_model_golden import FILES, recorded, spans
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 @pytest.fixture(scope="module")
 def kernel(tmp_path_factory):
-    work = tmp_path_factory.mktemp("summary_kernel_host")
-    exe = str(work / "summary_kernel_host")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-pthread", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I" + os.path.join(ROOT, "bx-python_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "summary_kernel_host.cpp"), "-o", exe])
+    program = kernel_host.build(tmp_path_factory, "summary_kernel_host", "summary kernel host ok")
 
     def run(tracks, track_of, starts, ends, size):
-        src, dst = str(work / "in.bin"), str(work / "out.bin")
-        with open(src, "wb") as f:
+        def write_in(f):
             np.array([len(tracks), len(starts), size], dtype=np.int32).tofile(f)
             for s, e, v in tracks:
                 ordered = bool(np.all(np.diff(s) >= 0) and np.all(np.diff(e) >= 0))
-                np.array([len(s), ordered], dtype=np.int32).tofile(f)
-                for a, dtype in ((s, np.int32), (e, np.int32), (v, np.float32)):
-                    np.ascontiguousarray(a, dtype=dtype).tofile(f)
-            for a in (track_of, starts, ends):
-                np.ascontiguousarray(a, dtype=np.int32).tofile(f)
-        out = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0 and out.stdout.strip().endswith("summary kernel host ok"), (out.stdout[-500:], out.stderr[-3000:])
-        return np.fromfile(dst, dtype=np.float64).reshape(5, len(starts), size)
+                kernel_host.write_arrays(f, ([len(s), ordered], np.int32), (s, np.int32), (e, np.int32), (v, np.float32))
+            kernel_host.write_arrays(f, (track_of, np.int32), (starts, np.int32), (ends, np.int32))
+
+        return np.fromfile(program(write_in), dtype=np.float64).reshape(5, len(starts), size)
 
     return run
 

@@ -3,38 +3,27 @@ tests/cpp/zoom_kernel_host.cpp -- 64 threads per workgroup, a barrier for __sync
 on -- gives every recorded reference result, the model's answer on the seeded batches of the GPU tests (several tracks and levels,
 an empty one, rows without a track, a region ending at 2^31 - 1) and on runs around the chunk size.  This is the kernel's logic and
 indexing, not the GPU's arithmetic: tests/test_gpu_zoom.py checks the same cases on the device."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import kernel_host
 import zoom_model as M
 from zoom_cases import CHUNK, FILES, SIZES, assert_planes, chunk_level, differential_case, levels, recorded, zoom_cases
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def kernel(tmp_path_factory):
-    work = tmp_path_factory.mktemp("zoom_kernel_host")
-    exe = str(work / "zoom_kernel_host")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-pthread", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I" + os.path.join(ROOT, "bx-python_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "zoom_kernel_host.cpp"), "-o", exe])
+    program = kernel_host.build(tmp_path_factory, "zoom_kernel_host", "zoom kernel host ok")
 
     def run(tracks, track_of, starts, ends, size):
-        src, dst = str(work / "in.bin"), str(work / "out.bin")
-        with open(src, "wb") as f:
+        def write_in(f):
             np.array([len(tracks), len(starts), size], dtype=np.int32).tofile(f)
             for z in tracks:
                 np.array([len(z.start), len(z.leaf_lo)], dtype=np.int32).tofile(f)
-                for a, dtype in zip(z, (np.int32, np.int32, np.uint32) + (np.float32,) * 4 + (np.int32, np.int32, np.int64)):
-                    np.ascontiguousarray(a, dtype=dtype).tofile(f)
-            for a in (track_of, starts, ends):
-                np.ascontiguousarray(a, dtype=np.int32).tofile(f)
-        out = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0 and out.stdout.strip().endswith("zoom kernel host ok"), (out.stdout[-500:], out.stderr[-3000:])
-        return np.fromfile(dst, dtype=np.float64).reshape(5, len(starts), size)
+                kernel_host.write_arrays(f, *zip(z, (np.int32, np.int32, np.uint32) + (np.float32,) * 4 + (np.int32, np.int32, np.int64)))
+            kernel_host.write_arrays(f, (track_of, np.int32), (starts, np.int32), (ends, np.int32))
+
+        return np.fromfile(program(write_in), dtype=np.float64).reshape(5, len(starts), size)
 
     return run
 
