@@ -99,6 +99,13 @@ _SIGNATURES = {
     "bxmi_beds_info": [vp, _p(i64), _p(C.c_int)],
     "bxmi_beds_summarize": [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp],
     "bxmi_beds_summarize_dev": [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp],
+    "bxmi_twobit_create": [vp, i64, vp, vp, i64, vp, vp, i64, _p(vp)],
+    "bxmi_twobit_destroy": [vp],
+    "bxmi_twobit_info": [vp, _p(i64), _p(i64), _p(i64)],
+    "bxmi_twobit_bases": [vp, i32, vp, vp, i64, i32, vp, i64, C.c_int, C.c_int, vp],
+    "bxmi_twobit_bases_dev": [vp, i32, vp, vp, i64, i32, vp, i64, C.c_int, C.c_int, vp, vp],
+    "bxmi_twobit_composition": [vp, i32, vp, vp, vp, i64, C.c_int, vp],
+    "bxmi_twobit_composition_dev": [vp, i32, vp, vp, vp, i64, C.c_int, vp, vp],
     "bxmi_bits_create": [i64, i64, _p(vp)],
     "bxmi_bits_destroy": [vp],
     "bxmi_bits_info": [vp, _p(i32), _p(i32), _p(i32)],

@@ -1,0 +1,230 @@
+"""
+The sequence of .2bit files on the MI355X: ``TwoBitSequence.get`` / ``__getitem__`` (reference: lib/bx/seq/twobit.py:34-56 over
+``_twobit.read``, lib/bx/seq/_twobit.pyx:22-137) for a whole array of regions per call, and the base counts of those regions.
+
+``TwoBitTrack`` is one sequence resident in HBM (``bxmi_twobit_*`` of include/bxmi.h): its packed bytes, its N blocks and its mask
+blocks.  ``TwoBitSet`` is a whole file on the device.  ``sequences`` / ``strings`` give every row's letters exactly as the
+reference's string has them -- TCAG by code, N inside an N block, lower case inside a mask block when ``do_mask`` is set --
+``matrix`` the site x base matrix uint8 [n, width] with a pad byte outside the sequence, ``composition`` the int32 [n, 6] counts
+A, C, G, T, N, masked of every row at a cost that does not depend on the row's length.  The ``_dev`` forms take and return torch
+tensors on the caller's stream; the matrix stays on the device, where a lookup on the byte tensor gives codes or one-hot planes.
+Everything is integer work: the outputs are the reference's byte for byte.
+
+Only files whose blocks are sorted, non-empty, disjoint and inside the sequence are accepted -- every real file; for those the
+reference's walk over the blocks is plain coverage.  Anything else raises BxmiError (EINVAL) naming the condition.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _ffi, twobit
+from ._ffi import as_i32, call, ptr
+from .summary import _rows_i32, _Track
+
+COLUMNS = ("A", "C", "G", "T", "N", "masked")  # of `composition`
+
+
+class TwoBitTrack(_Track):
+    """One sequence on the device."""
+
+    _destroy = "bxmi_twobit_destroy"
+
+    def __init__(self, seq):
+        """seq: a bxmi.twobit.Sequence"""
+        _ffi.require_gpu()
+        blocks = [as_i32(a) for a in (seq.n_starts, seq.n_sizes, seq.m_starts, seq.m_sizes)]
+        packed = np.ascontiguousarray(seq.packed, dtype=np.uint8)
+        size = int(seq.size)
+        if blocks[0].shape != blocks[1].shape or blocks[2].shape != blocks[3].shape or any(b.ndim != 1 for b in blocks):
+            raise ValueError("block starts and sizes must be 1-d arrays of equal length")
+        if packed.ndim != 1 or (0 <= size and len(packed) < (size + 3) // 4):
+            raise ValueError("packed must hold (size + 3) // 4 bytes")
+        self._create("bxmi_twobit_create", ptr(packed), size, ptr(blocks[0]), ptr(blocks[1]), len(blocks[0]), ptr(blocks[2]), ptr(blocks[3]),
+                     len(blocks[2]))
+        self.size, self.n_blocks, self.m_blocks = self._info("bxmi_twobit_info", C.c_int64, C.c_int64, C.c_int64)
+
+    @classmethod
+    def from_arrays(cls, packed, size, n_starts=(), n_sizes=(), m_starts=(), m_sizes=()):
+        u32 = [np.asarray(a, dtype=np.int64) for a in (n_starts, n_sizes, m_starts, m_sizes)]
+        return cls(twobit.Sequence(size, *u32, np.asarray(packed, dtype=np.uint8)))
+
+
+def _pad_byte(pad):
+    if isinstance(pad, (bytes, str)):
+        if len(pad) != 1:
+            raise ValueError("pad must be one byte")
+        return ord(pad)
+    return int(pad)
+
+
+def _clip(sizes, track_of, s, e):
+    """the rows as TwoBitSequence.get clips them (twobit.py:44-51): start below 0 is 0, end beyond the size is the size; a row the
+    reference refuses ("end before start") or whose sequence is unknown is empty -> (starts, lengths) int64.  A track_of beyond
+    the list is left to the C check that follows: its row is empty here."""
+    table = np.array(list(sizes) + [0], dtype=np.int64)  # (the last entry: rows without a track)
+    named = (track_of >= 0) & (track_of < len(sizes))
+    size = table[np.where(named, track_of, len(sizes))]
+    first = np.maximum(s.astype(np.int64), 0)
+    return first, np.maximum(np.minimum(e.astype(np.int64), size) - first, 0)
+
+
+def sequences(tracks, track_of, starts, ends, do_mask=True):
+    """The letters of regions [starts[i], ends[i]) of tracks[track_of[i]], clipped as TwoBitSequence.get clips them -> (bytes
+    uint8[total], offsets int64[n + 1]): row i is bytes[offsets[i]:offsets[i + 1]].  Where the reference raises "end before start"
+    the row is empty; track_of[i] < 0 (unknown name) gives an empty row.  One device pass over the OUTPUT."""
+    _ffi.require_gpu()
+    tracks = list(tracks)
+    t, s, e = _rows_i32("track_of, starts and ends", track_of, starts, ends)
+    s64, lengths = _clip([tr.size for tr in tracks], t, s, e)
+    offsets = np.zeros(len(s) + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offsets[1:])
+    out = np.empty(int(offsets[-1]), dtype=np.uint8)
+    call("bxmi_twobit_bases", _ffi.handles(tracks), len(tracks), ptr(t), ptr(as_i32(s64)), len(t), 0, ptr(offsets), len(out), int(bool(do_mask)), ord("N"),
+         ptr(out))
+    return out, offsets
+
+
+def strings(tracks, track_of, starts, ends, do_mask=True):
+    """`sequences` as a list of str"""
+    data, offsets = sequences(tracks, track_of, starts, ends, do_mask)
+    text = data.tobytes().decode("ascii")
+    return [text[a:b] for a, b in zip(offsets[:-1].tolist(), offsets[1:].tolist())]
+
+
+def matrix(tracks, track_of, starts, width, pad=b"N", do_mask=True):
+    """The windows [starts[i], starts[i] + width) of tracks[track_of[i]] -> uint8 [n, width] of letters, the byte `pad` where a
+    position is outside the sequence or the row names no track.  width < 1 raises BxmiError (EINVAL)."""
+    _ffi.require_gpu()
+    tracks = list(tracks)
+    t, s = _rows_i32("track_of and starts", track_of, starts)
+    width = int(width)
+    out = np.empty((len(t), max(width, 0)), dtype=np.uint8)
+    call("bxmi_twobit_bases", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), len(t), width, None, out.size, int(bool(do_mask)), _pad_byte(pad), ptr(out))
+    return out
+
+
+def composition(tracks, track_of, starts, ends, do_mask=True):
+    """int32 [n, 6] = A, C, G, T, N, masked of [starts[i], ends[i]) clipped to the sequence: what counting the characters of the
+    reference's string gives (case folded for the first five, the lower-case ones for the sixth; masked is 0 without do_mask).  An
+    unknown sequence or an empty row gives zeros.  A row's cost does not depend on its length."""
+    _ffi.require_gpu()
+    tracks = list(tracks)
+    t, s, e = _rows_i32("track_of, starts and ends", track_of, starts, ends)
+    out = np.zeros((len(t), 6), dtype=np.int32)
+    call("bxmi_twobit_composition", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), ptr(e), len(t), int(bool(do_mask)), ptr(out))
+    return out
+
+
+def matrix_dev(tracks, track_of, starts, width, pad=b"N", do_mask=True, stream=None, out=None):
+    """`matrix` on device arrays: int32 torch tensors on the GPU in, the uint8 [n, width] tensor out -- `out` if given (contiguous
+    uint8 [n, width] on the same device; 16-byte aligned it is written by 16-byte stores, otherwise byte by byte, with the same
+    result), else a new one.  Queued on torch's current stream (or `stream`), nothing is waited for.  A track_of outside
+    [0, len(tracks)) gives a row of `pad`.  ONE 2bit call at a time per process may be in flight: the table of tracks the kernel
+    reads belongs to the library and is rewritten by every call on that call's stream."""
+    import torch
+
+    tracks = list(tracks)
+    (track_of, starts), n, dev, stream = _ffi.device_args("matrix_dev", "matrix", ("track_of", "starts"), (track_of, starts), stream)
+    width = int(width)
+    if out is None:
+        out = torch.empty((n, max(width, 0)), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (n, width) or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous uint8 [n, width] tensor on the device of the rows")
+    call("bxmi_twobit_bases_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), n, width, None, out.numel(),
+         int(bool(do_mask)), _pad_byte(pad), out.data_ptr(), stream)
+    return out
+
+
+def sequences_dev(tracks, track_of, starts, ends, do_mask=True, stream=None):
+    """`sequences` on device arrays: int32 torch tensors on the GPU in, (bytes uint8[total], offsets int64[n + 1]) tensors out.
+    The clipping and the offsets are computed by torch on its current stream and `total` is read back to size the output -- ONE
+    synchronisation; the letters are then queued on torch's current stream (or `stream`: the tensors made here are then recorded
+    as in use on it) and not waited for.  One 2bit call at a time, as `matrix_dev`."""
+    import torch
+
+    tracks = list(tracks)
+    (track_of, starts, ends), n, dev, stream = _ffi.device_args("sequences_dev", "sequences", ("track_of", "starts", "ends"), (track_of, starts, ends), stream)
+    sizes = torch.tensor([tr.size for tr in tracks] + [0], dtype=torch.int64, device=dev)  # (the last: rows without a track)
+    named = (track_of >= 0) & (track_of < len(tracks))
+    size = sizes[torch.where(named, track_of, torch.full_like(track_of, len(tracks))).to(torch.int64)]
+    first = starts.clamp(min=0)
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        torch.cumsum((torch.minimum(ends.to(torch.int64), size) - first.to(torch.int64)).clamp_(min=0), 0, out=offsets[1:])
+    total = int(offsets[-1].item()) if n else 0  # (the synchronisation: `first` and `offsets` are complete after it)
+    out = torch.empty(total, dtype=torch.uint8, device=dev)
+    call("bxmi_twobit_bases_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), first.data_ptr(), n, 0, offsets.data_ptr(), total,
+         int(bool(do_mask)), ord("N"), out.data_ptr(), stream)
+    if total and stream != torch.cuda.current_stream(dev).cuda_stream:
+        # the kernel reads `first` and `offsets` and writes `out` on a stream torch's allocator does not know them by: `first` is
+        # dropped on return and its block must not be handed out again before that stream has passed this point
+        used_on = torch.cuda.ExternalStream(stream, device=dev)
+        for t in (first, offsets, out):
+            t.record_stream(used_on)
+    return out, offsets
+
+
+def composition_dev(tracks, track_of, starts, ends, do_mask=True, stream=None):
+    """`composition` on device arrays: int32 torch tensors in, the int32 [n, 6] tensor out, queued on torch's current stream (or
+    `stream`), nothing waited for.  One 2bit call at a time, as `matrix_dev`."""
+    import torch
+
+    tracks = list(tracks)
+    (track_of, starts, ends), n, dev, stream = _ffi.device_args("composition_dev", "composition", ("track_of", "starts", "ends"), (track_of, starts, ends), stream)
+    out = torch.zeros((n, 6), dtype=torch.int32, device=dev)
+    call("bxmi_twobit_composition_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), ends.data_ptr(), n, int(bool(do_mask)),
+         out.data_ptr(), stream)
+    return out
+
+
+class TwoBitSet:
+    """A whole .2bit file on the device: one TwoBitTrack per sequence, `chroms` the names in file order.  Rows are given by name or
+    by position in `chroms` (an int array; -1: unknown), as bxmi.summary.TrackSet takes them."""
+
+    def __init__(self, seqs, do_mask=True):
+        """seqs: bxmi.twobit.read_file's result"""
+        self.do_mask = bool(do_mask)
+        self.chroms = list(seqs)
+        self.tracks = {name: TwoBitTrack(seqs[name]) for name in self.chroms}
+        self.sizes = {name: self.tracks[name].size for name in self.chroms}
+
+    @classmethod
+    def from_file(cls, path=None, do_mask=True, data=None):
+        return cls(twobit.read_file(path, data=data), do_mask)
+
+    def close(self):
+        _ffi.close_all(self.tracks.values())
+
+    def _track_of(self, chroms):
+        chroms = np.asarray(chroms)
+        if chroms.dtype.kind in "iu":
+            track_of = as_i32(chroms)
+        else:
+            index = {chrom: k for k, chrom in enumerate(self.chroms)}
+            track_of = np.array([index.get(c, -1) for c in chroms.tolist()], dtype=np.int32)
+        if track_of.ndim != 1:
+            raise ValueError("chroms, starts and ends must be 1-d arrays of equal length")
+        if len(track_of) and track_of.max() >= len(self.chroms):
+            raise ValueError("a sequence position beyond the file's %d sequences" % len(self.chroms))
+        return track_of
+
+    def sequences(self, chroms, starts, ends):
+        return sequences(self.tracks.values(), self._track_of(chroms), starts, ends, self.do_mask)
+
+    def strings(self, chroms, starts, ends):
+        return strings(self.tracks.values(), self._track_of(chroms), starts, ends, self.do_mask)
+
+    def matrix(self, chroms, starts, width, pad=b"N"):
+        return matrix(self.tracks.values(), self._track_of(chroms), starts, width, pad, self.do_mask)
+
+    def composition(self, chroms, starts, ends):
+        return composition(self.tracks.values(), self._track_of(chroms), starts, ends, self.do_mask)
+
+    def matrix_dev(self, track_of, starts, width, pad=b"N", stream=None, out=None):
+        return matrix_dev(self.tracks.values(), track_of, starts, width, pad, self.do_mask, stream, out)
+
+    def sequences_dev(self, track_of, starts, ends, stream=None):
+        return sequences_dev(self.tracks.values(), track_of, starts, ends, self.do_mask, stream)
+
+    def composition_dev(self, track_of, starts, ends, stream=None):
+        return composition_dev(self.tracks.values(), track_of, starts, ends, self.do_mask, stream)

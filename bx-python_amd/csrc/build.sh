@@ -11,7 +11,7 @@ mkdir -p "$OBJ"
 # a change of flags (BXMI_DEFS experiments) must rebuild everything
 if [ "$(cat "$OBJ/.flags" 2>/dev/null)" != "$FLAGS" ]; then rm -f "$OBJ"/*.o; echo "$FLAGS" > "$OBJ/.flags"; fi
 pids=()
-for f in core intervals bitset scores summary liftover bedparse comm; do
+for f in core intervals bitset scores summary sequence liftover bedparse comm; do
   src="$HERE/$f.hip"; [ -f "$src" ] || src="$HERE/$f.cpp"
   stale=0
   [ -f "$OBJ/$f.o" ] || stale=1
@@ -22,5 +22,5 @@ for f in core intervals bitset scores summary liftover bedparse comm; do
   fi
 done
 for p in "${pids[@]:-}"; do [ -n "$p" ] && wait "$p"; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$OBJ/core.o" "$OBJ/intervals.o" "$OBJ/bitset.o" "$OBJ/scores.o" "$OBJ/summary.o" "$OBJ/liftover.o" "$OBJ/bedparse.o" "$OBJ/comm.o" -ldl
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$OBJ/core.o" "$OBJ/intervals.o" "$OBJ/bitset.o" "$OBJ/scores.o" "$OBJ/summary.o" "$OBJ/sequence.o" "$OBJ/liftover.o" "$OBJ/bedparse.o" "$OBJ/comm.o" -ldl
 echo "built $OUT"

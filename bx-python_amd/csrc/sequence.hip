@@ -1,0 +1,317 @@
+// sequence.hip -- 2bit tracks (bxmi_twobit_*): one sequence of a .2bit file in HBM -- its packed bytes, its N blocks and its mask
+// blocks -- the letters under batches of rows (bxmi_twobit_bases*) and their base counts (bxmi_twobit_composition*).  Kernels and
+// semantics: twobit.hpp.  The argument checks, the track table and the staging are track_batch.hpp's, as in summary.hip; the scratch
+// is this unit's own, so these calls do not share the one-call-at-a-time rule with the summaries, only with each other.
+#include <memory>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "common.hpp"
+#include "primitives.hpp"
+// twobit.hpp takes sm_first_above, sa_row_of and sa_rows_of from summary.hpp and span_arrays.hpp, which also DEFINE their kernels
+// wherever they are included.  summary.hip owns those; the copies this unit cannot avoid take other names and are never launched.
+#define sm_summary_kernel sm_summary_kernel_unused_in_sequence
+#define sa_arrays_kernel sa_arrays_kernel_unused_in_sequence
+#include "summary.hpp"
+#include "span_arrays.hpp"
+#undef sm_summary_kernel
+#undef sa_arrays_kernel
+#include "twobit.hpp"
+#include "track_batch.hpp"
+
+using namespace bxmi;
+
+struct bxmi_twobit {
+    int64_t size = 0, n_blocks = 0, m_blocks = 0;
+    DevBuf packed, n_start, n_end, m_start, m_end, ckpt, n_cum, n_codes, m_cum;
+    TbTrack entry() const
+    {
+        return TbTrack{packed.as<uint32_t>(), n_start.as<int32_t>(), n_end.as<int32_t>(), m_start.as<int32_t>(), m_end.as<int32_t>(), ckpt.as<int32_t>(),
+                       n_cum.as<int32_t>(), n_codes.as<int32_t>(), m_cum.as<int32_t>(), size, n_blocks, m_blocks};
+    }
+};
+
+namespace {
+constexpr int64_t TB_SLAB = (int64_t)TB_TILE << 14;   // output bytes per slab of the host form (64 MiB), whole tiles
+constexpr int64_t TB_TILES_PER_LAUNCH = 1 << 22;      // (a grid's threads are counted in 32 bits: 2^22 workgroups of 256)
+constexpr int64_t TB_ROWS_PER_LAUNCH = 1 << 25;       // (2^25 workgroups of 64)
+constexpr int64_t TB_COMP_SLAB = 1 << 22;             // rows per slab of the host form of the composition
+
+struct SequenceBufs {
+    DevBuf table;                         // TbTrack [n_tracks + 1], the last one the spare entry
+    DevBuf q_track, q_start, q_end, r;    // staging of the host forms
+};
+LibraryScratch<SequenceBufs> &g_sequence = LibraryScratch<SequenceBufs>::leaked();
+
+// `what` blocks [start[i], start[i] + size[i]): sorted, non-empty, disjoint, inside [0, size] -> ends[] and the running sizes cum[]
+int check_blocks(const char *who, const char *what, const int32_t *start, const int32_t *sizes, int64_t blocks, int64_t size, std::vector<int32_t> &ends,
+                 std::vector<int32_t> &cum)
+{
+    ends.resize((size_t)blocks);
+    cum.assign((size_t)blocks + 1, 0);
+    int64_t prev_end = 0;
+    for (int64_t i = 0; i < blocks; i++) {
+        const int64_t s = start[i], e = s + (int64_t)sizes[i];
+        if (sizes[i] < 1) return fail(BXMI_EINVAL, "%s: %s block %lld at %lld is empty (size %d)", who, what, (long long)i, (long long)s, (int)sizes[i]);
+        if (s < 0 || e > size)
+            return fail(BXMI_EINVAL, "%s: %s block %lld = [%lld, %lld) is outside [0, size = %lld]", who, what, (long long)i, (long long)s, (long long)e,
+                        (long long)size);
+        if (i > 0 && s < prev_end)
+            return fail(BXMI_EINVAL, "%s: %s blocks are not sorted and disjoint (block %lld starts at %lld, the one before ends at %lld)", who, what,
+                        (long long)i, (long long)s, (long long)prev_end);
+        prev_end = e;
+        ends[(size_t)i] = (int32_t)e;
+        cum[(size_t)i + 1] = cum[(size_t)i] + sizes[i];
+    }
+    return BXMI_OK;
+}
+
+int put(DevBuf &to, const void *from, size_t bytes)
+{
+    BXMI_TRY(to.reserve(bytes ? bytes : 8));
+    if (bytes) BXMI_HIP(hipMemcpy(to.p, from, bytes, hipMemcpyHostToDevice));
+    return BXMI_OK;
+}
+
+// table = the running totals, one 16-byte entry each, of planes[4][stride] (counts per item in [0, items), scanned in place into
+// [1, items]; entry 0 is zero): items + 1 entries
+int running_codes(DevBuf &planes, int64_t items, DevBuf &table, DevBuf &scratch, hipStream_t st)
+{
+    const int64_t stride = items + 1;
+    int32_t *p = planes.as<int32_t>();
+    for (int c = 0; c < 4; c++)  // the counts sit at [1, items] of every plane, a zero before them
+        BXMI_TRY((device_scan<int32_t, int32_t, OpSum, true>(p + c * stride, p + c * stride, stride, 0, nullptr, scratch, st)));
+    BXMI_TRY(table.reserve((size_t)stride * 16));
+    hipLaunchKernelGGL(tb_interleave_kernel, dim3((unsigned)div_up(stride, TB_THREADS)), dim3(TB_THREADS), 0, st, p, stride, stride, table.as<int32_t>());
+    BXMI_LAUNCH_CHECK();
+    return BXMI_OK;
+}
+}  // namespace
+
+extern "C" int bxmi_twobit_create(const uint8_t *packed, int64_t size, const int32_t *n_start, const int32_t *n_size, int64_t n_blocks,
+                                  const int32_t *m_start, const int32_t *m_size, int64_t m_blocks, bxmi_twobit_t **out)
+{
+    const char *who = "bxmi_twobit_create";
+    if (!out) return fail(BXMI_EINVAL, "%s: out is NULL", who);
+    *out = nullptr;
+    if (size < 0 || size > TB_SIZE_MAX) return fail(BXMI_EINVAL, "%s: size = %lld outside [0, 2^31-1]", who, (long long)size);
+    if (n_blocks < 0 || m_blocks < 0 || (size > 0 && !packed) || (n_blocks > 0 && (!n_start || !n_size)) || (m_blocks > 0 && (!m_start || !m_size)))
+        return fail(BXMI_EINVAL, "%s: bad arguments", who);
+    std::vector<int32_t> n_end, n_cum, m_end, m_cum;
+    BXMI_TRY(check_blocks(who, "N", n_start, n_size, n_blocks, size, n_end, n_cum));
+    BXMI_TRY(check_blocks(who, "mask", m_start, m_size, m_blocks, size, m_end, m_cum));
+    std::unique_ptr<bxmi_twobit> h(new (std::nothrow) bxmi_twobit());
+    if (!h) return fail(BXMI_ENOMEM, "%s: host allocation failed", who);
+    h->size = size;
+    h->n_blocks = n_blocks;
+    h->m_blocks = m_blocks;
+    // the packed bytes, zero-filled to whole checkpoint blocks: the kernels read aligned words
+    const int64_t ckpts = div_up(size, TB_CKPT);
+    const size_t bytes = (size_t)((size + 3) / 4), room = (size_t)(ckpts > 0 ? ckpts : 1) * (TB_CKPT / 4);
+    BXMI_TRY(h->packed.reserve(room));
+    BXMI_HIP(hipMemset(h->packed.p, 0, room));
+    if (bytes) BXMI_HIP(hipMemcpy(h->packed.p, packed, bytes, hipMemcpyHostToDevice));
+    BXMI_TRY(put(h->n_start, n_start, (size_t)n_blocks * 4));
+    BXMI_TRY(put(h->n_end, n_end.data(), (size_t)n_blocks * 4));
+    BXMI_TRY(put(h->n_cum, n_cum.data(), (size_t)(n_blocks + 1) * 4));
+    BXMI_TRY(put(h->m_start, m_start, (size_t)m_blocks * 4));
+    BXMI_TRY(put(h->m_end, m_end.data(), (size_t)m_blocks * 4));
+    BXMI_TRY(put(h->m_cum, m_cum.data(), (size_t)(m_blocks + 1) * 4));
+    // the checkpoints, then the counts under the N blocks from them
+    const hipStream_t st = nullptr;
+    DevBuf planes, scratch;
+    const int64_t most = ckpts > n_blocks ? ckpts : n_blocks;
+    BXMI_TRY(planes.reserve((size_t)(most + 1) * 16));
+    BXMI_HIP(hipMemsetAsync(planes.p, 0, (size_t)(ckpts + 1) * 16, st));
+    if (ckpts > 0) {
+        hipLaunchKernelGGL(tb_count_kernel, dim3((unsigned)ckpts), dim3(TB_WAVE), 0, st, h->packed.as<uint32_t>(), size, ckpts + 1, planes.as<int32_t>() + 1);
+        BXMI_LAUNCH_CHECK();
+    }
+    BXMI_TRY(running_codes(planes, ckpts, h->ckpt, scratch, st));
+    BXMI_HIP(hipMemsetAsync(planes.p, 0, (size_t)(n_blocks + 1) * 16, st));
+    for (int64_t first = 0; first < n_blocks; first += TB_ROWS_PER_LAUNCH) {  // (one wave per block: a grid's threads are counted in 32 bits)
+        const int64_t m = n_blocks - first < TB_ROWS_PER_LAUNCH ? n_blocks - first : TB_ROWS_PER_LAUNCH;
+        hipLaunchKernelGGL(tb_under_kernel, dim3((unsigned)m), dim3(TB_WAVE), 0, st, h->packed.as<uint32_t>(), h->ckpt.as<int32_t>(),
+                           h->n_start.as<int32_t>() + first, h->n_end.as<int32_t>() + first, n_blocks + 1, planes.as<int32_t>() + 1 + first);
+        BXMI_LAUNCH_CHECK();
+    }
+    BXMI_TRY(running_codes(planes, n_blocks, h->n_codes, scratch, st));
+    BXMI_HIP(hipStreamSynchronize(st));  // (planes and scratch go away)
+    *out = h.release();
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_twobit_destroy(bxmi_twobit_t *h)
+{
+    delete h;
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_twobit_info(const bxmi_twobit_t *h, int64_t *size, int64_t *n_blocks, int64_t *m_blocks)
+{
+    if (!h) return fail(BXMI_EINVAL, "bxmi_twobit_info: NULL handle");
+    if (size) *size = h->size;
+    if (n_blocks) *n_blocks = h->n_blocks;
+    if (m_blocks) *m_blocks = h->m_blocks;
+    return BXMI_OK;
+}
+
+static int sequence_fill_table(SequenceBufs &S, bxmi_twobit_t *const *tracks, int32_t n_tracks, hipStream_t st)
+{
+    return fill_track_table<TbTrack, 8>(S.table, n_tracks, [&](int k) { return tracks[k]->entry(); }, TbTrack{}, st);
+}
+
+// ---- letters (tb_bases_kernel) ----
+// what both forms check; `row_off` is only tested for being there
+static int bases_check(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const void *track_of, const void *start, int64_t n, int32_t width,
+                       const void *row_off, int64_t total, int pad, const void *out)
+{
+    if (!row_off) {
+        BXMI_TRY(track_batch_check(who, "width", width, tracks, n_tracks, n));
+        if (total != n * (int64_t)width)
+            return fail(BXMI_EINVAL, "%s: total = %lld, but n * width = %lld", who, (long long)total, (long long)(n * (int64_t)width));
+    } else {
+        if (width != 0) return fail(BXMI_EINVAL, "%s: width = %d with row offsets, must be 0", who, (int)width);
+        BXMI_TRY(track_batch_check(who, "width", 1, tracks, n_tracks, n));
+        if (total < 0) return fail(BXMI_EINVAL, "%s: total = %lld is negative", who, (long long)total);
+    }
+    if (pad < 0 || pad > 255) return fail(BXMI_EINVAL, "%s: pad = %d is not a byte", who, pad);
+    if ((n > 0 && (!track_of || !start)) || (n > 0 && total > 0 && !out)) return fail(BXMI_EINVAL, "%s: NULL array", who);
+    return BXMI_OK;
+}
+
+// output bytes [o_first, o_first + count) of rows [row_base, row_base + n_rows); `out` is byte o_first's address
+static int bases_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n_rows, int64_t row_base, int32_t width,
+                        const int64_t *row_off, int64_t o_first, int64_t count, int do_mask, int pad, uint8_t *out, hipStream_t st)
+{
+    const int vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0;  // else the kernel stores byte by byte
+    constexpr int64_t PER_LAUNCH = TB_TILES_PER_LAUNCH * TB_TILE;
+    for (int64_t done = 0; done < count; done += PER_LAUNCH) {
+        const int64_t m = count - done < PER_LAUNCH ? count - done : PER_LAUNCH;
+        hipLaunchKernelGGL(tb_bases_kernel, dim3((unsigned)div_up(m, TB_TILE)), dim3(TB_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of,
+                           start, n_rows, row_base, (int)width, row_off, o_first + done, m, do_mask, pad, out + done, vec);
+        BXMI_LAUNCH_CHECK();
+    }
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_twobit_bases_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
+                                     int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, int pad, uint8_t *out, void *stream)
+{
+    const char *who = "bxmi_twobit_bases_dev";
+    BXMI_TRY(bases_check(who, tracks, n_tracks, track_of, start, n, width, row_off_or_null, total, pad, out));
+    if (n == 0 || total == 0) return BXMI_OK;
+    std::lock_guard<std::mutex> hold(g_sequence.lock);
+    BXMI_TRY(g_sequence.enter());
+    BXMI_TRY(sequence_fill_table(g_sequence.bufs, tracks, n_tracks, as_stream(stream)));
+    return bases_launch(g_sequence.bufs, n_tracks, track_of, start, n, 0, width, row_off_or_null, 0, total, do_mask != 0, pad, out, as_stream(stream));
+}
+
+extern "C" int bxmi_twobit_bases(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                                 const int64_t *row_off_or_null, int64_t total, int do_mask, int pad, uint8_t *out)
+{
+    const char *who = "bxmi_twobit_bases";
+    const int64_t *row_off = row_off_or_null;
+    BXMI_TRY(bases_check(who, tracks, n_tracks, track_of, start, n, width, row_off, total, pad, out));
+    if (row_off) {
+        if (row_off[0] != 0) return fail(BXMI_EINVAL, "%s: row_off[0] = %lld, must be 0", who, (long long)row_off[0]);
+        for (int64_t i = 0; i < n; i++) {
+            if (row_off[i + 1] < row_off[i]) return fail(BXMI_EINVAL, "%s: row_off descends at row %lld", who, (long long)i);
+            if (row_off[i + 1] - row_off[i] > 2147483647LL)
+                return fail(BXMI_EINVAL, "%s: row %lld has %lld elements, more than 2^31-1", who, (long long)i, (long long)(row_off[i + 1] - row_off[i]));
+        }
+        if (row_off[n] != total) return fail(BXMI_EINVAL, "%s: row_off[n] = %lld, but total = %lld", who, (long long)row_off[n], (long long)total);
+    }
+    BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    if (n == 0 || total == 0) return BXMI_OK;
+    std::lock_guard<std::mutex> hold(g_sequence.lock);
+    BXMI_TRY(g_sequence.enter(true));
+    SequenceBufs &S = g_sequence.bufs;
+    const hipStream_t st = g_sequence.stream;
+    BXMI_TRY(sequence_fill_table(S, tracks, n_tracks, st));
+    for (int64_t o0 = 0; o0 < total; o0 += TB_SLAB) {  // slabs of whole tiles; a row may lie in several
+        const int64_t count = total - o0 < TB_SLAB ? total - o0 : TB_SLAB;
+        const SaRows rows = sa_rows_of(row_off, n, width, o0, count);  // the slab's rows
+        const int64_t r0 = rows.r0, m = rows.m;
+        const size_t in_bytes = (size_t)m * sizeof(int32_t), off_bytes = (size_t)(m + 1) * sizeof(int64_t);
+        BXMI_TRY(S.q_track.reserve(in_bytes));
+        BXMI_TRY(S.q_start.reserve(in_bytes));
+        BXMI_TRY(S.r.reserve((size_t)count));
+        BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of + r0, in_bytes, hipMemcpyHostToDevice, st));
+        BXMI_HIP(hipMemcpyAsync(S.q_start.p, start + r0, in_bytes, hipMemcpyHostToDevice, st));
+        if (row_off) {  // (q_end holds the slab's offsets)
+            BXMI_TRY(S.q_end.reserve(off_bytes));
+            BXMI_HIP(hipMemcpyAsync(S.q_end.p, row_off + r0, off_bytes, hipMemcpyHostToDevice, st));
+        }
+        BXMI_TRY(bases_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), m, r0, width, row_off ? S.q_end.as<int64_t>() : nullptr, o0, count,
+                              do_mask != 0, pad, S.r.as<uint8_t>(), st));
+        BXMI_HIP(hipMemcpyAsync(out + o0, S.r.p, (size_t)count, hipMemcpyDeviceToHost, st));
+        BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
+    }
+    return BXMI_OK;
+}
+
+// ---- base counts (tb_composition_kernel) ----
+static int composition_check(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const void *track_of, const void *start, const void *end,
+                             int64_t n, const void *counts)
+{
+    BXMI_TRY(track_batch_check(who, "width", 1, tracks, n_tracks, n));
+    if (n > 0 && (!track_of || !start || !end || !counts)) return fail(BXMI_EINVAL, "%s: NULL array", who);
+    return BXMI_OK;
+}
+
+static int composition_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, int64_t n, int do_mask,
+                              int32_t *counts, hipStream_t st)
+{
+    for (int64_t first = 0; first < n; first += TB_ROWS_PER_LAUNCH) {
+        const int64_t m = n - first < TB_ROWS_PER_LAUNCH ? n - first : TB_ROWS_PER_LAUNCH;
+        hipLaunchKernelGGL(tb_composition_kernel, dim3((unsigned)m), dim3(TB_WAVE), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of + first,
+                           start + first, end + first, do_mask, counts + 6 * first);
+        BXMI_LAUNCH_CHECK();
+    }
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_twobit_composition_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                           const int32_t *end, int64_t n, int do_mask, int32_t *counts, void *stream)
+{
+    const char *who = "bxmi_twobit_composition_dev";
+    BXMI_TRY(composition_check(who, tracks, n_tracks, track_of, start, end, n, counts));
+    if (n == 0) return BXMI_OK;
+    std::lock_guard<std::mutex> hold(g_sequence.lock);
+    BXMI_TRY(g_sequence.enter());
+    BXMI_TRY(sequence_fill_table(g_sequence.bufs, tracks, n_tracks, as_stream(stream)));
+    return composition_launch(g_sequence.bufs, n_tracks, track_of, start, end, n, do_mask != 0, counts, as_stream(stream));
+}
+
+extern "C" int bxmi_twobit_composition(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                                       int64_t n, int do_mask, int32_t *counts)
+{
+    const char *who = "bxmi_twobit_composition";
+    BXMI_TRY(composition_check(who, tracks, n_tracks, track_of, start, end, n, counts));
+    BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    if (n == 0) return BXMI_OK;
+    std::lock_guard<std::mutex> hold(g_sequence.lock);
+    BXMI_TRY(g_sequence.enter(true));
+    SequenceBufs &S = g_sequence.bufs;
+    const hipStream_t st = g_sequence.stream;
+    const int64_t slab = n < TB_COMP_SLAB ? n : TB_COMP_SLAB;
+    const size_t rows = (size_t)slab * sizeof(int32_t);
+    BXMI_TRY(S.q_track.reserve(rows));
+    BXMI_TRY(S.q_start.reserve(rows));
+    BXMI_TRY(S.q_end.reserve(rows));
+    BXMI_TRY(S.r.reserve(rows * 6));
+    BXMI_TRY(sequence_fill_table(S, tracks, n_tracks, st));
+    for (int64_t first = 0; first < n; first += slab) {
+        const int64_t m = n - first < slab ? n - first : slab;
+        const size_t in_bytes = (size_t)m * sizeof(int32_t);
+        BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of + first, in_bytes, hipMemcpyHostToDevice, st));
+        BXMI_HIP(hipMemcpyAsync(S.q_start.p, start + first, in_bytes, hipMemcpyHostToDevice, st));
+        BXMI_HIP(hipMemcpyAsync(S.q_end.p, end + first, in_bytes, hipMemcpyHostToDevice, st));
+        BXMI_TRY(composition_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), S.q_end.as<int32_t>(), m, do_mask != 0, S.r.as<int32_t>(), st));
+        BXMI_HIP(hipMemcpyAsync(counts + 6 * first, S.r.p, in_bytes * 6, hipMemcpyDeviceToHost, st));
+        BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
+    }
+    return BXMI_OK;
+}

@@ -30,6 +30,8 @@
  *                                ZoomLevel._summarize: summarize / query from a zoom level -> bxmi_zoom_*
  *   lib/bx/bbi/bigbed_file.pyx:57-76,104-113
  *                                BigBedFile.summarize_from_full / query over full data -> bxmi_beds_*
+ *   lib/bx/seq/_twobit.pyx:22-137, twobit.py:34-56
+ *                                TwoBitSequence.get / __getitem__, a batch of regions per call -> bxmi_twobit_*
  *   (intersection.pyx has no C ABI of its own: its cdef classes are the
  *    interface, so the entry points below are what a Cython/ctypes shim of
  *    those classes binds; see INTEGRATION.md.)
@@ -531,6 +533,52 @@ int bxmi_beds_summarize(bxmi_beds_t *const *tracks, int32_t n_tracks, const int3
 /* Device variant, as bxmi_spans_summarize_dev. */
 int bxmi_beds_summarize_dev(bxmi_beds_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
                             int64_t n, int32_t size, double *valid, double *min, double *max, double *sum, double *sumsq, void *stream);
+
+/* ---- 2bit tracks: the sequence under batches of rows and its base counts  (lib/bx/seq/twobit.py, _twobit.pyx) ----------
+ * One bxmi_twobit_t is ONE sequence of a .2bit file in HBM (bxmi.twobit.read_file returns its arrays): `size` bases packed 4 to a
+ * byte, the first base in the two most significant bits, codes T=0 C=1 A=2 G=3; n_blocks N blocks [n_start[i], n_start[i] +
+ * n_size[i]) and m_blocks mask blocks likewise.  _create accepts only what every real file holds and refuses anything else with
+ * BXMI_EINVAL, the message naming the condition, before the first device call: 0 <= size <= 2^31-1 and, within each list, blocks
+ * sorted, non-empty, disjoint and inside [0, size].  Under those conditions the reference's bisect-and-walk over the blocks
+ * (_twobit.pyx:100-133: it starts one block before the first that starts after the region and stops at the first that starts past
+ * it) is plain coverage -- a position is N, or masked, exactly where a block covers it -- and that is why the condition is there:
+ * with overlapping or unsorted blocks the walk can miss a block that covers the region, which no kernel should imitate.
+ * Creation also builds, on the device, the running code counts per checkpoint block of 1024 bases and under the N blocks that
+ * bxmi_twobit_composition answers from (csrc/twobit.hpp). */
+typedef struct bxmi_twobit bxmi_twobit_t;
+int bxmi_twobit_create(const uint8_t *packed, int64_t size, const int32_t *n_start, const int32_t *n_size, int64_t n_blocks,
+                       const int32_t *m_start, const int32_t *m_size, int64_t m_blocks, bxmi_twobit_t **out);
+int bxmi_twobit_destroy(bxmi_twobit_t *h);
+int bxmi_twobit_info(const bxmi_twobit_t *h, int64_t *size, int64_t *n_blocks, int64_t *m_blocks);
+/* _twobit.read for a batch of n rows, the contract of bxmi_spans_arrays with bytes for floats: element j of row i is position p =
+ * start[i] + j (taken in 64 bits) of tracks[track_of[i]] and holds the ASCII letter the reference's string has there: "TCAG" by
+ * code, 'N' inside an N block, lower case inside a mask block when do_mask != 0 (so 'n' inside both).  It holds the byte `pad`
+ * (0 .. 255) where p is outside [0, size) and where track_of[i] is outside [0, n_tracks).  Matrix form (row_off_or_null == NULL,
+ * width >= 1, total == n * width) and ragged form (width == 0, row_off[n + 1] from 0 to total, never descending, no row longer than
+ * 2^31-1), the argument errors, n == 0 and total == 0: exactly as bxmi_spans_arrays.  The work is cut into tiles of the OUTPUT:
+ * rows of one base and rows of a whole chromosome cost their bases.  The track table and the staging belong to the library: one
+ * 2bit call (bases or composition) at a time per process; the summaries' calls are not involved.  Host arrays; goes through the
+ * device in slabs of output and BLOCKS until `out` is written. */
+int bxmi_twobit_bases(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                      const int64_t *row_off_or_null, int64_t total, int do_mask, int pad, uint8_t *out);
+/* Device variant: `tracks` stays a host array of handles; track_of, start, row_off and out are device pointers.  Where `out` is
+ * 16-byte aligned every full group of 16 bytes is written by one 16-byte store; any other `out` gives the same bytes, more slowly.
+ * Stream-ordered on `stream`, no host synchronisation.  Unchecked entries as bxmi_spans_arrays_dev: a track_of[i] outside
+ * [0, n_tracks) gives a row of `pad`; whatever row_off holds, nothing outside out[0 .. total) is written. */
+int bxmi_twobit_bases_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                          const int64_t *row_off_or_null, int64_t total, int do_mask, int pad, uint8_t *out, void *stream);
+/* Base counts of n rows: counts is [n, 6] int32 = A, C, G, T, N, masked of [start[i], end[i]) clipped to [0, size) of
+ * tracks[track_of[i]].  N = the bases inside N blocks; A, C, G, T = the bases by code OUTSIDE N blocks (a file may pack anything
+ * under an N); masked = the bases inside mask blocks, 0 when do_mask == 0: what counting the characters of the reference's string
+ * gives, case folded for the first five, the lower-case ones for the sixth.  track_of[i] outside [0, n_tracks) (the host form
+ * refuses one >= n_tracks) or an empty row gives six zeros.  A row costs two searches per list of blocks, two 16-byte checkpoint
+ * loads and a few edge pieces of at most 256 packed bytes, WHATEVER ITS LENGTH.  n outside [0, 2^31-1], n_tracks < 0 ->
+ * BXMI_EINVAL; n == 0 succeeds without a launch.  Table, staging and the one-call-at-a-time rule: as bxmi_twobit_bases. */
+int bxmi_twobit_composition(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                            int64_t n, int do_mask, int32_t *counts);
+/* Device variant: device pointers of natural alignment, stream-ordered on `stream`, no host synchronisation. */
+int bxmi_twobit_composition_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                                int64_t n, int do_mask, int32_t *counts, void *stream);
 
 /* ---- BED text -> SoA columns on the host (the step before the hot path) ------
  * Strict single-pass parser for what lib/bx/bitset_builders.py:33-46 and
