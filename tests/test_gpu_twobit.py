@@ -1,8 +1,10 @@
 """
 2bit sequence and base counts on the device (bxmi_twobit_*, bxmi.sequence, bx.seq.twobit.TwoBitFile, bxmi.cli.twobit_intervals_to_fasta)
 against the strings recorded from the reference's bx.seq.twobit (tests/golden/twobit) and, beyond them, against
-tests/twobit_model.py -- itself pinned to those recordings by tests/test_twobit_model_golden.py.  Every comparison is of bytes.
+tests/twobit_model.py -- itself pinned to those recordings by tests/test_twobit_model_golden.py -- and, at scale, against the window
+and running-count models of tests/twobit_cases.py, pinned to that one by tests/test_twobit_cases.py.  Every comparison is of bytes.
 """
+import contextlib
 import io
 import os
 import subprocess
@@ -11,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+import twobit_cases as K
 import twobit_model as M
 
 pytestmark = pytest.mark.gpu
@@ -236,6 +239,263 @@ def test_no_rows_and_bad_arguments(structural):
         sequence.TwoBitTrack.from_arrays(seq.packed, seq.size, [3, 5], [4, 2])
     with pytest.raises(ValueError):
         sequence.matrix(tracks, [0], [0], 4, pad=b"NN")
+
+
+# ------------------------------------------------------------ seeded cases and scale, host forms and _dev forms --
+# Two limits of csrc/sequence.hip are deliberately not reached: TB_ROWS_PER_LAUNCH (2^25 rows per launch of the base counts: 768 MiB
+# of counts and as much model) and TB_TILES_PER_LAUNCH (2^22 tiles: 16 GiB of letters).  Neither can be had in seconds.
+def bases_host(tracks, track_of, starts, do_mask, pad, width=0, lengths=None):
+    """bxmi_twobit_bases as it stands (no clipping), `out` filled with the sentinel first -> uint8[total]"""
+    from bxmi import _ffi as ffi
+
+    t, s = np.ascontiguousarray(track_of, dtype=np.int32), np.ascontiguousarray(starts, dtype=np.int32)
+    offsets = None if lengths is None else np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    out = np.full(len(t) * width if offsets is None else int(offsets[-1]), SENTINEL, dtype=np.uint8)
+    ffi.call("bxmi_twobit_bases", ffi.handles(tracks), len(tracks), ffi.ptr(t), ffi.ptr(s), len(t), width, ffi.ptr(offsets), len(out), int(do_mask), pad,
+             ffi.ptr(out))
+    return out
+
+
+def bases_dev(tracks, track_of, starts, do_mask, pad, width=0, lengths=None, lead=64, tail=37):
+    """bxmi_twobit_bases_dev on arrays in device memory, on the null stream, `out` `lead` bytes into an allocation of sentinel
+    bytes, which must still be there on both sides afterwards -> uint8[total]"""
+    from bxmi import _ffi as ffi
+
+    offsets = None if lengths is None else np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    total = len(track_of) * width if offsets is None else int(offsets[-1])
+    rows = [ffi.DeviceArray.from_numpy(np.ascontiguousarray(a, dtype=np.int32)) for a in (track_of, starts)]
+    rows += [ffi.DeviceArray.from_numpy(offsets)] if offsets is not None else []
+    out = ffi.DeviceArray.from_numpy(np.full(lead + total + tail, SENTINEL, dtype=np.uint8))
+    assert out.ptr % 16 == 0
+    ffi.call("bxmi_twobit_bases_dev", ffi.handles(tracks), len(tracks), rows[0].ptr, rows[1].ptr, len(track_of), width,
+             rows[2].ptr if offsets is not None else None, total, int(do_mask), pad, out.ptr + lead, None)
+    ffi.call("bxmi_synchronize", None)
+    data = out.to_numpy(np.uint8)
+    for a in rows + [out]:
+        a.free()
+    assert (data[:lead] == SENTINEL).all() and (data[lead + total:] == SENTINEL).all(), "written outside the output"
+    return data[lead:lead + total]
+
+
+def counts_host(tracks, track_of, starts, ends, do_mask):
+    from bxmi import sequence
+
+    got = sequence.composition(tracks, track_of, starts, ends, do_mask)
+    assert got.dtype == np.int32 and got.shape == (len(track_of), 6)
+    return got
+
+
+def counts_dev(tracks, track_of, starts, ends, do_mask, lead=3, tail=5):
+    """bxmi_twobit_composition_dev, sentinels before and after the counts -> int32 [n, 6]"""
+    from bxmi import _ffi as ffi
+
+    n = len(track_of)
+    rows = [ffi.DeviceArray.from_numpy(np.ascontiguousarray(a, dtype=np.int32)) for a in (track_of, starts, ends)]
+    out = ffi.DeviceArray.from_numpy(np.full(lead + 6 * n + tail, -7, dtype=np.int32))
+    ffi.call("bxmi_twobit_composition_dev", ffi.handles(tracks), len(tracks), rows[0].ptr, rows[1].ptr, rows[2].ptr, n, int(do_mask), out.ptr + 4 * lead, None)
+    ffi.call("bxmi_synchronize", None)
+    words = out.to_numpy(np.int32)
+    for a in rows + [out]:
+        a.free()
+    assert (words[:lead] == -7).all() and (words[lead + 6 * n:] == -7).all(), "written outside the counts"
+    return words[lead:lead + 6 * n].reshape(n, 6)
+
+
+def through_device(tracks):
+    """the `bases` and `counts` of twobit_cases.check_random_case: the host form's answer, which the _dev form's must equal (the
+    letters with `out` 16-byte aligned and one byte past that)"""
+
+    def bases(_seqs, track_of, starts, do_mask, pad, width=0, lengths=None):
+        got = bases_host(tracks, track_of, starts, do_mask, pad, width, lengths)
+        for lead in (64, 1):
+            assert np.array_equal(bases_dev(tracks, track_of, starts, do_mask, pad, width, lengths, lead=lead), got), ("device form", lead)
+        return got
+
+    def counts(_seqs, track_of, starts, ends, do_mask):
+        got = counts_host(tracks, track_of, starts, ends, do_mask)
+        assert np.array_equal(counts_dev(tracks, track_of, starts, ends, do_mask), got), "device form"
+        return got
+
+    return bases, counts
+
+
+@contextlib.contextmanager
+def on_device(seqs):
+    """the sequences as tracks on the device, closed again whatever the test does with them"""
+    from bxmi import sequence
+
+    tracks = []
+    try:
+        for s in seqs:
+            tracks.append(sequence.TwoBitTrack(s))
+        yield tracks
+    finally:
+        for t in tracks:
+            t.close()
+
+
+@pytest.mark.parametrize("seed", K.RANDOM_SEEDS)
+def test_random_sequences(seed):
+    """tests/test_twobit_kernel_host.py::test_random_sequences on the device: the same sequences, rows and comparisons"""
+    with on_device(K.random_case(seed)["seqs"]) as tracks:
+        K.check_random_case(seed, *through_device(tracks))
+
+
+def test_many_chunks_and_sixteen_blocks_in_a_thread():
+    """tests/test_twobit_kernel_host.py's test of that name on the device"""
+    with on_device(K.many_blocks_case()["seqs"]) as tracks:
+        K.check_many_blocks_case(*through_device(tracks))
+
+
+@pytest.fixture(scope="module")
+def big_tracks():
+    """the two sequences of twobit_cases.big_sequence on the device, each made when first asked for"""
+    from bxmi import sequence
+
+    made = {}
+
+    def get(which):
+        if which not in made:
+            made[which] = sequence.TwoBitTrack(K.big_sequence(which))
+        return made[which]
+
+    yield get
+    for t in made.values():
+        t.close()
+
+
+@pytest.mark.parametrize("which", (0, 1))
+def test_tables_beyond_one_scan_tile(big_tracks, which):
+    """10 241 and 6 143 checkpoints, 7 000 N blocks: every plane of both running tables is scanned in several tiles of the device
+    scan, the planes 16-byte aligned (stride 6 144) or not (10 242; 7 001).  40 000 random rows and rows cut around the tiles'
+    edges against the running-count model, every 500th row counted from its own letters; 2 000 windows and 100 ragged rows
+    against the letters of their windows.  (The row counts are what the time allows: the letters of 10 M bases and their six
+    running counts cost what they cost, whatever the rows.)"""
+    seq, facts = K.big_conditions(which)
+    assert facts["stride"] == (10242, 6144)[which] and facts["stride"] % 4 == (2, 0)[which] and (len(seq.n_starts) + 1) % 2 == 1
+    assert facts["rows over N block 2048"] > 100 and facts["rows over checkpoint 2048"] > 100
+    track = big_tracks(which)
+    assert (track.size, track.n_blocks, track.m_blocks) == (seq.size, K.BIG_N_BLOCKS, K.BIG_M_BLOCKS)
+    whole = K.big_letters(which)
+    starts, ends = K.big_composition_rows(which)
+    zeros = np.zeros(len(starts), dtype=np.int32)
+    want = K.big_composition_want(which)
+    for i in range(0, len(starts), 500):
+        s, e = max(int(starts[i]), 0), min(int(ends[i]), seq.size)
+        assert want[i].tolist() == K.counts_of_letters(whole[s:e]), i
+    assert (want > 0).any(axis=0).all() and int(want[:, :5].sum(axis=1).max()) == seq.size
+    got = counts_host([track], zeros, starts, ends, True)
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert len(bad) == 0, (len(bad), [(int(starts[i]), int(ends[i]), got[i].tolist(), want[i].tolist()) for i in bad[:5]])
+    assert np.array_equal(counts_dev([track], zeros, starts, ends, True), want)
+    unmasked = want[::7].copy()
+    unmasked[:, 5] = 0  # (without do_mask the letters are these in upper case)
+    assert np.array_equal(counts_host([track], zeros[::7], starts[::7], ends[::7], False), unmasked)
+    # letters
+    rng = np.random.default_rng(340 + which)
+    n, width = 2000, 100
+    at = rng.integers(-50, seq.size - 49, n)
+    at[:4] = (-50, -1, seq.size - 99, seq.size - 50)
+    want = np.stack([K.window_row([seq], 0, int(a), width, True, ord("-")) for a in at])
+    got = bases_host([track], zeros[:n], at, True, ord("-"), width=width)
+    assert np.array_equal(got.reshape(n, width), want)
+    assert np.array_equal(bases_dev([track], zeros[:n], at, True, ord("-"), width=width).reshape(n, width), want)
+    lengths = K.log_uniform(rng, 1, 3 * M.TILE + 1, 100) - 1
+    at = rng.integers(-50, seq.size - 49, 100)
+    at[:2], lengths[:2] = (seq.size - 3 * M.TILE + 9, 17), (3 * M.TILE, 3 * M.TILE)
+    for do_mask in (True, False):
+        want = K.window_bases([seq], zeros[:100], at, lengths, do_mask, ord("."))
+        assert np.array_equal(bases_host([track], zeros[:100], at, do_mask, ord("."), lengths=lengths), want), do_mask
+        assert np.array_equal(bases_dev([track], zeros[:100], at, do_mask, ord("."), lengths=lengths, lead=7), want), do_mask
+
+
+def test_host_forms_go_through_more_than_one_slab(big_tracks):
+    """bxmi_twobit_bases in slabs of 2^26 output bytes -- 17 rows of 2^22 + 3 bases, then ragged rows of 0 to 2^23 + 9, a slab
+    ending inside a row both times -- and bxmi_twobit_composition in slabs of 2^22 rows; the letters wanted are slices of the
+    whole sequence's"""
+    from bxmi import sequence
+
+    seq, track, whole = K.big_sequence(0), big_tracks(0), K.big_letters(0)
+    width, n = (1 << 22) + 3, 17
+    assert n * width > K.TB_SLAB and K.TB_SLAB % width != 0
+    starts = np.arange(n, dtype=np.int32) * 37 - 5
+    want = np.full((n, width), ord("-"), dtype=np.uint8)
+    for i, s in enumerate(starts.tolist()):
+        want[i, max(-s, 0):] = whole[max(s, 0):s + width]
+    got = sequence.matrix([track], np.zeros(n, dtype=np.int32), starts, width, pad=b"-")
+    assert got.shape == want.shape and np.array_equal(got, want)
+    big = 1 << 23
+    lengths = np.array([5, big + 1, 0, 1, big - 7, 3, big + 2, 0, big, 1000, big + 9, 2, big - 1, big + 5, big, 77, big + 3, 4, big - 2, 999], dtype=np.int64)
+    assert lengths.sum() > K.TB_SLAB + (1 << 22) and K.TB_SLAB not in np.cumsum(lengths)
+    starts = (np.arange(len(lengths), dtype=np.int32) * 53) % 1100 - 5
+    offsets = np.concatenate([[0], np.cumsum(lengths)])
+    want = np.full(int(offsets[-1]), ord("."), dtype=np.uint8)
+    for i, (s, m) in enumerate(zip(starts.tolist(), lengths.tolist())):
+        want[offsets[i] + max(-s, 0):offsets[i + 1]] = whole[max(s, 0):s + m] & ~np.uint8(0x20)
+    got = bases_host([track], np.zeros(len(lengths), dtype=np.int32), starts, False, ord("."), lengths=lengths)
+    assert np.array_equal(got, want)
+    del got, want
+    # base counts: 2^22 + 1001 rows drawn from those of test_tables_beyond_one_scan_tile, whose counts the model has (the running
+    # counts of 10 M letters are made once); the rows on both sides of the slab's edge have three different, known answers
+    n = K.TB_COMP_SLAB + 1001
+    pool_starts, pool_ends = K.big_composition_rows(0)
+    idx = np.random.default_rng(350).integers(0, len(pool_starts), n)
+    edge = K.TB_COMP_SLAB
+    idx[edge - 1:edge + 2] = (len(pool_starts) - 3, len(pool_starts) - 2, len(pool_starts) - 1)
+    starts, ends, want = pool_starts[idx], pool_ends[idx], K.big_composition_want(0)[idx]
+    assert len(np.unique(idx)) > len(pool_starts) // 2
+    # (0, size), (size - 3, size + 100) and (0, the end of N block 2048): three different answers, each counted from its letters
+    cut = int(seq.n_starts[2048] + seq.n_sizes[2048])
+    known = [K.counts_of_letters(whole), K.counts_of_letters(whole[seq.size - 3:]), K.counts_of_letters(whole[:cut])]
+    assert list(zip(starts[edge - 1:edge + 2].tolist(), ends[edge - 1:edge + 2].tolist())) == [(0, seq.size), (seq.size - 3, seq.size + 100), (0, cut)]
+    assert want[edge - 1:edge + 2].tolist() == known and len({tuple(k) for k in known}) == 3 and all(sum(k) > 0 for k in known) and (want[edge - 1] > 0).all()
+    got = counts_host([track], np.zeros(n, dtype=np.int32), starts, ends, True)
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert len(bad) == 0, (len(bad), bad[:5].tolist(), got[bad[:5]].tolist(), want[bad[:5]].tolist())
+
+
+def test_sequence_at_the_top_of_int32():
+    """2^31 - 1 bases (twobit_cases.TopSequence): positions, running sizes and running counts next to the top of int32 -- the T
+    count of the whole sequence is beyond 2^30, its masked count 14 000 below 2^31 -- in rows at the sequence's end, across it,
+    and across the edges of an N block of 2^28 bases and of a mask block of nearly everything"""
+    top = K.top_sequence()
+    with on_device([top.seq]) as tracks:  # (512 MiB of device memory: given back whatever happens)
+        check_top_sequence(top, tracks[0])
+
+
+def check_top_sequence(top, track):
+    from bxmi import sequence
+
+    size, half = top.size, 1 << 30
+    assert (track.size, track.n_blocks, track.m_blocks) == (size, len(top.seq.n_starts), len(top.seq.m_starts)) and size == 2 ** 31 - 1
+    # letters: windows of 100 (the pad belongs to the matrix form) and of TILE + 1
+    at = [size - 100, size - 1, size, size - 50, size - 99, K.TOP_N[0] - 50, K.TOP_N[1] - 50, K.TOP_N[0] - 100, K.TOP_N[1], K.TOP_MASK[0] - 50, K.TOP_MASK[1] - 50,
+          half - 2048 - 50, half - 50, half + 2048 - 50, size - 8192 - 50, size - 4097 - 40, -50, 4096 - 50, 0]
+    zeros = np.zeros(len(at), dtype=np.int32)
+    for width in (100, M.TILE + 1):
+        starts = [a - (width - 100) // 2 for a in at[3:]] + at[:3]
+        for do_mask in (True, False):
+            want = np.stack([top.row(s, width, do_mask, ord("-")) for s in starts])
+            if width == 100:  # the last three rows: up to the size, its last base and pad, pad only
+                assert not (want[-3] == ord("-")).any() and want[-2, 0] != ord("-") and (want[-2, 1:] == ord("-")).all() and (want[-1] == ord("-")).all()
+            got = bases_host([track], zeros, starts, do_mask, ord("-"), width=width).reshape(len(at), width)
+            assert np.array_equal(got, want), (width, do_mask, [starts[i] for i in np.flatnonzero((got != want).any(axis=1))])
+            assert np.array_equal(bases_dev([track], zeros, starts, do_mask, ord("-"), width=width).reshape(len(at), width), want), (width, do_mask)
+    # the clipped regions of the Python layer: rows that end at the size, the last base, nothing
+    starts, ends = [size - 3000, size - 1, size, half - 10, -5, K.TOP_MASK[1] - 7], [size, size, size, half + 10, 12, K.TOP_MASK[1] + 7]
+    data, offsets = sequence.sequences([track], [0] * len(starts), starts, ends)
+    assert np.diff(offsets).tolist() == [3000, 1, 0, 20, 12, 14]
+    assert np.array_equal(data, np.concatenate([top.letters(max(s, 0), e) for s, e in zip(starts, ends)]))
+    # base counts
+    starts = [0, 1, K.TOP_N[0] - 3, half - 10, half - 3000, half, half - 1, size - 1, size - 1, size, size - 8192, 0, K.TOP_MASK[0] - 1, -7]
+    ends = [size, size - 1, K.TOP_N[1] + 3, half + 10, half + 3000, half + 1, half, size, size, size, size, half, K.TOP_MASK[1] + 1, size]
+    for do_mask in (True, False):
+        want = top.composition(starts, ends, do_mask)
+        assert want[0, 3] > half and want[0, :5].sum() == size and (want[0, 5] > 2 ** 31 - 20000) == do_mask and want.max() < 2 ** 31
+        assert want[7].sum() == 1 + do_mask and want[9].sum() == 0 and want[2].tolist()[:5] == [0, 0, 0, 6, 1 << 28]
+        got = counts_host([track], [0] * len(starts), starts, ends, do_mask)
+        assert np.array_equal(got, want), (do_mask, got.tolist(), want.tolist())
+        assert np.array_equal(counts_dev([track], [0] * len(starts), starts, ends, do_mask), want), (do_mask, "device form")
 
 
 # ------------------------------------------------------------ device entry points on torch tensors --

@@ -5,11 +5,14 @@ recorded reference string and the model's answer on the structural cases of the 
 empty rows, rows inside an N block, more one-base blocks in a segment than a chunk stages, pad on both sides, rows without a
 track, the size-0 sequence, widths that are no multiple of 16, an output off a 16-byte boundary, the output cut into slabs; and
 the base counts of rows inside one checkpoint block, on checkpoints, over everything, ending at a size that is no multiple of 4.
+Then the seeded cases of tests/twobit_cases.py: random sequences that carry every block edge under random ragged rows, windows and
+count rows, and a sequence where one segment meets six chunks of one-base blocks and a thread's 16 positions are 16 blocks.
 This is the kernels' logic and indexing; tests/test_gpu_twobit.py checks the same cases on the device."""
 import numpy as np
 import pytest
 
 import kernel_host
+import twobit_cases as K
 import twobit_model as M
 
 GUARD = 64
@@ -108,3 +111,27 @@ def test_nothing_to_do(kernel):
     assert len(kernel(seqs, [], [], width=5)) == 0
     assert len(kernel(seqs, [0, 1], [3, 4], offsets=np.zeros(3, dtype=np.int64))) == 0
     assert kernel(seqs, [], [], ends=[]).shape == (0, 6)
+
+
+def through(kernel):
+    """the program as the `bases` and `counts` of twobit_cases.check_random_case"""
+
+    def bases(seqs, track_of, starts, do_mask, pad, width=0, lengths=None):
+        return kernel(seqs, track_of, starts, width=width, offsets=None if lengths is None else offsets_of(lengths), do_mask=do_mask, pad=pad)
+
+    def counts(seqs, track_of, starts, ends, do_mask):
+        return kernel(seqs, track_of, starts, ends=ends, do_mask=do_mask)
+
+    return bases, counts
+
+
+@pytest.mark.parametrize("seed", K.RANDOM_SEEDS)
+def test_random_sequences(kernel, seed):
+    """four random sequences with every block edge (twobit_cases.random_sequence), random ragged rows, windows of widths 1, 37
+    and TILE + 1, random base-count rows: tests/test_gpu_twobit.py gives the device the same"""
+    K.check_random_case(seed, *through(kernel))
+
+
+def test_many_chunks_and_sixteen_blocks_in_a_thread(kernel):
+    """1500 one-base N blocks in one segment, 1200 adjacent one-base mask blocks, their starts at every byte of a thread's 16"""
+    K.check_many_blocks_case(*through(kernel))
