@@ -199,3 +199,61 @@ def matrix_case(width):
         starts = starts.astype(np.int32)
         _cache[key] = (ts, track_of, starts, matrix(ts, track_of, starts, width))
     return _cache[key]
+
+
+# ------------------------------------------------------------ items that end at 2^31 - 1 --
+INT32_MAX = 2 ** 31 - 1
+TOP_WIDTHS = (3, TILE + 1)
+
+
+def top_tracks():
+    """0 ordered with overlaps (2000 items), 1 not ordered (300 items): every coordinate shifted (in int64) so that the track's last
+    end is exactly 2^31 - 1, the last position that can hold data 2^31 - 2"""
+    if "top tracks" not in _cache:
+        rng = np.random.default_rng(43)
+        out = []
+        for s, e, v in (random_track(rng, 2000), random_track(rng, 300, ordered=False)):
+            shift = INT32_MAX - int(e.max())
+            out.append(((s.astype(np.int64) + shift).astype(np.int32), (e.astype(np.int64) + shift).astype(np.int32), v))
+        assert [is_ordered(t) for t in out] == [True, False] and all(int(t[1].max()) == INT32_MAX and t[0].min() >= 0 for t in out)
+        _cache["top tracks"] = out
+    return _cache["top tracks"]
+
+
+def top_ragged_case():
+    """(tracks, track_of, starts int32, ends INT64, (values, offsets) of the model, n_fit): on both tracks and on none, rows of
+    1 ... 3 TILE + 7 bases whose last position is 2^31 - 2 (end == 2^31 - 1), 24 seeded rows inside the last 100000 bases and the
+    whole of the unordered track; then, from row n_fit on, rows whose end lies BEYOND 2^31 - 1 (NaN from position 2^31 - 1 on),
+    which only a form that takes offsets can be given: one of them starts at 2^31 - 1 itself"""
+    if "top ragged" not in _cache:
+        rng = np.random.default_rng(44)
+        ts = top_tracks()
+        rows = [(t, INT32_MAX - length, INT32_MAX) for t in (0, 1, -1) for length in (1, 2, 5, TILE - 1, TILE + 1, 3 * TILE + 7)]
+        for _ in range(24):
+            s = INT32_MAX - int(rng.integers(1, 100000))
+            rows.append((int(rng.integers(-1, 2)), s, min(s + int(rng.integers(1, 3000)), INT32_MAX)))
+        rows.append((1, int(ts[1][0].min()) - 3, INT32_MAX))
+        n_fit = len(rows)
+        rows += [(t, INT32_MAX - length, INT32_MAX + beyond) for t in (0, 1) for length, beyond in ((1, 1), (0, 4), (5, 3), (TILE, TILE + 9), (2 * TILE + 3, 1))]
+        track_of, starts = (np.array(c, dtype=np.int32) for c in list(zip(*rows))[:2])
+        ends = np.array([r[2] for r in rows], dtype=np.int64)
+        assert ends[:n_fit].max() == INT32_MAX and ends[n_fit:].min() > INT32_MAX and starts.max() == INT32_MAX
+        want = arrays(ts, track_of, starts, ends)
+        assert not np.isnan(want[0][want[1][0]:want[1][1]]).any()  # (track 0 has data at 2^31 - 2)
+        _cache["top ragged"] = (ts, track_of, starts, ends, want, n_fit)
+    return _cache["top ragged"]
+
+
+def top_matrix_case(width):
+    """(tracks, track_of, win_starts, the model's [n, width]): on both tracks and on none, windows whose last position is 2^31 - 2,
+    windows that run past it by 1 base, by half and by all but one of their bases, a window from 2^31 - 1 (nothing), and 24 seeded
+    ones inside the last 100000 bases"""
+    key = ("top matrix", width)
+    if key not in _cache:
+        rng = np.random.default_rng(2000 + width)
+        ts = top_tracks()
+        rows = [(t, s) for t in (0, 1, -1) for s in (INT32_MAX - width, INT32_MAX - width + 1, INT32_MAX - (width + 1) // 2, INT32_MAX - 1, INT32_MAX)]
+        rows += [(int(rng.integers(-1, 2)), INT32_MAX - int(rng.integers(1, 100000))) for _ in range(24)]
+        track_of, starts = (np.array(c, dtype=np.int32) for c in zip(*rows))
+        _cache[key] = (ts, track_of, starts, matrix(ts, track_of, starts, width))
+    return _cache[key]

@@ -1,9 +1,10 @@
 """
 Inputs and comparisons shared by the tests of the bigBed coverage summaries (tests/test_gpu_bed_summary.py on the device,
 tests/test_bed_summary_kernel_host.py on the host, tests/test_bigbed_model_golden.py on the model): the chunk size read out of
-bed_summary.hpp, what tools/record_bigbed_golden.py recorded under tests/golden/bigbed, seeded tracks and batches and the chunk
-cases with the model's answer -- tests/summary_model.py over the same records as items of value 1, which is what the reference
-computes (tests/test_bigbed_model_golden.py pins it to the recorded arrays).
+bed_summary.hpp, what tools/record_bigbed_golden.py recorded under tests/golden/bigbed, seeded tracks and batches, the chunk
+cases, the cases of more than 64 chunks (window_cases) and the tracks that end at 2^31 - 1 (top_case) with the model's answer --
+tests/summary_model.py over the same records as items of value 1, which is what the reference computes
+(tests/test_bigbed_model_golden.py pins it to the recorded arrays).
 """
 import json
 import os
@@ -12,6 +13,7 @@ import re
 import numpy as np
 
 import summary_model as M
+from summary_cases import TOP_SIZES, shifted_to_the_top, top_regions  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "bigbed")
@@ -204,3 +206,128 @@ def chunk_cases():
     cases.append(("the same records shuffled", [shuffled(rng, skip)], z2, s2, e2, 3))
     _chunk.extend(c + (model(c[1], c[2], c[3], c[4], c[5]),) for c in cases)
     return _chunk
+
+
+# ------------------------------------------------------------ chunk windows --
+# bd_summary_kernel tests a run's chunks 64 at a time (lane = chunk): a run of more than 64 chunks takes a second window
+WINDOW = 64
+
+
+def at(c):
+    """the start of record c of paced_records()"""
+    return 10 + 5 * c
+
+
+def paced_records(n):
+    """record k = [10 + 5 k, 10 + 5 k + 1 + (7 k mod 9)): sorted, 1 to 9 bases long, a start every 5 bases"""
+    k = np.arange(n, dtype=np.int64)
+    return at(k), at(k) + 1 + (7 * k) % 9
+
+
+def long_track():
+    """150 CHUNK + 77 paced records -- three windows of chunks, the last one partly filled, its last chunk partly filled -- with
+    three ends raised: record 0 ends 500 bases behind the last start (every region's first record is record 0), record
+    70 CHUNK + 13 ends 100 bases behind it (a far-reaching record inside the second window), record 100 CHUNK + 200 ends where record
+    140 CHUNK starts.  A region near the end stages chunk 0, chunk 70, perhaps chunk 100 and its own, and skips all between."""
+    starts, ends = paced_records(150 * CHUNK + 77)
+    ends[0], ends[70 * CHUNK + 13], ends[100 * CHUNK + 200] = starts[-1] + 500, starts[-1] + 100, at(140 * CHUNK)
+    return starts.astype(np.int32), ends.astype(np.int32)
+
+
+def plain_track():
+    """the records of long_track() without the raised ends: a region's first record is its own, so its first chunk is any chunk"""
+    starts, ends = paced_records(150 * CHUNK + 77)
+    return starts.astype(np.int32), ends.astype(np.int32)
+
+
+def big_track():
+    """2^20 + 77 paced records, 4097 chunks: record 0 spans everything, and every 100000th record reaches 40 chunks ahead"""
+    n = 2 ** 20 + 77
+    starts, ends = paced_records(n)
+    ends[0] = starts[-1] + 500
+    for k in range(100000, n - 40 * CHUNK, 100000):
+        ends[k] = at(k + 40 * CHUNK)
+    return starts.astype(np.int32), ends.astype(np.int32)
+
+
+def staged_chunks(track, s, e):
+    """(c_first, c_end, the chunks of [c_first, c_end) that the kernel stages) for the region [s, e) of a sorted track in ONE bin,
+    worked out from the definitions: the run [glo, ghi) is from the first record at or behind which something ends after s to the
+    first that starts at or after e; a chunk is staged when one of its records inside the run ends after s"""
+    starts, ends = (np.asarray(a, dtype=np.int64) for a in track)
+    glo = int(np.searchsorted(np.maximum.accumulate(ends), s, side="right"))
+    ghi = max(int(np.searchsorted(starts, e - 1, side="right")), glo)
+    c_first, c_end = glo // CHUNK, (ghi + CHUNK - 1) // CHUNK
+    return c_first, c_end, [c for c in range(c_first, c_end) if ends[c * CHUNK:min((c + 1) * CHUNK, ghi)].max() > s]
+
+
+_window = []
+
+
+def window_cases():
+    """[(label, tracks, track_of, starts, ends, size, the model's answer)]: runs of more than WINDOW chunks"""
+    if _window:
+        return _window
+    rng = np.random.default_rng(78)
+    long, plain, big = long_track(), plain_track(), big_track()
+    last = int(long[0][-1])
+    # on `long`: near the end; where record 100 CHUNK + 200 still reaches; two wide ones; everything; a narrow one; beyond the last
+    # short record, where only records 0 and 70 CHUNK + 13 reach
+    regions = [(at(149 * CHUNK + 5), 400), (at(140 * CHUNK - 3), 3000), (at(66 * CHUNK), 90 * CHUNK * 5), (at(5 * CHUNK + 9), 70 * CHUNK * 5),
+               (0, int(long[1][0])), (at(130 * CHUNK), 64), (last + 20, 70)]
+    wide = [2, 4]
+    starts = np.array([r[0] for r in regions], dtype=np.int32)
+    ends = np.array([r[0] + r[1] for r in regions], dtype=np.int32)
+    assert sorted(range(len(regions)), key=lambda k: regions[k][1])[-2:] == wide
+    c_first, c_end, staged = staged_chunks(long, starts[1], ends[1])
+    assert (c_first, c_end) == (0, 143) and staged[:3] == [0, 70, 100] and staged[3:] == list(range(139, 143)), (c_first, c_end, staged)
+    assert staged_chunks(long, starts[0], ends[0])[2] == [0, 70, 149] and staged_chunks(long, starts[6], ends[6]) == (0, 151, [0, 70])
+    assert staged_chunks(long, starts[4], ends[4])[2] == list(range(151))
+    zeros = np.zeros(len(regions), dtype=np.int32)
+    back = shuffled(rng, long)
+    # on `plain`: runs of exactly 63, 64, 65 and 128 chunks from an aligned first record and from one in the middle of chunk 5
+    runs = [(64 * CHUNK, 63), (64 * CHUNK, 64), (64 * CHUNK, 65), (16 * CHUNK, 128), (5 * CHUNK + 9, 63), (5 * CHUNK + 9, 64), (5 * CHUNK + 9, 65),
+            (5 * CHUNK + 9, 128)]
+    run_starts = np.array([at(first) for first, _ in runs], dtype=np.int32)
+    run_ends = np.array([at(first + r * CHUNK) for first, r in runs], dtype=np.int32)
+    spans = [staged_chunks(plain, s, e) for s, e in zip(run_starts, run_ends)]
+    assert [(c0, c1 - c0) for c0, c1, _ in spans] == [(64, 63), (64, 64), (64, 65), (16, 128), (5, 64), (5, 65), (5, 66), (5, 129)], spans
+    assert all(chunks == list(range(c0, c1)) for c0, c1, chunks in spans)
+    run_zeros = np.zeros(len(runs), dtype=np.int32)
+    cases = []
+    for size in (1, 3, 64, 65):
+        cases.append(("long, %d bins" % size, [long], zeros, starts, ends, size))
+        cases.append(("plain: runs of 63 to 129 chunks, %d bins" % size, [plain], run_zeros, run_starts, run_ends, size))
+        cases.append(("long shuffled: the general walk, %d bins" % size, [back], zeros, starts, ends, size))
+    cases.append(("long, the two widest regions, 200 bins", [long], zeros[wide], starts[wide], ends[wide], 200))
+    # the scenario of a whole chromosome: 200 regions of 50 to 50000 bases all over `big`, each with 64 windows or so to test
+    n = 200
+    big_starts = rng.integers(0, int(big[0][-1]), size=n)
+    big_ends = big_starts + (50 * 1000 ** rng.random(n)).astype(np.int64)
+    big_starts[:2], big_ends[:2] = (at(2 ** 20) - 30, at(400000 + 40 * CHUNK) - 40), (at(2 ** 20) + 49970, at(400000 + 40 * CHUNK) + 10)
+    assert (big_ends - big_starts).min() >= 50 and (big_ends - big_starts).max() <= 50000
+    c_first, c_end, staged = staged_chunks(big, big_starts[1], big_ends[1])
+    assert c_first == 0 and c_end > 8 * WINDOW and len(staged) <= 4 and 400000 // CHUNK in staged, (c_first, c_end, staged)
+    for size in (1, 65):
+        cases.append(("big, %d bins" % size, [big], np.zeros(n, dtype=np.int32), big_starts.astype(np.int32), big_ends.astype(np.int32), size))
+    _window.extend(c + (model(c[1], c[2], c[3], c[4], c[5]),) for c in cases)
+    return _window
+
+
+# ------------------------------------------------------------ records that end at 2^31 - 1 --
+_top = {}
+
+
+def top_case(size):
+    """(host tracks, track_of, starts, ends, the model's answer), once per size: a nested and a spanning track of 2000 records,
+    each shifted so that its furthest end is exactly 2^31 - 1, under summary_cases.top_regions()"""
+    if size not in _top:
+        rng = np.random.default_rng(600 + size)
+        tracks = []
+        for s, e in (nested_track(rng, 2000), spanning_track(rng, 1999)):
+            e, s = shifted_to_the_top(e, s)
+            tracks.append((s, e))
+        assert all(len(t[0]) == 2000 and int(t[1].max()) == INT32_MAX for t in tracks)
+        track_of, starts, ends = top_regions(rng, [t[0].min() for t in tracks], size)
+        _top[size] = (tracks, track_of, starts, ends, model(tracks, track_of, starts, ends, size))
+    return _top[size]

@@ -37,14 +37,18 @@ def summarize_region(track, start, end, size, fused=False, reverse=False):
     valid, mn, mx, sm, sq = [0.0] * size, [INF] * size, [-INF] * size, [0.0] * size, [0.0] * size
     step = (end - start) // size
     starts, ends, values = track
-    idx = overlapping(track, start, end) if step > 0 else []
-    for i in (idx[::-1] if reverse else idx):
-        s, e = max(int(starts[i]), start), min(int(ends[i]), end)
+    idx = overlapping(track, start, end) if step > 0 else np.zeros(0, dtype=np.intp)
+    if reverse:
+        idx = idx[::-1]
+    # the items' fields as Python numbers, converted once for the whole region (a long region walks tens of thousands of items)
+    val32 = np.asarray(values, dtype=np.float32)[idx]
+    with np.errstate(all="ignore"):
+        squares = (val32 * val32).astype(np.float64).tolist()  # the square is a float32 product
+    fields = zip(np.asarray(starts)[idx].tolist(), np.asarray(ends)[idx].tolist(), val32.astype(np.float64).tolist(), squares)
+    for item_start, item_end, v, v2 in fields:
+        s, e = max(item_start, start), min(item_end, end)
         if s >= e:
             continue
-        val32 = np.float32(values[i])
-        with np.errstate(all="ignore"):
-            v, v2 = float(val32), float(val32 * val32)  # the square is a float32 product
         n = e - s
         for j in range((s - start) // step, min((e - 1 - start) // step, size - 1) + 1):
             b0 = start + step * j

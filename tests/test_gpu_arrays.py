@@ -209,6 +209,35 @@ def test_matrix_of_every_width(width):
         t.close()
 
 
+def test_items_that_end_at_the_top_of_int32():
+    """tracks whose last end is 2^31 - 1: ragged rows that end there through the host form, the same and rows that run past it
+    through the device form (which takes offsets), and matrices whose windows end there or run past it through both"""
+    from bxmi import _ffi as ffi
+    from bxmi import summary
+
+    tracks, track_of, starts, ends, (want, want_offsets), n_fit = M.top_ragged_case()
+    dev = [summary.SpanTrack(*t) for t in tracks]
+    assert [t.ordered for t in dev] == [True, False]
+    values, offsets = summary.arrays(dev, track_of[:n_fit], starts[:n_fit], ends[:n_fit].astype(np.int32))
+    assert np.array_equal(offsets, want_offsets[:n_fit + 1])
+    M.assert_same(values, want[:want_offsets[n_fit]], "ragged, host form")
+    words = arrays_dev_raw(dev, track_of, starts, want_offsets, 64)
+    assert (words[:64] == SENTINEL).all() and (words[64 + len(want):] == SENTINEL).all()
+    M.assert_same(words[64:64 + len(want)].view(np.float32), want, "ragged, device form")
+    for width in M.TOP_WIDTHS:
+        _, track_of, starts, want = M.top_matrix_case(width)
+        M.assert_same(summary.matrix(dev, track_of, starts, width), want, ("matrix, host form", width))
+        rows = [ffi.DeviceArray.from_numpy(a) for a in (track_of, starts)]
+        out = ffi.DeviceArray(4 * want.size)
+        ffi.call("bxmi_spans_arrays_dev", ffi.handles(dev), len(dev), rows[0].ptr, rows[1].ptr, len(track_of), width, None, want.size, out.ptr, None)
+        ffi.call("bxmi_synchronize", None)
+        M.assert_same(out.to_numpy(np.float32, want.size).reshape(want.shape), want, ("matrix, device form", width))
+        for a in rows + [out]:
+            a.free()
+    for t in dev:
+        t.close()
+
+
 def test_host_form_goes_through_more_than_one_slab():
     """17 rows of 2^20 + 3 bases: more than the 2^24 output elements of one slab, which ends inside a row"""
     from bxmi import summary

@@ -13,8 +13,9 @@ import numpy as np
 import pytest
 
 import summary_model as M
-from bed_cases import (CHUNK, FILES, ROOT, SIZES, assert_planes, by_size, chunk_cases, differential_case, empty_planes, items, model, path_of, recorded,
-                       recorded_batch, with_ones)
+from bed_cases import (CHUNK, FILES, ROOT, SIZES, TOP_SIZES, WINDOW, assert_planes, by_size, chunk_cases, differential_case, empty_planes, items, model,
+                       nested_track, path_of, recorded, recorded_batch, top_case, window_cases, with_ones)
+from summary_cases import SLAB_SIZE, assert_slabs, slab_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -214,6 +215,57 @@ def test_chunk_edges():
         for t in dev:
             t.close()
     assert seen == {True, False}
+
+
+def test_chunk_windows():
+    """runs of more than WINDOW chunks, whose chunks the wave tests in a second and a third window: aligned and unaligned runs of
+    63 to 129 chunks, chunks to stage that lie far apart in two windows, the general walk over 151 chunks, and 200 regions all over
+    a track of 4097 chunks whose first record spans everything (bed_cases.window_cases)"""
+    from bxmi import summary
+
+    assert WINDOW == 64
+    seen, most = set(), 0
+    for label, tracks, track_of, starts, ends, size, want in window_cases():
+        dev = [summary.BedTrack(*t) for t in tracks]
+        seen.add(dev[0].sorted)
+        most = max(most, dev[0].n)
+        assert_planes(summary.summarize_beds(dev, track_of, starts, ends, size), want, label)
+        assert_planes(summarize_dev_raw(dev, track_of, starts, ends, size), want, (label, "device form"))
+        for t in dev:
+            t.close()
+    assert seen == {True, False} and most > 64 * WINDOW * CHUNK
+
+
+@pytest.mark.parametrize("size", TOP_SIZES)
+def test_records_that_end_at_the_top_of_int32(size):
+    """tracks whose furthest end is 2^31 - 1, regions in their last 100000 bases and up to 2^31 - 1: host and device form"""
+    from bxmi import summary
+
+    tracks, track_of, starts, ends, want = top_case(size)
+    dev = [summary.BedTrack(*t) for t in tracks]
+    assert [t.sorted for t in dev] == [True, True]
+    assert_planes(summary.summarize_beds(dev, track_of, starts, ends, size), want, size)
+    assert_planes(summarize_dev_raw(dev, track_of, starts, ends, size), want, (size, "device form"))
+    for t in dev:
+        t.close()
+
+
+def test_host_form_goes_through_more_than_one_slab():
+    """slab + 5 rows of 3000 bins: the host form's second slab, copied back behind the first.  Every cell equals the device
+    form's, which has no slabs and which the other tests of this file pin to the model; a sample of rows -- those around the slab
+    edge among them, which differ pairwise -- is compared with the model itself (summary_cases.assert_slabs)"""
+    from bxmi import summary
+
+    rng = np.random.default_rng(81)
+    tracks = [nested_track(rng, 3000), nested_track(rng, 3000)]
+    slab, track_of, starts, ends = slab_batch(82, 1, [int(t[1].max()) for t in tracks])
+    dev = [summary.BedTrack(*t) for t in tracks]
+    host = summary.summarize_beds(dev, track_of, starts, ends, SLAB_SIZE)
+    device = summarize_dev_raw(dev, track_of, starts, ends, SLAB_SIZE)
+    assert_slabs(host, device, lambda rows: model(tracks, track_of[rows], starts[rows], ends[rows], SLAB_SIZE), slab, len(track_of))
+    del host, device
+    for t in dev:
+        t.close()
 
 
 def test_no_regions_and_bad_arguments():

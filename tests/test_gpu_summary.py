@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 import summary_model as M
-from summary_cases import CHUNK, assert_planes, chunk_track, differential_case, empty_planes
+from summary_cases import (CHUNK, SLAB_SIZE, TOP_SIZES, assert_planes, assert_slabs, chunk_track, differential_case, empty_planes, random_track, slab_batch,
+                           top_case)
 from test_summary_model_golden import FILES, path_of, recorded, spans
 
 pytestmark = pytest.mark.gpu
@@ -216,6 +217,40 @@ def summarize_dev_raw(tracks, track_of, starts, ends, size):
     for a in rows + planes:
         a.free()
     return out
+
+
+@pytest.mark.parametrize("size", TOP_SIZES)
+def test_items_that_end_at_the_top_of_int32(size):
+    """an ordered and an unordered track whose last end is 2^31 - 1, regions in their last 100000 bases and up to 2^31 - 1: host
+    and device form"""
+    from bxmi import summary
+
+    tracks, track_of, starts, ends, want = top_case(size)
+    dev = [summary.SpanTrack(*t) for t in tracks]
+    assert [t.ordered for t in dev] == [True, False]
+    assert_planes(summary.summarize(dev, track_of, starts, ends, size), want, size)
+    assert_planes(summarize_dev_raw(dev, track_of, starts, ends, size), want, (size, "device form"))
+    for t in dev:
+        t.close()
+
+
+def test_host_form_goes_through_more_than_one_slab():
+    """2 slabs + 5 rows of 3000 bins: three turns of the host form's slab loop, the middle slab full, the last one short, each
+    copied back behind the one before.  Every cell equals the device form's, which has no slabs and which the other tests of this
+    file pin to the model; a sample of rows -- those around both slab edges among them, which differ pairwise -- is compared
+    with the model itself (summary_cases.assert_slabs)"""
+    from bxmi import summary
+
+    rng = np.random.default_rng(83)
+    tracks = [random_track(rng, 5000), random_track(rng, 5000)]
+    slab, track_of, starts, ends = slab_batch(84, 2, [int(t[1].max()) for t in tracks])
+    dev = [summary.SpanTrack(*t) for t in tracks]
+    host = summary.summarize(dev, track_of, starts, ends, SLAB_SIZE)
+    device = summarize_dev_raw(dev, track_of, starts, ends, SLAB_SIZE)
+    assert_slabs(host, device, lambda rows: M.summarize(tracks, track_of[rows], starts[rows], ends[rows], SLAB_SIZE), slab, len(track_of))
+    del host, device
+    for t in dev:
+        t.close()
 
 
 @pytest.mark.parametrize("n_tracks", TABLE_TRACKS)

@@ -14,7 +14,9 @@ import numpy as np
 import pytest
 
 import zoom_model as M
-from zoom_cases import CHUNK, FILES, GOLDEN, SIZES, assert_planes, chunk_level, differential_case, empty_planes, levels, path_of, recorded, zoom_cases
+from summary_cases import SLAB_SIZE, TOP_SIZES, assert_slabs, slab_batch
+from zoom_cases import (CHUNK, FILES, GOLDEN, SIZES, assert_planes, chunk_level, differential_case, empty_planes, levels, path_of, random_level, recorded, top_case,
+                        zoom_cases)
 
 pytestmark = pytest.mark.gpu
 
@@ -289,6 +291,38 @@ def test_device_form_and_its_unchecked_rows():
     many = dev[:4] + dev[:4] + [dev[3]]
     got = summarize_dev_raw(many, [8, 9, 4, -1], [0, 0, 600, 0], [30, 30, 2600, 30], 4)
     assert_planes(got, M.summarize(tracks, [3, -1, 0, -1], [0, 0, 600, 0], [30, 30, 2600, 30], 4), "nine tracks")
+    for t in dev:
+        t.close()
+
+
+@pytest.mark.parametrize("size", TOP_SIZES)
+def test_records_that_end_at_the_top_of_int32(size):
+    """a level whose last record and last leaf end at 2^31 - 1, regions in its last 100000 bases and up to 2^31 - 1: host and
+    device form"""
+    from bxmi import summary
+
+    tracks, track_of, starts, ends, want = top_case(size)
+    dev = [summary.ZoomTrack(z) for z in tracks]
+    assert_planes(summary.summarize_zoom(dev, track_of, starts, ends, size), want, size)
+    assert_planes(summarize_dev_raw(dev, track_of, starts, ends, size), want, (size, "device form"))
+    for t in dev:
+        t.close()
+
+
+def test_host_form_goes_through_more_than_one_slab():
+    """slab + 5 rows of 3000 bins: the host form's second slab, copied back behind the first.  Every cell equals the device
+    form's, which has no slabs and which the other tests of this file pin to the model; a sample of rows -- those around the slab
+    edge among them, which differ pairwise -- is compared with the model itself (summary_cases.assert_slabs)"""
+    from bxmi import summary
+
+    rng = np.random.default_rng(85)
+    tracks = [random_level(rng, 3000, 16), random_level(rng, 3000, 16, first=300)]
+    slab, track_of, starts, ends = slab_batch(86, 1, [int(z.end.max()) for z in tracks])
+    dev = [summary.ZoomTrack(z) for z in tracks]
+    host = summary.summarize_zoom(dev, track_of, starts, ends, SLAB_SIZE)
+    device = summarize_dev_raw(dev, track_of, starts, ends, SLAB_SIZE)
+    assert_slabs(host, device, lambda rows: M.summarize(tracks, track_of[rows], starts[rows], ends[rows], SLAB_SIZE), slab, len(track_of))
+    del host, device
     for t in dev:
         t.close()
 

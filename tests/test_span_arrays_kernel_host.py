@@ -3,7 +3,7 @@ tests/cpp/span_arrays_kernel_host.cpp -- a workgroup of host threads, a barrier 
 sanitizers on, the output between two guard bands -- gives every recorded reference array and the model's answer on the edge shapes
 of the GPU tests: ragged batches whose rows start anywhere in a thread's 4 elements, empty rows, widths around a tile, runs around
 the chunk size, ordered tracks with overlapping items, tracks that are not ordered, rows without a track, windows from below 0 and
-at the end of int32, an output off a 16-byte boundary, and the output cut into slabs as the host form cuts it.  This is the
+at the end of int32, items that end at 2^31 - 1 under rows that end there or run past it, an output off a 16-byte boundary, and the output cut into slabs as the host form cuts it.  This is the
 kernel's logic and indexing; tests/test_gpu_arrays.py checks the same cases on the device."""
 import numpy as np
 import pytest
@@ -68,6 +68,15 @@ def test_matrix_widths(kernel, width):
     M.assert_same(kernel(tracks, track_of, starts, width=width).reshape(-1, width), want, width)
     if width in (3, M.TILE + 1):
         M.assert_same(kernel(tracks, track_of, starts, width=width, slab_tiles=2, misalign=3).reshape(-1, width), want, (width, "slabs of 2 tiles"))
+
+
+def test_items_that_end_at_the_top_of_int32(kernel):
+    tracks, track_of, starts, _, (want, offsets), _ = M.top_ragged_case()
+    M.assert_same(kernel(tracks, track_of, starts, offsets=offsets), want, "ragged")
+    M.assert_same(kernel(tracks, track_of, starts, offsets=offsets, misalign=1, slab_tiles=2), want, "ragged, in slabs of 2 tiles, out off a 16-byte boundary")
+    for width in M.TOP_WIDTHS:
+        tracks, track_of, starts, want = M.top_matrix_case(width)
+        M.assert_same(kernel(tracks, track_of, starts, width=width).reshape(-1, width), want, width)
 
 
 def test_nothing_to_do(kernel):

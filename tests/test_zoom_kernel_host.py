@@ -1,14 +1,15 @@
 """CPU-only: the text of zm_summary_kernel (bx-python_amd/csrc/zoom_summary.hpp) compiled for the host by
 tests/cpp/zoom_kernel_host.cpp -- 64 threads per workgroup, a barrier for __syncthreads, address and undefined-behaviour sanitizers
 on -- gives every recorded reference result, the model's answer on the seeded batches of the GPU tests (several tracks and levels,
-an empty one, rows without a track, a region ending at 2^31 - 1) and on runs around the chunk size.  This is the kernel's logic and
+an empty one, rows without a track, a region ending at 2^31 - 1), under records and leaves that end at 2^31 - 1 and on runs around
+the chunk size.  This is the kernel's logic and
 indexing, not the GPU's arithmetic: tests/test_gpu_zoom.py checks the same cases on the device."""
 import numpy as np
 import pytest
 
 import kernel_host
 import zoom_model as M
-from zoom_cases import CHUNK, FILES, SIZES, assert_planes, chunk_level, differential_case, levels, recorded, zoom_cases
+from zoom_cases import CHUNK, FILES, SIZES, TOP_SIZES, assert_planes, chunk_level, differential_case, levels, recorded, top_case, zoom_cases
 
 
 @pytest.fixture(scope="module")
@@ -46,6 +47,12 @@ def test_recorded_cases(kernel, name):
 @pytest.mark.parametrize("size", SIZES)
 def test_seeded_batches(kernel, size):
     tracks, track_of, starts, ends, want = differential_case(size)
+    assert_planes(kernel(tracks, track_of, starts, ends, size), want, size)
+
+
+@pytest.mark.parametrize("size", TOP_SIZES)
+def test_records_that_end_at_the_top_of_int32(kernel, size):
+    tracks, track_of, starts, ends, want = top_case(size)
     assert_planes(kernel(tracks, track_of, starts, ends, size), want, size)
 
 

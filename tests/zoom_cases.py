@@ -10,7 +10,7 @@ import re
 import numpy as np
 
 import zoom_model as M
-from summary_cases import assert_planes, empty_planes  # noqa: F401  (the byte-for-byte comparison of the five planes)
+from summary_cases import TOP_SIZES, assert_planes, empty_planes, shifted_to_the_top, top_regions  # noqa: F401  (the byte-for-byte comparison of the five planes)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "zoom")
@@ -139,3 +139,20 @@ def differential_case(size):
         ends = np.concatenate([ends, extra_end, [int(tracks[0].end.max()) + 77, INT32_MAX, 1500]]).astype(np.int32)
         _cache[size] = (tracks, track_of, starts, ends, M.summarize(tracks, track_of, starts, ends, size))
     return _cache[size]
+
+
+def top_case(size):
+    """(level parts, track_of, starts, ends, the model's answer), once per size: two levels of 2000 records (one with many gaps),
+    records and leaf ranges shifted by one amount so that the last record and the last leaf end at exactly 2^31 - 1, under
+    summary_cases.top_regions()"""
+    if ("top", size) not in _cache:
+        rng = np.random.default_rng(700 + size)
+        tracks = []
+        for gap_rate in (0.05, 0.2):
+            z = random_level(rng, 2000, 16, first=40, gap_rate=gap_rate)
+            end, start, leaf_lo, leaf_hi = shifted_to_the_top(z.end, z.start, z.leaf_lo, z.leaf_hi)
+            tracks.append(z._replace(start=start, end=end, leaf_lo=leaf_lo, leaf_hi=leaf_hi))
+        assert all(int(z.end[-1]) == INT32_MAX and int(z.leaf_hi[-1]) == INT32_MAX for z in tracks)
+        track_of, starts, ends = top_regions(rng, [z.start[0] for z in tracks], size)
+        _cache["top", size] = (tracks, track_of, starts, ends, M.summarize(tracks, track_of, starts, ends, size))
+    return _cache["top", size]
