@@ -106,6 +106,13 @@ _SIGNATURES = {
     "bxmi_twobit_bases_dev": [vp, i32, vp, vp, i64, i32, vp, i64, C.c_int, C.c_int, vp, vp],
     "bxmi_twobit_composition": [vp, i32, vp, vp, vp, i64, C.c_int, vp],
     "bxmi_twobit_composition_dev": [vp, i32, vp, vp, vp, i64, C.c_int, vp, vp],
+    "bxmi_pwm_create": [vp, vp, i32, i32, vp, _p(vp)],
+    "bxmi_pwm_destroy": [vp],
+    "bxmi_pwm_info": [vp, _p(i32), _p(i32), _p(i32)],
+    "bxmi_twobit_pwm_scores": [vp, i32, vp, vp, i64, i32, vp, i64, C.c_int, vp, vp],
+    "bxmi_twobit_pwm_scores_dev": [vp, i32, vp, vp, i64, i32, vp, i64, C.c_int, vp, vp, vp],
+    "bxmi_twobit_pwm_best": [vp, i32, vp, vp, i64, i32, vp, i64, C.c_int, vp, vp, vp],
+    "bxmi_twobit_pwm_best_dev": [vp, i32, vp, vp, i64, i32, vp, i64, C.c_int, vp, vp, vp, vp],
     "bxmi_bits_create": [i64, i64, _p(vp)],
     "bxmi_bits_destroy": [vp],
     "bxmi_bits_info": [vp, _p(i32), _p(i32), _p(i32)],

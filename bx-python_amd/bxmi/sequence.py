@@ -135,6 +135,32 @@ def matrix_dev(tracks, track_of, starts, width, pad=b"N", do_mask=True, stream=N
     return out
 
 
+def _clip_dev(tracks, track_of, starts, ends, n, dev):
+    """`_clip` by torch on its current stream, for the device forms -> (first int32 [n], offsets int64 [n + 1])"""
+    import torch
+
+    sizes = torch.tensor([tr.size for tr in tracks] + [0], dtype=torch.int64, device=dev)  # (the last: rows without a track)
+    named = (track_of >= 0) & (track_of < len(tracks))
+    size = sizes[torch.where(named, track_of, torch.full_like(track_of, len(tracks))).to(torch.int64)]
+    first = starts.clamp(min=0)
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        torch.cumsum((torch.minimum(ends.to(torch.int64), size) - first.to(torch.int64)).clamp_(min=0), 0, out=offsets[1:])
+    return first, offsets
+
+
+def _record(stream, dev, tensors):
+    """Tensors a device form made for itself are read or written by a kernel on `stream`; when that is not torch's current stream
+    its allocator does not know them by it: a tensor dropped on return must not have its block handed out again before `stream`
+    has passed this point.  (This protects the memory; it orders no work.)"""
+    import torch
+
+    if stream != torch.cuda.current_stream(dev).cuda_stream:
+        used_on = torch.cuda.ExternalStream(stream, device=dev)
+        for t in tensors:
+            t.record_stream(used_on)
+
+
 def sequences_dev(tracks, track_of, starts, ends, do_mask=True, stream=None):
     """`sequences` on device arrays: int32 torch tensors on the GPU in, (bytes uint8[total], offsets int64[n + 1]) tensors out.
     The clipping and the offsets are computed by torch on its current stream and `total` is read back to size the output -- ONE
@@ -144,23 +170,13 @@ def sequences_dev(tracks, track_of, starts, ends, do_mask=True, stream=None):
 
     tracks = list(tracks)
     (track_of, starts, ends), n, dev, stream = _ffi.device_args("sequences_dev", "sequences", ("track_of", "starts", "ends"), (track_of, starts, ends), stream)
-    sizes = torch.tensor([tr.size for tr in tracks] + [0], dtype=torch.int64, device=dev)  # (the last: rows without a track)
-    named = (track_of >= 0) & (track_of < len(tracks))
-    size = sizes[torch.where(named, track_of, torch.full_like(track_of, len(tracks))).to(torch.int64)]
-    first = starts.clamp(min=0)
-    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    if n:
-        torch.cumsum((torch.minimum(ends.to(torch.int64), size) - first.to(torch.int64)).clamp_(min=0), 0, out=offsets[1:])
+    first, offsets = _clip_dev(tracks, track_of, starts, ends, n, dev)
     total = int(offsets[-1].item()) if n else 0  # (the synchronisation: `first` and `offsets` are complete after it)
     out = torch.empty(total, dtype=torch.uint8, device=dev)
     call("bxmi_twobit_bases_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), first.data_ptr(), n, 0, offsets.data_ptr(), total,
          int(bool(do_mask)), ord("N"), out.data_ptr(), stream)
-    if total and stream != torch.cuda.current_stream(dev).cuda_stream:
-        # the kernel reads `first` and `offsets` and writes `out` on a stream torch's allocator does not know them by: `first` is
-        # dropped on return and its block must not be handed out again before that stream has passed this point
-        used_on = torch.cuda.ExternalStream(stream, device=dev)
-        for t in (first, offsets, out):
-            t.record_stream(used_on)
+    if total:
+        _record(stream, dev, (first, offsets, out))
     return out, offsets
 
 
@@ -228,3 +244,35 @@ class TwoBitSet:
 
     def composition_dev(self, track_of, starts, ends, stream=None):
         return composition_dev(self.tracks.values(), track_of, starts, ends, self.do_mask, stream)
+
+    # position weight matrices over the rows (bxmi.motif, which builds on this module); `pwms`: a motif.MatrixSet, for the host
+    # forms also a list of motif.ScoringMatrix
+    def scores(self, chroms, starts, ends, pwms):
+        from . import motif
+
+        return motif.scores(self.tracks.values(), self._track_of(chroms), starts, ends, pwms, self.do_mask)
+
+    def score_matrix(self, chroms, starts, width, pwms):
+        from . import motif
+
+        return motif.score_matrix(self.tracks.values(), self._track_of(chroms), starts, width, pwms, self.do_mask)
+
+    def best(self, chroms, starts, ends, pwms):
+        from . import motif
+
+        return motif.best(self.tracks.values(), self._track_of(chroms), starts, ends, pwms, self.do_mask)
+
+    def scores_dev(self, track_of, starts, ends, pwms, stream=None):
+        from . import motif
+
+        return motif.scores_dev(self.tracks.values(), track_of, starts, ends, pwms, self.do_mask, stream)
+
+    def score_matrix_dev(self, track_of, starts, width, pwms, stream=None, out=None):
+        from . import motif
+
+        return motif.score_matrix_dev(self.tracks.values(), track_of, starts, width, pwms, self.do_mask, stream, out)
+
+    def best_dev(self, track_of, starts, ends, pwms, stream=None):
+        from . import motif
+
+        return motif.best_dev(self.tracks.values(), track_of, starts, ends, pwms, self.do_mask, stream)

@@ -2,6 +2,8 @@
 // blocks -- the letters under batches of rows (bxmi_twobit_bases*) and their base counts (bxmi_twobit_composition*).  Kernels and
 // semantics: twobit.hpp.  The argument checks, the track table and the staging are track_batch.hpp's, as in summary.hip; the scratch
 // is this unit's own, so these calls do not share the one-call-at-a-time rule with the summaries, only with each other.
+// Position weight matrices scored over those rows (bxmi_pwm_*, bxmi_twobit_pwm_*): kernels and semantics in pwm.hpp; they use the
+// same table and scratch and so the same rule.
 #include <memory>
 #include <mutex>
 #include <new>
@@ -18,6 +20,7 @@
 #undef sm_summary_kernel
 #undef sa_arrays_kernel
 #include "twobit.hpp"
+#include "pwm.hpp"
 #include "track_batch.hpp"
 
 using namespace bxmi;
@@ -37,10 +40,14 @@ constexpr int64_t TB_SLAB = (int64_t)TB_TILE << 14;   // output bytes per slab o
 constexpr int64_t TB_TILES_PER_LAUNCH = 1 << 22;      // (a grid's threads are counted in 32 bits: 2^22 workgroups of 256)
 constexpr int64_t TB_ROWS_PER_LAUNCH = 1 << 25;       // (2^25 workgroups of 64)
 constexpr int64_t TB_COMP_SLAB = 1 << 22;             // rows per slab of the host form of the composition
+constexpr int64_t PW_SLAB = (int64_t)PW_TILE << 12;   // output elements of ALL planes per slab of the host form of the scores (16 MiB): whole tiles per plane
+constexpr int64_t PW_TILES_PER_LAUNCH = 1 << 22;      // (2^22 workgroups of 256)
+constexpr int64_t PW_OUT_MAX = INT64_MAX / 8;         // elements of all planes: their byte offsets stay far inside int64
 
 struct SequenceBufs {
     DevBuf table;                         // TbTrack [n_tracks + 1], the last one the spare entry
     DevBuf q_track, q_start, q_end, r;    // staging of the host forms
+    DevBuf keys;                          // uint64 [n_mats][n] of the best hits
 };
 LibraryScratch<SequenceBufs> &g_sequence = LibraryScratch<SequenceBufs>::leaked();
 
@@ -164,8 +171,7 @@ static int sequence_fill_table(SequenceBufs &S, bxmi_twobit_t *const *tracks, in
 
 // ---- letters (tb_bases_kernel) ----
 // what both forms check; `row_off` is only tested for being there
-static int bases_check(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const void *track_of, const void *start, int64_t n, int32_t width,
-                       const void *row_off, int64_t total, int pad, const void *out)
+static int rows_check(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, int64_t n, int32_t width, const void *row_off, int64_t total)
 {
     if (!row_off) {
         BXMI_TRY(track_batch_check(who, "width", width, tracks, n_tracks, n));
@@ -176,8 +182,29 @@ static int bases_check(const char *who, bxmi_twobit_t *const *tracks, int32_t n_
         BXMI_TRY(track_batch_check(who, "width", 1, tracks, n_tracks, n));
         if (total < 0) return fail(BXMI_EINVAL, "%s: total = %lld is negative", who, (long long)total);
     }
+    return BXMI_OK;
+}
+
+static int bases_check(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const void *track_of, const void *start, int64_t n, int32_t width,
+                       const void *row_off, int64_t total, int pad, const void *out)
+{
+    BXMI_TRY(rows_check(who, tracks, n_tracks, n, width, row_off, total));
     if (pad < 0 || pad > 255) return fail(BXMI_EINVAL, "%s: pad = %d is not a byte", who, pad);
     if ((n > 0 && (!track_of || !start)) || (n > 0 && total > 0 && !out)) return fail(BXMI_EINVAL, "%s: NULL array", who);
+    return BXMI_OK;
+}
+
+// what the host forms check of the offsets they can read (row_off == nullptr: nothing)
+static int offsets_check(const char *who, const int64_t *row_off, int64_t n, int64_t total)
+{
+    if (!row_off) return BXMI_OK;
+    if (row_off[0] != 0) return fail(BXMI_EINVAL, "%s: row_off[0] = %lld, must be 0", who, (long long)row_off[0]);
+    for (int64_t i = 0; i < n; i++) {
+        if (row_off[i + 1] < row_off[i]) return fail(BXMI_EINVAL, "%s: row_off descends at row %lld", who, (long long)i);
+        if (row_off[i + 1] - row_off[i] > 2147483647LL)
+            return fail(BXMI_EINVAL, "%s: row %lld has %lld elements, more than 2^31-1", who, (long long)i, (long long)(row_off[i + 1] - row_off[i]));
+    }
+    if (row_off[n] != total) return fail(BXMI_EINVAL, "%s: row_off[n] = %lld, but total = %lld", who, (long long)row_off[n], (long long)total);
     return BXMI_OK;
 }
 
@@ -214,15 +241,7 @@ extern "C" int bxmi_twobit_bases(bxmi_twobit_t *const *tracks, int32_t n_tracks,
     const char *who = "bxmi_twobit_bases";
     const int64_t *row_off = row_off_or_null;
     BXMI_TRY(bases_check(who, tracks, n_tracks, track_of, start, n, width, row_off, total, pad, out));
-    if (row_off) {
-        if (row_off[0] != 0) return fail(BXMI_EINVAL, "%s: row_off[0] = %lld, must be 0", who, (long long)row_off[0]);
-        for (int64_t i = 0; i < n; i++) {
-            if (row_off[i + 1] < row_off[i]) return fail(BXMI_EINVAL, "%s: row_off descends at row %lld", who, (long long)i);
-            if (row_off[i + 1] - row_off[i] > 2147483647LL)
-                return fail(BXMI_EINVAL, "%s: row %lld has %lld elements, more than 2^31-1", who, (long long)i, (long long)(row_off[i + 1] - row_off[i]));
-        }
-        if (row_off[n] != total) return fail(BXMI_EINVAL, "%s: row_off[n] = %lld, but total = %lld", who, (long long)row_off[n], (long long)total);
-    }
+    BXMI_TRY(offsets_check(who, row_off, n, total));
     BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
     if (n == 0 || total == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_sequence.lock);
@@ -313,5 +332,220 @@ extern "C" int bxmi_twobit_composition(bxmi_twobit_t *const *tracks, int32_t n_t
         BXMI_HIP(hipMemcpyAsync(counts + 6 * first, S.r.p, in_bytes * 6, hipMemcpyDeviceToHost, st));
         BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
     }
+    return BXMI_OK;
+}
+
+// ---- position weight matrices (pwm.hpp) ----
+struct bxmi_pwm {
+    int32_t n_mats = 0, n_cols = 0, max_width = 0;
+    unsigned long long letters = 0;
+    DevBuf values, mat_off;
+    PwSet set() const { return PwSet{values.as<float>(), mat_off.as<int32_t>(), n_mats, n_cols, max_width, letters}; }
+};
+
+extern "C" int bxmi_pwm_create(const float *values, const int32_t *mat_off, int32_t n_mats, int32_t n_cols, const int8_t *letter_col, bxmi_pwm_t **out)
+{
+    const char *who = "bxmi_pwm_create";
+    if (!out) return fail(BXMI_EINVAL, "%s: out is NULL", who);
+    *out = nullptr;
+    if (!values || !mat_off || !letter_col) return fail(BXMI_EINVAL, "%s: NULL array", who);
+    if (n_mats < 1 || n_mats > PW_MATS_MAX) return fail(BXMI_EINVAL, "%s: n_mats = %d outside [1, %d]", who, (int)n_mats, PW_MATS_MAX);
+    if (n_cols < 1 || n_cols > PW_COLS_MAX) return fail(BXMI_EINVAL, "%s: n_cols = %d outside [1, %d]", who, (int)n_cols, PW_COLS_MAX);
+    if (mat_off[0] != 0) return fail(BXMI_EINVAL, "%s: mat_off[0] = %d, must be 0", who, (int)mat_off[0]);
+    int32_t max_width = 0;
+    for (int32_t m = 0; m < n_mats; m++) {
+        const int64_t w = (int64_t)mat_off[m + 1] - mat_off[m];
+        if (w < 0) return fail(BXMI_EINVAL, "%s: mat_off descends at matrix %d", who, (int)m);
+        if (w < 1 || w > PW_WIDTH_MAX) return fail(BXMI_EINVAL, "%s: matrix %d has width %lld outside [1, %d]", who, (int)m, (long long)w, PW_WIDTH_MAX);
+        if (w > max_width) max_width = (int32_t)w;
+    }
+    unsigned long long letters = 0;
+    for (int k = 0; k < PW_LETTERS; k++) {
+        if (letter_col[k] < -1 || letter_col[k] >= n_cols)
+            return fail(BXMI_EINVAL, "%s: letter_col[%d] = %d outside [-1, n_cols = %d)", who, k, (int)letter_col[k], (int)n_cols);
+        letters |= (unsigned long long)(letter_col[k] + 1) << (5 * k);
+    }
+    std::unique_ptr<bxmi_pwm> h(new (std::nothrow) bxmi_pwm());
+    if (!h) return fail(BXMI_ENOMEM, "%s: host allocation failed", who);
+    h->n_mats = n_mats;
+    h->n_cols = n_cols;
+    h->max_width = max_width;
+    h->letters = letters;
+    BXMI_TRY(put(h->values, values, (size_t)mat_off[n_mats] * (size_t)n_cols * sizeof(float)));
+    BXMI_TRY(put(h->mat_off, mat_off, (size_t)(n_mats + 1) * sizeof(int32_t)));
+    *out = h.release();
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_pwm_destroy(bxmi_pwm_t *h)
+{
+    delete h;
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_pwm_info(const bxmi_pwm_t *h, int32_t *n_mats, int32_t *n_cols, int32_t *max_width)
+{
+    if (!h) return fail(BXMI_EINVAL, "bxmi_pwm_info: NULL handle");
+    if (n_mats) *n_mats = h->n_mats;
+    if (n_cols) *n_cols = h->n_cols;
+    if (max_width) *max_width = h->max_width;
+    return BXMI_OK;
+}
+
+// what all four scoring calls check (`planes`: the call writes [n_mats][total] scores); `row_off` is only tested for being there
+static int pwm_check(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const void *track_of, const void *start, int64_t n, int32_t width,
+                     const void *row_off, int64_t total, const bxmi_pwm_t *pwm, bool planes)
+{
+    BXMI_TRY(rows_check(who, tracks, n_tracks, n, width, row_off, total));
+    if (!pwm) return fail(BXMI_EINVAL, "%s: NULL matrix set", who);
+    if (planes && total > PW_OUT_MAX / pwm->n_mats)
+        return fail(BXMI_EINVAL, "%s: total = %lld elements in each of %d planes is more than the output index holds", who, (long long)total, (int)pwm->n_mats);
+    if (n > 0 && (!track_of || !start)) return fail(BXMI_EINVAL, "%s: NULL array", who);
+    return BXMI_OK;
+}
+
+// elements [o_first, o_first + count) of every plane, of rows [row_base, row_base + n_rows); `out` is element o_first's address in
+// plane 0.  keys != nullptr: the best hits instead (the whole batch: row_base == 0), nothing is stored to `out`.
+static int pwm_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n_rows, int64_t row_base, int32_t width,
+                      const int64_t *row_off, int64_t o_first, int64_t count, int do_mask, const bxmi_pwm_t *pwm, float *out, int64_t plane_stride,
+                      unsigned long long *keys, hipStream_t st)
+{
+    if (keys) {  // one launch of at most a device's fill of workgroups, each walking every gridDim.x-th tile: `count` may be a bound
+        const int64_t tiles = div_up(count, PW_TILE), fill = (int64_t)device_props().cus * 8;
+        hipLaunchKernelGGL(pw_scores_kernel<true>, dim3((unsigned)(tiles < fill ? tiles : fill)), dim3(PW_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks,
+                           track_of, start, n_rows, row_base, (int)width, row_off, o_first, count, do_mask, pwm->set(), (float *)nullptr, (int64_t)0, keys, n_rows);
+        BXMI_LAUNCH_CHECK();
+        return BXMI_OK;
+    }
+    constexpr int64_t PER_LAUNCH = PW_TILES_PER_LAUNCH * PW_TILE;
+    for (int64_t done = 0; done < count; done += PER_LAUNCH) {  // a workgroup per tile
+        const int64_t m = count - done < PER_LAUNCH ? count - done : PER_LAUNCH;
+        hipLaunchKernelGGL(pw_scores_kernel<false>, dim3((unsigned)div_up(m, PW_TILE)), dim3(PW_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of,
+                           start, n_rows, row_base, (int)width, row_off, o_first + done, m, do_mask, pwm->set(), out + done, plane_stride,
+                           (unsigned long long *)nullptr, (int64_t)0);
+        BXMI_LAUNCH_CHECK();
+    }
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_twobit_pwm_scores_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
+                                          int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *out,
+                                          void *stream)
+{
+    const char *who = "bxmi_twobit_pwm_scores_dev";
+    BXMI_TRY(pwm_check(who, tracks, n_tracks, track_of, start, n, width, row_off_or_null, total, pwm, true));
+    if (n > 0 && total > 0 && !out) return fail(BXMI_EINVAL, "%s: NULL array", who);
+    if (n == 0 || total == 0) return BXMI_OK;
+    std::lock_guard<std::mutex> hold(g_sequence.lock);
+    BXMI_TRY(g_sequence.enter());
+    BXMI_TRY(sequence_fill_table(g_sequence.bufs, tracks, n_tracks, as_stream(stream)));
+    return pwm_launch(g_sequence.bufs, n_tracks, track_of, start, n, 0, width, row_off_or_null, 0, total, do_mask != 0, pwm, out, total, nullptr,
+                      as_stream(stream));
+}
+
+extern "C" int bxmi_twobit_pwm_scores(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                                      const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *out)
+{
+    const char *who = "bxmi_twobit_pwm_scores";
+    const int64_t *row_off = row_off_or_null;
+    BXMI_TRY(pwm_check(who, tracks, n_tracks, track_of, start, n, width, row_off, total, pwm, true));
+    if (n > 0 && total > 0 && !out) return fail(BXMI_EINVAL, "%s: NULL array", who);
+    BXMI_TRY(offsets_check(who, row_off, n, total));
+    BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    if (n == 0 || total == 0) return BXMI_OK;
+    std::lock_guard<std::mutex> hold(g_sequence.lock);
+    BXMI_TRY(g_sequence.enter(true));
+    SequenceBufs &S = g_sequence.bufs;
+    const hipStream_t st = g_sequence.stream;
+    BXMI_TRY(sequence_fill_table(S, tracks, n_tracks, st));
+    // slabs of whole tiles per plane, PW_SLAB elements over all planes (at least one tile each); a row may lie in several
+    const int64_t slab = PW_SLAB / pwm->n_mats / PW_TILE > 0 ? PW_SLAB / pwm->n_mats / PW_TILE * PW_TILE : PW_TILE;
+    for (int64_t o0 = 0; o0 < total; o0 += slab) {
+        const int64_t count = total - o0 < slab ? total - o0 : slab;
+        const SaRows rows = sa_rows_of(row_off, n, width, o0, count);  // the slab's rows
+        const int64_t r0 = rows.r0, m = rows.m;
+        const size_t in_bytes = (size_t)m * sizeof(int32_t), off_bytes = (size_t)(m + 1) * sizeof(int64_t);
+        BXMI_TRY(S.q_track.reserve(in_bytes));
+        BXMI_TRY(S.q_start.reserve(in_bytes));
+        BXMI_TRY(S.r.reserve((size_t)count * sizeof(float) * (size_t)pwm->n_mats));
+        BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of + r0, in_bytes, hipMemcpyHostToDevice, st));
+        BXMI_HIP(hipMemcpyAsync(S.q_start.p, start + r0, in_bytes, hipMemcpyHostToDevice, st));
+        if (row_off) {  // (q_end holds the slab's offsets)
+            BXMI_TRY(S.q_end.reserve(off_bytes));
+            BXMI_HIP(hipMemcpyAsync(S.q_end.p, row_off + r0, off_bytes, hipMemcpyHostToDevice, st));
+        }
+        BXMI_TRY(pwm_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), m, r0, width, row_off ? S.q_end.as<int64_t>() : nullptr, o0, count,
+                            do_mask != 0, pwm, S.r.as<float>(), count, nullptr, st));
+        for (int32_t k = 0; k < pwm->n_mats; k++)  // each plane's part of the slab
+            BXMI_HIP(hipMemcpyAsync(out + (int64_t)k * total + o0, S.r.as<float>() + (int64_t)k * count, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, st));
+        BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
+    }
+    return BXMI_OK;
+}
+
+// keys = 0, the walk, the keys unpacked into best_score and best_pos [n_mats][n]
+static int pwm_best_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width, const int64_t *row_off,
+                           int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score, int32_t *best_pos, hipStream_t st)
+{
+    const int64_t cells = (int64_t)pwm->n_mats * n;
+    BXMI_TRY(S.keys.reserve((size_t)cells * sizeof(unsigned long long)));
+    BXMI_HIP(hipMemsetAsync(S.keys.p, 0, (size_t)cells * sizeof(unsigned long long), st));
+    if (total > 0)
+        BXMI_TRY(pwm_launch(S, n_tracks, track_of, start, n, 0, width, row_off, 0, total, do_mask, pwm, nullptr, 0, S.keys.as<unsigned long long>(), st));
+    hipLaunchKernelGGL(pw_unpack_kernel, dim3((unsigned)div_up(cells, PW_THREADS)), dim3(PW_THREADS), 0, st, S.keys.as<unsigned long long>(), cells, best_score,
+                       best_pos);
+    BXMI_LAUNCH_CHECK();
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_twobit_pwm_best_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
+                                        int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score,
+                                        int32_t *best_pos, void *stream)
+{
+    const char *who = "bxmi_twobit_pwm_best_dev";
+    BXMI_TRY(pwm_check(who, tracks, n_tracks, track_of, start, n, width, row_off_or_null, total, pwm, false));
+    if (n > 0 && (!best_score || !best_pos)) return fail(BXMI_EINVAL, "%s: NULL array", who);
+    if (n == 0) return BXMI_OK;
+    std::lock_guard<std::mutex> hold(g_sequence.lock);
+    BXMI_TRY(g_sequence.enter());
+    BXMI_TRY(sequence_fill_table(g_sequence.bufs, tracks, n_tracks, as_stream(stream)));
+    return pwm_best_launch(g_sequence.bufs, n_tracks, track_of, start, n, width, row_off_or_null, total, do_mask != 0, pwm, best_score, best_pos,
+                           as_stream(stream));
+}
+
+extern "C" int bxmi_twobit_pwm_best(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                                    const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score, int32_t *best_pos)
+{
+    const char *who = "bxmi_twobit_pwm_best";
+    const int64_t *row_off = row_off_or_null;
+    BXMI_TRY(pwm_check(who, tracks, n_tracks, track_of, start, n, width, row_off, total, pwm, false));
+    if (n > 0 && (!best_score || !best_pos)) return fail(BXMI_EINVAL, "%s: NULL array", who);
+    BXMI_TRY(offsets_check(who, row_off, n, total));
+    BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    if (n == 0) return BXMI_OK;
+    std::lock_guard<std::mutex> hold(g_sequence.lock);
+    BXMI_TRY(g_sequence.enter(true));
+    SequenceBufs &S = g_sequence.bufs;
+    const hipStream_t st = g_sequence.stream;
+    // nothing per base comes back: the rows go to the device whole and the walk is one launch
+    const int64_t cells = (int64_t)pwm->n_mats * n;
+    const size_t in_bytes = (size_t)n * sizeof(int32_t), off_bytes = (size_t)(n + 1) * sizeof(int64_t), cell_bytes = (size_t)cells * 4;
+    BXMI_TRY(S.q_track.reserve(in_bytes));
+    BXMI_TRY(S.q_start.reserve(in_bytes));
+    BXMI_TRY(S.r.reserve(2 * cell_bytes));
+    BXMI_TRY(sequence_fill_table(S, tracks, n_tracks, st));
+    BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of, in_bytes, hipMemcpyHostToDevice, st));
+    BXMI_HIP(hipMemcpyAsync(S.q_start.p, start, in_bytes, hipMemcpyHostToDevice, st));
+    if (row_off) {  // (q_end holds the offsets)
+        BXMI_TRY(S.q_end.reserve(off_bytes));
+        BXMI_HIP(hipMemcpyAsync(S.q_end.p, row_off, off_bytes, hipMemcpyHostToDevice, st));
+    }
+    float *d_score = S.r.as<float>();
+    int32_t *d_pos = S.r.as<int32_t>() + cells;
+    BXMI_TRY(pwm_best_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), n, width, row_off ? S.q_end.as<int64_t>() : nullptr, total,
+                             do_mask != 0, pwm, d_score, d_pos, st));
+    BXMI_HIP(hipMemcpyAsync(best_score, d_score, cell_bytes, hipMemcpyDeviceToHost, st));
+    BXMI_HIP(hipMemcpyAsync(best_pos, d_pos, cell_bytes, hipMemcpyDeviceToHost, st));
+    BXMI_HIP(hipStreamSynchronize(st));
     return BXMI_OK;
 }

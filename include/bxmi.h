@@ -32,6 +32,8 @@
  *                                BigBedFile.summarize_from_full / query over full data -> bxmi_beds_*
  *   lib/bx/seq/_twobit.pyx:22-137, twobit.py:34-56
  *                                TwoBitSequence.get / __getitem__, a batch of regions per call -> bxmi_twobit_*
+ *   lib/bx/motif/_pwm.pyx:23-55, pwm.py:141-149
+ *                                ScoringMatrix.score_string over the sequence of a batch of regions -> bxmi_pwm_*, bxmi_twobit_pwm_*
  *   (intersection.pyx has no C ABI of its own: its cdef classes are the
  *    interface, so the entry points below are what a Cython/ctypes shim of
  *    those classes binds; see INTEGRATION.md.)
@@ -579,6 +581,48 @@ int bxmi_twobit_composition(bxmi_twobit_t *const *tracks, int32_t n_tracks, cons
 /* Device variant: device pointers of natural alignment, stream-ordered on `stream`, no host synchronisation. */
 int bxmi_twobit_composition_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
                                 int64_t n, int do_mask, int32_t *counts, void *stream);
+
+/* ---- position weight matrices scored over 2bit rows  (lib/bx/motif/pwm.py:141-149, _pwm.pyx:23-55) ------------------------
+ * One bxmi_pwm_t is a set of n_mats matrices over ONE alphabet of n_cols columns, in HBM: `values` is float32 [mat_off[n_mats]]
+ * [n_cols], matrix m its rows [mat_off[m], mat_off[m + 1]) (widths may differ); letter_col[10] gives, for the ten letters a 2bit
+ * string can hold, in the order T C A G N t c a g n, the column of that letter or -1 (the reference's char_to_index at those ten
+ * characters).  _create refuses with BXMI_EINVAL, naming the condition, before any device call: n_mats outside [1, 32], n_cols
+ * outside [1, 16], a width outside [1, 256], mat_off[0] != 0, mat_off descending, a letter_col entry outside [-1, n_cols), NULLs.
+ * The values are taken as they are: -inf entries are legitimate and exact. */
+typedef struct bxmi_pwm bxmi_pwm_t;
+int bxmi_pwm_create(const float *values, const int32_t *mat_off, int32_t n_mats, int32_t n_cols, const int8_t *letter_col, bxmi_pwm_t **out);
+int bxmi_pwm_destroy(bxmi_pwm_t *h);
+int bxmi_pwm_info(const bxmi_pwm_t *h, int32_t *n_mats, int32_t *n_cols, int32_t *max_width);
+/* score_string for a batch of n rows described exactly as for bxmi_twobit_bases (matrix form: width >= 1, row_off NULL, total ==
+ * n * width; ragged form: width == 0 and row_off[n + 1]); `out` is float32 [n_mats][total].  Row i is the string of the letters
+ * bxmi_twobit_bases gives (TCAG by code, 'N' in an N block, lower case in a mask block when do_mask != 0); element j of row i of
+ * plane m is ((0.0f + v[0][c(j)]) + v[1][c(j + 1)]) + ... + v[W - 1][c(j + W - 1)], float32 additions in that order, bit for bit
+ * the reference's, when all W letters have a column and lie in the row; every other element -- the last W - 1 of a row, all of a
+ * row shorter than W, windows over a letter without a column, over a position outside [0, size), rows that name no track -- is
+ * the float32 NaN 0x7FC00000 (numpy's nan).  A NaN that the arithmetic itself produces (inf - inf, a NaN entry) is a NaN of
+ * unspecified sign and payload.  Refused with BXMI_EINVAL before any device call: everything bxmi_twobit_bases refuses about the
+ * rows (there is no pad), a NULL matrix set, total * n_mats beyond what the output index holds.  These calls use the track table
+ * and the scratch of the 2bit calls: one 2bit call (bases, composition, pwm) at a time per process.  Host arrays; goes through
+ * the device in slabs of output and BLOCKS until `out` is written. */
+int bxmi_twobit_pwm_scores(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                           const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *out);
+/* Device variant: `tracks` and `pwm` stay host handles; track_of, start, row_off and out are device pointers.  A thread's four
+ * elements of a plane are written by one 16-byte store where their address is 16-byte aligned, else element by element, with the
+ * same result (total % 4 != 0 misaligns the planes after the first).  Nothing outside out[0 .. n_mats * total) is written.
+ * Stream-ordered on `stream`, no host synchronisation; unchecked entries as bxmi_twobit_bases_dev. */
+int bxmi_twobit_pwm_scores_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                               const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *out, void *stream);
+/* The best hit per row, no per-base output: best_score float32 [n_mats][n] is the greatest score of the row's elements that are
+ * not NaN (a NaN is never a candidate), best_pos int32 [n_mats][n] the FIRST offset within the row that holds it; a row with no
+ * scored element gives NaN (0x7FC00000) and -1.  Rows, refusals (but for the one about the output index: there are no planes)
+ * and the one-call-at-a-time rule as bxmi_twobit_pwm_scores.  The device variant reads where the rows end from row_off[n] itself:
+ * in its ragged form `total` may be any bound >= row_off[n], so a caller whose offsets were computed on the device need not wait
+ * for them.  A row's cost is its bases, whatever its length. */
+int bxmi_twobit_pwm_best(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                         const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score, int32_t *best_pos);
+int bxmi_twobit_pwm_best_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                             const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score, int32_t *best_pos,
+                             void *stream);
 
 /* ---- BED text -> SoA columns on the host (the step before the hot path) ------
  * Strict single-pass parser for what lib/bx/bitset_builders.py:33-46 and

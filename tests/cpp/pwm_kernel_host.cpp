@@ -1,0 +1,202 @@
+// The kernels of bx-python_amd/csrc/pwm.hpp run on the host, their text compiled as it stands over kernel_host.hpp: pw_scores_kernel
+// storing scores, or folding best hits into keys that pw_unpack_kernel then unpacks.  What this checks is everything in the kernels:
+// the segments of a tile, the columns a thread stages and from which words, the halo, the searches for the staged letters' run of
+// blocks, the chunks, the order of every accumulator's additions, the keys, every index and every store (build it with
+// -fsanitize=address,undefined and -ffp-contract=off; the packed bytes are held in a buffer of exactly their whole words, every
+// table in one of exactly its size, the output planes between two guard bands).
+//
+// usage: pwm_kernel_host IN OUT
+//   IN:  int32 mode (0 scores, 1 best), n_tracks, n, width, ragged, misalign, slab_tiles, do_mask, n_mats, n_cols, grid; int64 total;
+//        int8 letter_col[10]; int32 mat_off[n_mats + 1]; float32 values[mat_off[n_mats]][n_cols];
+//        per track int64 size, n_blocks, m_blocks, then packed[(size + 3) / 4] (uint8), n_start[], n_size[], m_start[], m_size[]
+//        (int32); then track_of[n], start[n] (int32) and, when ragged, row_off[n + 1] (int64)
+//        misalign: `out` starts this many floats past a 16-byte boundary
+//        slab_tiles: > 0 cuts the output into launches of that many tiles, each given only its own rows and planes of exactly the
+//        slab's elements, as the host form of bxmi_twobit_pwm_scores does (mode 0)
+//        grid: mode 1: the workgroups of the one launch (0: one per tile), each walking every grid-th tile; `total` may then be a
+//        bound beyond row_off[n]
+//   OUT: mode 0: float32 [GUARD + n_mats * total + GUARD], the guard bands as they were filled (bits 0xEEEEEEEE)
+//        mode 1: float32 [GUARD + n_mats * n + GUARD] best scores, then int32 [GUARD + n_mats * n + GUARD] best positions
+#include "kernel_host.hpp"
+
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <new>
+
+// what the kernels use that kernel_host.hpp lacks
+struct int4 {
+    int x, y, z, w;
+};
+static int4 load_int4(const int32_t *p)
+{
+    if (reinterpret_cast<uintptr_t>(p) & 15) abort();  // (the device would fault)
+    return int4{p[0], p[1], p[2], p[3]};
+}
+static std::atomic<bool> g_misaligned_vector_store{false};
+static std::atomic<long> g_vector_stores{0};
+static void store_int4(int32_t *p, int a, int b, int c, int d)
+{
+    if (reinterpret_cast<uintptr_t>(p) & 15) g_misaligned_vector_store = true;
+    g_vector_stores++;
+    p[0] = a, p[1] = b, p[2] = c, p[3] = d;
+}
+static Dim gridDim;
+// TB_WAVE_SUM4 (twobit.hpp's creation kernels, not run here) and PW_WAVE_MAX64 for a workgroup of host threads: everyone leaves its
+// value, meets at the barrier, reads its wave's 64, meets again
+static void host_wave_sum4(int v[4]) { (void)v; abort(); }
+#define TB_WAVE_SUM4(v) host_wave_sum4(v)
+static unsigned long long g_lane_keys[1024];
+static unsigned long long host_wave_max64(unsigned long long key)
+{
+    g_lane_keys[threadIdx.x] = key;
+    g_barrier.wait();
+    const unsigned first = threadIdx.x & ~63u;
+    unsigned long long top = 0;
+    for (unsigned lane = first; lane < first + 64; lane++) top = g_lane_keys[lane] > top ? g_lane_keys[lane] : top;
+    g_barrier.wait();
+    return top;
+}
+#define PW_WAVE_MAX64(key) host_wave_max64(key)
+static std::mutex g_atomic_lock;
+static void host_atomic_max64(unsigned long long *at, unsigned long long key)
+{
+    std::lock_guard<std::mutex> hold(g_atomic_lock);
+    if (key > *at) *at = key;
+}
+#define PW_ATOMIC_MAX64(at, key) host_atomic_max64(at, key)
+#include "pwm.hpp"
+using namespace bxmi;
+
+constexpr size_t GUARD = 64;
+constexpr uint32_t GUARD_BITS = 0xEEEEEEEEu;
+
+struct Track {
+    int64_t size = 0, n_blocks = 0, m_blocks = 0;
+    std::vector<uint32_t> packed;
+    std::vector<int32_t> n_start, n_end, m_start, m_end;
+};
+
+static bool read_track(FILE *f, Track &t)
+{
+    std::vector<int64_t> head;
+    std::vector<uint8_t> bytes;
+    std::vector<int32_t> n_size, m_size;
+    if (!read_n(f, head, 3)) return false;
+    t.size = head[0], t.n_blocks = head[1], t.m_blocks = head[2];
+    if (!read_n(f, bytes, (size_t)(t.size + 3) / 4) || !read_n(f, t.n_start, t.n_blocks) || !read_n(f, n_size, t.n_blocks) ||
+        !read_n(f, t.m_start, t.m_blocks) || !read_n(f, m_size, t.m_blocks))
+        return false;
+    t.packed.assign((bytes.size() + 3) / 4, 0u);  // whole words, the rest of the last one zero
+    if (!bytes.empty()) memcpy(t.packed.data(), bytes.data(), bytes.size());
+    t.n_end.resize(t.n_start.size());
+    t.m_end.resize(t.m_start.size());
+    for (size_t i = 0; i < t.n_start.size(); i++) t.n_end[i] = t.n_start[i] + n_size[i];
+    for (size_t i = 0; i < t.m_start.size(); i++) t.m_end[i] = t.m_start[i] + m_size[i];
+    return true;
+}
+
+// a vector of float32 whose element `lead` is `misalign` floats past a 16-byte boundary: [..][GUARD][cells][GUARD], ending there
+struct Banded {
+    std::vector<uint32_t> raw;
+    size_t lead = 0, cells;
+    Banded(size_t cells_, int misalign) : raw(8 + 2 * GUARD + cells_, GUARD_BITS), cells(cells_)
+    {
+        while ((reinterpret_cast<uintptr_t>(raw.data() + lead + GUARD) & 15) != 0) lead++;
+        lead += misalign;
+        raw.resize(lead + 2 * GUARD + cells);
+    }
+    uint32_t *body() { return raw.data() + lead + GUARD; }
+    bool write(FILE *f) { return fwrite(raw.data() + lead, 4, 2 * GUARD + cells, f) == 2 * GUARD + cells; }
+};
+
+int main(int argc, char **argv)
+{
+    if (argc != 3) return 2;
+    FILE *f = fopen(argv[1], "rb");
+    if (!f) return 2;
+    std::vector<int32_t> head, mat_off;
+    std::vector<int64_t> total_in;
+    std::vector<int8_t> letter_col;
+    std::vector<float> values;
+    if (!read_n(f, head, 11) || !read_n(f, total_in, 1) || !read_n(f, letter_col, PW_LETTERS)) return 2;
+    const int mode = head[0], n_tracks = head[1], n = head[2], width = head[3], ragged = head[4], misalign = head[5], slab_tiles = head[6];
+    const int do_mask = head[7], n_mats = head[8], n_cols = head[9], grid = head[10];
+    const int64_t total = total_in[0];
+    if (!read_n(f, mat_off, (size_t)n_mats + 1) || !read_n(f, values, (size_t)mat_off[n_mats] * n_cols)) return 2;
+    std::vector<Track> tracks(n_tracks);
+    std::vector<TbTrack> table(n_tracks + 1);
+    for (int t = 0; t < n_tracks; t++) {
+        if (!read_track(f, tracks[t])) return 2;
+        const Track &k = tracks[t];
+        table[t] = TbTrack{k.packed.data(), k.n_start.data(), k.n_end.data(), k.m_start.data(), k.m_end.data(), nullptr, nullptr, nullptr, nullptr,
+                           k.size, k.n_blocks, k.m_blocks};
+    }
+    table[n_tracks] = TbTrack{};
+    std::vector<int32_t> track_of, start;
+    std::vector<int64_t> row_off;
+    if (!read_n(f, track_of, n) || !read_n(f, start, n) || (ragged && !read_n(f, row_off, (size_t)n + 1))) return 2;
+    fclose(f);
+
+    PwSet pw{values.data(), mat_off.data(), n_mats, n_cols, 0, 0ull};
+    for (int m = 0; m < n_mats; m++) pw.max_width = mat_off[m + 1] - mat_off[m] > pw.max_width ? mat_off[m + 1] - mat_off[m] : pw.max_width;
+    for (int k = 0; k < PW_LETTERS; k++) pw.letters |= (unsigned long long)(letter_col[k] + 1) << (5 * k);
+    const int64_t *offsets = ragged ? row_off.data() : nullptr;
+
+    if (mode == 1) {
+        const size_t cells = (size_t)n_mats * n;
+        std::vector<unsigned long long> keys(cells, 0ull);
+        const int64_t tiles = (total + PW_TILE - 1) / PW_TILE;
+        gridDim.x = (unsigned)(grid > 0 && grid < tiles ? grid : tiles);
+        if (total > 0 && n > 0)
+            run_grid(PW_THREADS, gridDim.x, [&] {
+                pw_scores_kernel<true>(table.data(), n_tracks, track_of.data(), start.data(), n, 0, width, offsets, 0, total, do_mask, pw, nullptr, 0,
+                                       keys.data(), n);
+            });
+        Banded score(cells, 0), pos(cells, 0);
+        if (cells > 0)
+            run_grid(PW_THREADS, (unsigned)((cells + PW_THREADS - 1) / PW_THREADS), [&] {
+                pw_unpack_kernel(keys.data(), (int64_t)cells, reinterpret_cast<float *>(score.body()), reinterpret_cast<int32_t *>(pos.body()));
+            });
+        f = fopen(argv[2], "wb");
+        if (!f || !score.write(f) || !pos.write(f)) return 2;
+        fclose(f);
+        puts("pwm kernel host ok");
+        return 0;
+    }
+
+    Banded out((size_t)n_mats * (size_t)total, misalign);
+    float *planes = reinterpret_cast<float *>(out.body());
+    if (((reinterpret_cast<uintptr_t>(planes) & 15) == 0) != (misalign == 0)) return 3;
+    const int64_t slab = slab_tiles > 0 ? (int64_t)slab_tiles * PW_TILE : (total > 0 ? total : 1);
+    for (int64_t o0 = 0; o0 < total && n > 0; o0 += slab) {
+        const int64_t count = total - o0 < slab ? total - o0 : slab;
+        gridDim.x = (unsigned)((count + PW_TILE - 1) / PW_TILE);
+        if (slab_tiles <= 0) {
+            run_grid(PW_THREADS, gridDim.x, [&] {
+                pw_scores_kernel<false>(table.data(), n_tracks, track_of.data(), start.data(), n, 0, width, offsets, 0, total, do_mask, pw, planes, total,
+                                        nullptr, 0);
+            });
+            break;
+        }
+        const SaRows rows = sa_rows_of(offsets, n, width, o0, count);
+        const int64_t r0 = rows.r0, m = rows.m;
+        // (copies of exactly the slab's rows, planes of exactly the slab's elements: an index outside them is an access outside an allocation)
+        const std::vector<int32_t> s_track(track_of.begin() + r0, track_of.begin() + r0 + m), s_start(start.begin() + r0, start.begin() + r0 + m);
+        std::vector<int64_t> s_off;
+        if (ragged) s_off.assign(row_off.begin() + r0, row_off.begin() + r0 + m + 1);
+        std::vector<float> part((size_t)n_mats * (size_t)count);
+        run_grid(PW_THREADS, gridDim.x, [&] {
+            pw_scores_kernel<false>(table.data(), n_tracks, s_track.data(), s_start.data(), m, r0, width, ragged ? s_off.data() : nullptr, o0, count, do_mask,
+                                    pw, part.data(), count, nullptr, 0);
+        });
+        for (int k = 0; k < n_mats; k++) memcpy(planes + (int64_t)k * total + o0, part.data() + (int64_t)k * count, (size_t)count * sizeof(float));
+    }
+    if (g_misaligned_vector_store) return 4;
+    f = fopen(argv[2], "wb");
+    if (!f || !out.write(f)) return 2;
+    fclose(f);
+    printf("vector stores %ld\n", g_vector_stores.load());
+    puts("pwm kernel host ok");
+    return 0;
+}
