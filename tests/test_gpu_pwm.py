@@ -2,7 +2,9 @@
 Position weight matrices scored over 2bit rows on the device (bxmi_pwm_*, bxmi_twobit_pwm_*, bxmi.motif, TwoBitSet.scores / score_matrix
 / best, bxmi.cli.twobit_pwm_scores) against the answers recorded from the reference's ScoringMatrix.score_string (tests/golden/pwm)
 and, beyond them, against tests/pwm_model.py -- itself pinned to those recordings by tests/test_pwm_model_golden.py.  Every
-comparison is of the 32 bits of a float: no tolerance anywhere.
+comparison is of the 32 bits of a float: no tolerance anywhere -- but where the model's own sum is an arithmetic NaN (inf - inf, a NaN
+entry), whose sign and payload include/bxmi.h leaves open: there the device's element must be a NaN (tests/pwm_cases.py, whose seeded
+cases tests/test_pwm_cases.py checks without a device).
 """
 import io
 import os
@@ -12,6 +14,7 @@ import sys
 import numpy as np
 import pytest
 
+import pwm_cases as PC
 import pwm_model as P
 import twobit_cases as K
 import twobit_model as M
@@ -379,6 +382,119 @@ def test_host_form_across_a_slab_boundary():
         assert same_bits(got[k], want[k % 4]), k
     ms.close()
     track.close()
+
+
+# ------------------------------------------------------------ the seeded cases of tests/pwm_cases.py --
+class Held:
+    """the tracks and matrix sets that the cases of a test put on the device, each once, all closed again whatever the test does"""
+
+    def __init__(self):
+        self.tracks, self.sets = {}, {}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for h in list(self.sets.values()) + list(self.tracks.values()):
+            h[1].close()
+
+    def tracks_of(self, seqs):
+        from bxmi import sequence
+
+        for s in seqs:
+            if id(s) not in self.tracks:
+                self.tracks[id(s)] = (s, sequence.TwoBitTrack(s))
+        return [self.tracks[id(s)][1] for s in seqs]
+
+    def set_of(self, mats):
+        if id(mats) not in self.sets:
+            self.sets[id(mats)] = (mats, device_set(mats))
+        return self.sets[id(mats)][1]
+
+
+class OnDevice:
+    """one form of the library, host arrays or the _dev entry points, as a device of pwm_cases.check_batch; `slack` goes to the
+    _dev form of the best hits alone: the host form asks that `total` is where the offsets end"""
+
+    def __init__(self, held, dev):
+        self.held, self.dev = held, dev
+
+    def scores(self, seqs, mats, track_of, starts, lengths=None, width=0, do_mask=True):
+        form = scores_dev if self.dev else scores_host
+        return form(self.held.tracks_of(seqs), self.held.set_of(mats), track_of, starts, width=width, lengths=lengths, do_mask=do_mask)
+
+    def best(self, seqs, mats, track_of, starts, lengths=None, width=0, do_mask=True, slack=0):
+        tracks, ms = self.held.tracks_of(seqs), self.held.set_of(mats)
+        if self.dev:
+            return best_dev(tracks, ms, track_of, starts, width=width, lengths=lengths, do_mask=do_mask, slack=slack)
+        return best_host(tracks, ms, track_of, starts, width=width, lengths=lengths, do_mask=do_mask)
+
+
+def both_forms(held):
+    return [OnDevice(held, False), OnDevice(held, True)]
+
+
+@pytest.mark.parametrize("name", sorted(PC.MATRIX_SETS))
+def test_seeded_matrix_sets(name):
+    """random matrices of mixed magnitudes, so that a sum in another order has other bits (asserted by the generator): exactly
+    PW_LDS_VALUES values as four matrices of 256 x 4 and as the largest single matrix, 256 x 16; PW_LDS_VALUES + n_cols values, the
+    smallest set staged matrix by matrix; PW_MATS_MAX matrices of 1 .. 256 rows, the halo from one of them; 16 columns with column
+    15 selected by t, by g, by n, by T, alphabets without N and n, without lower case, and with T and A in lower case only.  100 ragged rows of two sequences and
+    the same as windows of one width: scores, score_matrix and best, host and _dev forms, with and without the mask"""
+    with Held() as held:
+        PC.check_batch(both_forms(held), PC.matrix_set_case(name), where=name)
+
+
+def test_extremes_and_arithmetic_nans():
+    """pwm_cases.extremes_case: best scores that are negative, denormal, +inf (at its first offset) and -inf; windows that sum to
+    inf - inf or meet a NaN entry are a NaN in the planes, of whatever sign and payload, and never a candidate for the best hit,
+    also where the greatest score lies next to one; every other element bit for bit, the unscoreable ones 0x7FC00000"""
+    with Held() as held:
+        PC.check_batch(both_forms(held), PC.extremes_case(), where="extremes")
+
+
+def test_best_hit_on_every_lane():
+    """pwm_cases.lane_case: 1024 rows of one tile, about 1 M elements, the greatest score of row i at offset i -- the winning key
+    comes from every lane of every wave and from each of a thread's four elements; under the second matrix offsets i and i + k tie,
+    k of 1 .. 256: within a thread, across the lanes of a wave, across waves, and the first offset wins"""
+    case = PC.lane_case()
+    with Held() as held:
+        devs = both_forms(held)
+        PC.check_batch(devs, case, do_masks=(True,), planes=False, where="lanes")
+        for dev in devs:
+            score, pos = dev.best(case["seqs"], case["mats"], case["track_of"], case["starts"], case["lengths"])
+            assert np.array_equal(pos[0], np.arange(P.TILE)) and np.array_equal(pos[1], np.arange(P.TILE)) and (score == 1).all()
+
+
+def test_best_walks_more_tiles_than_the_grid():
+    """the grid of the best hits is at most compute units x 8 workgroups, each walking every gridDim.x-th tile: with half as many
+    tiles again some workgroups take two tiles and some one.  One row of all of them -- every workgroup sends keys to the same
+    cell: under the zeros matrix they all tie and the first scoreable offset wins; under the other the greatest score lies in the
+    far end of the row and its equal in the near end -- then a `total` several grid fills beyond the rows, then the same total in
+    a few thousand rows, so that the tiles of the second trip begin inside rows and hold several segments"""
+    import ctypes as C
+
+    from bxmi import _ffi
+
+    dev, cus = C.c_int(0), C.c_int(0)
+    _ffi.call("bxmi_get_device", C.byref(dev))
+    _ffi.call("bxmi_device_info", dev.value, None, 0, C.byref(cus), None)
+    fill = cus.value * 8
+    tiles = fill + fill // 2
+    assert cus.value > 0 and tiles > fill  # (or nothing here would take the second trip)
+    with Held() as held:
+        devs = both_forms(held)
+        PC.check_batch(devs, PC.long_row_case(tiles), planes=False, where="one long row", best_args=({}, dict(slack=5 * fill * P.TILE + 3)))
+        PC.check_batch(devs, PC.many_rows_case(tiles), planes=False, where="many rows")
+
+
+def test_scores_at_the_top_of_int32():
+    """pwm_cases.top_case on twobit_cases.TopSequence, 2^31 - 1 bases (512 MiB of device memory: given back whatever happens):
+    rows that end at the size, cross it, of W - 1, W and W + 1 bases ending at it, from its last base and from the size itself,
+    across the edges of an N block of 2^28 bases and of a mask block of nearly everything; matrices of 20 and 256 rows, whose
+    halo reaches past the size.  Positions, the packed word and the blocks' edges next to the top of int32"""
+    with Held() as held:
+        PC.check_batch(both_forms(held), PC.top_case(), where="top")
 
 
 # ------------------------------------------------------------ device entry points on torch tensors --

@@ -2,11 +2,14 @@
 workgroup of host threads, a barrier for __syncthreads and for the wave maximum, a lock for the atomic maximum, address and
 undefined-behaviour sanitizers on, -ffp-contract=off, every table in a buffer of exactly its size, the output planes between two
 guard bands -- gives every recorded answer of the reference bit for bit and the model's answer on the structural cases of the GPU
-tests.  This is the kernels' logic, indexing and order of additions; tests/test_gpu_pwm.py checks the same cases on the device."""
+tests.  This is the kernels' logic, indexing and order of additions; tests/test_gpu_pwm.py checks the same cases on the device.  The seeded cases of
+tests/pwm_cases.py -- random matrices, sets at the LDS boundary, infinities and arithmetic NaNs, the best hit on sampled lanes, more
+tiles than the grid, the phases of the top of int32 -- run here sized down."""
 import numpy as np
 import pytest
 
 import kernel_host
+import pwm_cases as PC
 import pwm_model as P
 import twobit_model as M
 
@@ -148,3 +151,56 @@ def test_nothing_to_do(kernel):
     assert kernel(seqs, mats, [0, 1], [3, 4], offsets=np.zeros(3, dtype=np.int64)).shape == (1, 0)
     top, at = kernel(seqs, mats, [0, 1], [3, 4], offsets=np.zeros(3, dtype=np.int64), best=True)
     assert (P.bits(top) == P.NAN_BITS).all() and (at == -1).all()
+
+
+# ------------------------------------------------------------ the seeded cases of tests/pwm_cases.py, sized down --
+class OnHost:
+    """the program as a device of pwm_cases.check_batch"""
+
+    def __init__(self, kernel):
+        self.kernel = kernel
+
+    def scores(self, seqs, mats, track_of, starts, lengths=None, width=0, do_mask=True):
+        return self.kernel(seqs, mats, track_of, starts, width=width, offsets=None if lengths is None else offsets_of(lengths), do_mask=do_mask)
+
+    def best(self, seqs, mats, track_of, starts, lengths=None, width=0, do_mask=True, grid=0, slack=0):
+        offsets = offsets_of(lengths)
+        return self.kernel(seqs, mats, track_of, starts, offsets=offsets, do_mask=do_mask, best=True, grid=grid, total=int(offsets[-1]) + slack)
+
+
+@pytest.mark.parametrize("name", sorted(PC.MATRIX_SETS))
+def test_seeded_matrix_sets(kernel, name):
+    """random matrices of mixed magnitudes, so that the order of the additions shows: exactly PW_LDS_VALUES values and the smallest
+    set beyond them, 16 columns with column 15 in use, PW_MATS_MAX matrices of 1 .. 256 rows; a few dozen ragged rows, and windows"""
+    rows, longest = (10, 400) if name == "mats_max" else (30, 1500)  # (the program's time goes with tiles x matrices)
+    PC.check_batch([OnHost(kernel)], PC.matrix_set_case(name, rows, 20_000, longest), where=name)
+
+
+def test_extremes_and_arithmetic_nans(kernel):
+    """negative, denormal, +inf and -inf best scores; windows that sum to inf - inf or meet a NaN entry are NaN in the planes and
+    never the best hit"""
+    PC.check_batch([OnHost(kernel)], PC.extremes_case(60, 20_000, 2000), where="extremes")
+
+
+def test_best_hit_on_sampled_lanes(kernel):
+    """rows of one tile whose greatest score lies at offset i, for the i of pwm_cases.LANE_SAMPLE: every element of a thread, the
+    first and last lane of every wave; under the second matrix offsets i and i + k tie, the first wins"""
+    case = PC.lane_case(PC.LANE_SAMPLE)
+    PC.check_batch([OnHost(kernel)], case, do_masks=(True,), planes=False, where="lanes")
+    got = OnHost(kernel).best(case["seqs"], case["mats"], case["track_of"], case["starts"], case["lengths"])
+    assert np.array_equal(got[1][0], case["which"]) and np.array_equal(got[1][1], case["which"]) and (got[0] == 1).all()
+
+
+@pytest.mark.parametrize("rows", ("long", "many"))
+def test_best_walks_more_tiles_than_the_grid(kernel, rows):
+    """five tiles and a bit in a grid of two workgroups, so each takes two or three: one long row in which every offset ties or
+    the greatest score lies in the far end and its equal in the near end, and the same total in many rows; a total that is only
+    a bound several grid fills beyond the rows"""
+    case = PC.long_row_case(5) if rows == "long" else PC.many_rows_case(5)
+    PC.check_batch([OnHost(kernel)], case, planes=False, where=rows, best_args=(dict(grid=2), dict(grid=2, slack=7 * P.TILE + 5)))
+
+
+def test_rows_at_the_phases_of_the_top_of_int32(kernel):
+    """pwm_cases.top_rows on a sequence of 2^15 - 1 bases: the size, the blocks' edges and so every staged word and column have
+    the phases they have at 2^31 - 1; matrices of 20 and 256 rows in 16 columns, the halo reaching past the size"""
+    PC.check_batch([OnHost(kernel)], PC.small_top_case(), where="small top")
