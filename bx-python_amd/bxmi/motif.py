@@ -9,7 +9,9 @@ every offset of every region, ``score_matrix`` the same for windows of one width
 and the first offset that holds it.  A score is the reference's float32 chain ``((0 + v[0][c0]) + v[1][c1]) + ...`` bit for bit;
 NaN (numpy's) where a letter of the window has no column -- with the alphabet ``ACGT`` an N or a soft-masked base -- and in the last
 ``width - 1`` offsets of a region.  The map is case sensitive, as the reference's: an alphabet with ``acgt`` or ``N`` scores them.
-The ``_dev`` forms take and return torch tensors on the caller's stream; thresholded hits are then torch's ``>=`` and ``nonzero``.
+``hits`` lists the offsets whose score reaches a threshold -- a scan -- as (matrix, region, offset, score) in that order, without the
+scores of the other offsets ever being written (``bxmi_twobit_pwm_hits*``; kernels: csrc/pwm_hits.hpp).  The ``_dev`` forms take and
+return torch tensors on the caller's stream.
 """
 import ctypes as C
 
@@ -146,6 +148,39 @@ def best(tracks, track_of, starts, ends, pwms, do_mask=True):
     return score, pos
 
 
+def _thresholds(thresholds, n_mats):
+    """a scalar or one value per matrix -> float32 [n_mats]"""
+    t = np.asarray(thresholds, dtype=np.float32)
+    if t.ndim > 1 or (t.ndim == 1 and len(t) != n_mats):
+        raise ValueError("thresholds must be a scalar or one value for each of the %d matrices" % n_mats)
+    return np.ascontiguousarray(np.broadcast_to(t, (n_mats,)))
+
+
+def hits(tracks, track_of, starts, ends, pwms, thresholds, do_mask=True):
+    """Every offset of regions [starts[i], ends[i]) (clipped as for `scores`) whose score under matrix m is not NaN and is >=
+    thresholds[m] (a scalar: one threshold for all) -> (mat_hits int64 [n_mats + 1], rows int32, pos int32, score float32): the
+    hits in ascending (matrix, region, offset), matrix m's being [mat_hits[m]:mat_hits[m + 1]] of the three arrays; `pos` is the
+    offset within the clipped region, `score` bit for bit the element of `scores`.  In the reference's terms, per matrix and
+    region, numpy.nonzero(pwms[m].score_string(seq.get(start, end)) >= thresholds[m]).  No score plane is written anywhere: a
+    call that counts, then a call into arrays of exactly that size."""
+    _ffi.require_gpu()
+    tracks = list(tracks)
+    t, s, e = _rows_i32("track_of, starts and ends", track_of, starts, ends)
+    s64, lengths = _clip([tr.size for tr in tracks], t, s, e)
+    offsets = np.zeros(len(s) + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offsets[1:])
+    with _held(pwms) as ms:
+        least = _thresholds(thresholds, ms.n_mats)
+        mat_hits = np.zeros(ms.n_mats + 1, dtype=np.int64)
+        rows_of = (_ffi.handles(tracks), len(tracks), ptr(t), ptr(as_i32(s64)), len(t), 0, ptr(offsets), int(offsets[-1]), int(bool(do_mask)), ms._h, ptr(least))
+        call("bxmi_twobit_pwm_hits", *rows_of, 0, ptr(mat_hits), None, None, None, allow=(_ffi.ERANGE,))
+        found = int(mat_hits[-1])
+        rows, pos, score = np.empty(found, dtype=np.int32), np.empty(found, dtype=np.int32), np.empty(found, dtype=np.float32)
+        if found:
+            call("bxmi_twobit_pwm_hits", *rows_of, found, ptr(mat_hits), ptr(rows), ptr(pos), ptr(score))
+    return mat_hits, rows, pos, score
+
+
 def _device_set(who, pwms):
     if not isinstance(pwms, MatrixSet):
         raise ValueError("%s takes a MatrixSet: the matrices must outlive the queued work" % who)
@@ -216,3 +251,43 @@ def best_dev(tracks, track_of, starts, ends, pwms, do_mask=True, stream=None):
     if n:
         _record(stream, dev, (first, offsets, score, pos))
     return score, pos
+
+
+def hits_dev(tracks, track_of, starts, ends, pwms, thresholds, do_mask=True, max_hits=None, stream=None):
+    """`hits` on device arrays: int32 torch tensors on the GPU in -> (mat_hits int64 [n_mats + 1], a HOST numpy array; rows int32,
+    pos int32, score float32 tensors on the device).  The clipping is torch's and its total is read back (one synchronisation);
+    the call itself waits once more, for the counts.  With `max_hits` the hits go into tensors of that capacity in ONE call -- two
+    scoring passes -- and views of the filled part are returned; if they do not fit, BxmiError (ERANGE) with the totals in its
+    message.  Without it a call that only counts comes first, so the regions are scored a THIRD time.  The hits are queued on
+    torch's current stream (or `stream`) and not waited for.  `pwms` is a MatrixSet.  One 2bit call at a time."""
+    import torch
+
+    tracks, ms = list(tracks), _device_set("hits_dev", pwms)
+    (track_of, starts, ends), n, dev, stream = _ffi.device_args("hits_dev", "hits", ("track_of", "starts", "ends"), (track_of, starts, ends), stream)
+    least = _thresholds(thresholds, ms.n_mats)
+    first, offsets = _clip_dev(tracks, track_of, starts, ends, n, dev)
+    total = int(offsets[-1].item()) if n else 0  # (the synchronisation: `first` and `offsets` are complete after it)
+    mat_hits = np.zeros(ms.n_mats + 1, dtype=np.int64)
+    rows_of = (_ffi.handles(tracks), len(tracks), track_of.data_ptr(), first.data_ptr(), n, 0, offsets.data_ptr(), total, int(bool(do_mask)), ms._h, ptr(least))
+    if max_hits is None:
+        call("bxmi_twobit_pwm_hits_dev", *rows_of, 0, ptr(mat_hits), None, None, None, stream, allow=(_ffi.ERANGE,))
+        cap = int(mat_hits[-1])
+    else:
+        cap = int(max_hits)
+        if cap < 0:
+            raise ValueError("max_hits must not be negative")
+    rows = torch.empty(cap, dtype=torch.int32, device=dev)
+    pos = torch.empty(cap, dtype=torch.int32, device=dev)
+    score = torch.empty(cap, dtype=torch.float32, device=dev)
+    if cap or max_hits is not None:
+        try:
+            call("bxmi_twobit_pwm_hits_dev", *rows_of, cap, ptr(mat_hits), rows.data_ptr() if cap else None, pos.data_ptr() if cap else None,
+                 score.data_ptr() if cap else None, stream)
+        except _ffi.BxmiError as err:
+            if err.code == _ffi.ERANGE:
+                raise _ffi.BxmiError(err.code, "%s (max_hits = %d; hits per matrix: %s)" % (err, cap, np.diff(mat_hits).tolist())) from None
+            raise
+    found = int(mat_hits[-1])
+    if total:
+        _record(stream, dev, (first, offsets, rows, pos, score))
+    return mat_hits, rows[:found], pos[:found], score[:found]

@@ -276,3 +276,13 @@ class TwoBitSet:
         from . import motif
 
         return motif.best_dev(self.tracks.values(), track_of, starts, ends, pwms, self.do_mask, stream)
+
+    def hits(self, chroms, starts, ends, pwms, thresholds):
+        from . import motif
+
+        return motif.hits(self.tracks.values(), self._track_of(chroms), starts, ends, pwms, thresholds, self.do_mask)
+
+    def hits_dev(self, track_of, starts, ends, pwms, thresholds, max_hits=None, stream=None):
+        from . import motif
+
+        return motif.hits_dev(self.tracks.values(), track_of, starts, ends, pwms, thresholds, self.do_mask, max_hits, stream)

@@ -2,8 +2,8 @@
 // blocks -- the letters under batches of rows (bxmi_twobit_bases*) and their base counts (bxmi_twobit_composition*).  Kernels and
 // semantics: twobit.hpp.  The argument checks, the track table and the staging are track_batch.hpp's, as in summary.hip; the scratch
 // is this unit's own, so these calls do not share the one-call-at-a-time rule with the summaries, only with each other.
-// Position weight matrices scored over those rows (bxmi_pwm_*, bxmi_twobit_pwm_*): kernels and semantics in pwm.hpp; they use the
-// same table and scratch and so the same rule.
+// Position weight matrices scored over those rows (bxmi_pwm_*, bxmi_twobit_pwm_*): kernels and semantics in pwm.hpp, those of the
+// thresholded hits (bxmi_twobit_pwm_hits*) in pwm_hits.hpp; they use the same table and scratch and so the same rule.
 #include <memory>
 #include <mutex>
 #include <new>
@@ -21,6 +21,7 @@
 #undef sa_arrays_kernel
 #include "twobit.hpp"
 #include "pwm.hpp"
+#include "pwm_hits.hpp"
 #include "track_batch.hpp"
 
 using namespace bxmi;
@@ -48,6 +49,7 @@ struct SequenceBufs {
     DevBuf table;                         // TbTrack [n_tracks + 1], the last one the spare entry
     DevBuf q_track, q_start, q_end, r;    // staging of the host forms
     DevBuf keys;                          // uint64 [n_mats][n] of the best hits
+    DevBuf hit_counts, hit_bases, hit_scan;  // of the thresholded hits: int32 [n_mats][tiles], int64 bases of them + total + heads, the scan's sums
 };
 LibraryScratch<SequenceBufs> &g_sequence = LibraryScratch<SequenceBufs>::leaked();
 
@@ -546,6 +548,129 @@ extern "C" int bxmi_twobit_pwm_best(bxmi_twobit_t *const *tracks, int32_t n_trac
                              do_mask != 0, pwm, d_score, d_pos, st));
     BXMI_HIP(hipMemcpyAsync(best_score, d_score, cell_bytes, hipMemcpyDeviceToHost, st));
     BXMI_HIP(hipMemcpyAsync(best_pos, d_pos, cell_bytes, hipMemcpyDeviceToHost, st));
+    BXMI_HIP(hipStreamSynchronize(st));
+    return BXMI_OK;
+}
+
+// ---- thresholded hits (pwm_hits.hpp) ----
+// what both forms check; `row_off` is only tested for being there
+static int pwm_hits_check(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const void *track_of, const void *start, int64_t n, int32_t width,
+                          const void *row_off, int64_t total, const bxmi_pwm_t *pwm, const float *threshold, int64_t cap, const int64_t *mat_hits,
+                          const void *hit_row, const void *hit_pos, const void *hit_score)
+{
+    BXMI_TRY(rows_check(who, tracks, n_tracks, n, width, row_off, total));  // (n above 2^31-1 is refused here: hit_row is int32)
+    if (!threshold) return fail(BXMI_EINVAL, "%s: NULL threshold", who);
+    if (!mat_hits) return fail(BXMI_EINVAL, "%s: NULL mat_hits", who);
+    if (cap < 0) return fail(BXMI_EINVAL, "%s: cap = %lld is negative", who, (long long)cap);
+    if (cap > 0 && (!hit_row || !hit_pos || !hit_score)) return fail(BXMI_EINVAL, "%s: NULL hit array with cap = %lld", who, (long long)cap);
+    if (!pwm) return fail(BXMI_EINVAL, "%s: NULL matrix set", who);
+    for (int32_t m = 0; m < pwm->n_mats; m++)
+        if (threshold[m] != threshold[m]) return fail(BXMI_EINVAL, "%s: threshold[%d] is NaN", who, (int)m);
+    if (total > PW_OUT_MAX / pwm->n_mats)
+        return fail(BXMI_EINVAL, "%s: total = %lld elements under each of %d matrices is more than the hit index holds", who, (long long)total,
+                    (int)pwm->n_mats);
+    if (n > 0 && (!track_of || !start)) return fail(BXMI_EINVAL, "%s: NULL array", who);
+    return BXMI_OK;
+}
+
+// One pass of pw_hits_kernel over the whole batch, a workgroup per tile (measured against grids of 8 and of 16 workgroups per compute
+// unit striding over the tiles: DESIGN.md 3.15), in launches of at most PH_TILES_PER_LAUNCH tiles.  FILL == false: S.hit_counts,
+// their scan into S.hit_bases, and mat_hits[n_mats + 1] (host) from it -- BLOCKS on `st`.  FILL == true: the three hit arrays from
+// S.hit_bases, queued.
+template <bool FILL>
+static int pwm_hits_pass(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width, const int64_t *row_off,
+                         int64_t total, int do_mask, const bxmi_pwm_t *pwm, const float *threshold, int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos,
+                         float *hit_score, hipStream_t st)
+{
+    const int64_t tiles = div_up(total, PW_TILE), cells = tiles * pwm->n_mats;
+    PhThresholds thr{};
+    for (int32_t m = 0; m < pwm->n_mats; m++) thr.t[m] = threshold[m];
+    if (!FILL) {
+        BXMI_TRY(S.hit_counts.reserve((size_t)cells * sizeof(int32_t)));
+        BXMI_TRY(S.hit_bases.reserve((size_t)(cells + 1 + pwm->n_mats + 1) * sizeof(int64_t)));
+    }
+    BXMI_TRY(ph_each_launch(tiles, PH_TILES_PER_LAUNCH, PH_TILES_PER_LAUNCH, [&](int64_t first, int64_t count, unsigned grid) {
+        hipLaunchKernelGGL(pw_hits_kernel<FILL>, dim3(grid), dim3(PW_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of, start, n, (int)width, row_off,
+                           total, do_mask, pwm->set(), thr, first, count, tiles, S.hit_counts.as<int32_t>(), S.hit_bases.as<int64_t>(), hit_row, hit_pos,
+                           hit_score);
+        BXMI_LAUNCH_CHECK();
+        return (int)BXMI_OK;
+    }));
+    if (FILL) return BXMI_OK;
+    int64_t *bases = S.hit_bases.as<int64_t>(), *heads = bases + cells + 1;
+    BXMI_TRY((device_scan<int32_t, int64_t, OpSum, false>(S.hit_counts.as<int32_t>(), bases, cells, (int64_t)0, bases + cells, S.hit_scan, st)));
+    hipLaunchKernelGGL(ph_heads_kernel, dim3(1), dim3(64), 0, st, bases, tiles, (int)pwm->n_mats + 1, heads);
+    BXMI_LAUNCH_CHECK();
+    BXMI_HIP(hipMemcpyAsync(mat_hits, heads, (size_t)(pwm->n_mats + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    BXMI_HIP(hipStreamSynchronize(st));
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_twobit_pwm_hits_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
+                                        int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm,
+                                        const float *threshold, int64_t cap, int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos, float *hit_score,
+                                        void *stream)
+{
+    const char *who = "bxmi_twobit_pwm_hits_dev";
+    BXMI_TRY(pwm_hits_check(who, tracks, n_tracks, track_of, start, n, width, row_off_or_null, total, pwm, threshold, cap, mat_hits, hit_row, hit_pos,
+                            hit_score));
+    for (int32_t m = 0; m <= pwm->n_mats; m++) mat_hits[m] = 0;
+    if (n == 0 || total == 0) return BXMI_OK;
+    std::lock_guard<std::mutex> hold(g_sequence.lock);
+    BXMI_TRY(g_sequence.enter());
+    SequenceBufs &S = g_sequence.bufs;
+    const hipStream_t st = as_stream(stream);
+    BXMI_TRY(sequence_fill_table(S, tracks, n_tracks, st));
+    BXMI_TRY(pwm_hits_pass<false>(S, n_tracks, track_of, start, n, width, row_off_or_null, total, do_mask != 0, pwm, threshold, mat_hits, nullptr, nullptr,
+                                  nullptr, st));
+    const int64_t hits = mat_hits[pwm->n_mats];
+    if (hits > cap) return fail(BXMI_ERANGE, "%s: %lld hits need larger arrays than cap=%lld", who, (long long)hits, (long long)cap);
+    if (hits == 0) return BXMI_OK;
+    return pwm_hits_pass<true>(S, n_tracks, track_of, start, n, width, row_off_or_null, total, do_mask != 0, pwm, threshold, nullptr, hit_row, hit_pos,
+                               hit_score, st);
+}
+
+extern "C" int bxmi_twobit_pwm_hits(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                                    const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, const float *threshold, int64_t cap,
+                                    int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos, float *hit_score)
+{
+    const char *who = "bxmi_twobit_pwm_hits";
+    const int64_t *row_off = row_off_or_null;
+    BXMI_TRY(pwm_hits_check(who, tracks, n_tracks, track_of, start, n, width, row_off, total, pwm, threshold, cap, mat_hits, hit_row, hit_pos, hit_score));
+    BXMI_TRY(offsets_check(who, row_off, n, total));
+    BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    for (int32_t m = 0; m <= pwm->n_mats; m++) mat_hits[m] = 0;
+    if (n == 0 || total == 0) return BXMI_OK;
+    std::lock_guard<std::mutex> hold(g_sequence.lock);
+    BXMI_TRY(g_sequence.enter(true));
+    SequenceBufs &S = g_sequence.bufs;
+    const hipStream_t st = g_sequence.stream;
+    // nothing per base comes back: the rows go to the device whole, as for the best hits
+    const size_t in_bytes = (size_t)n * sizeof(int32_t), off_bytes = (size_t)(n + 1) * sizeof(int64_t);
+    BXMI_TRY(S.q_track.reserve(in_bytes));
+    BXMI_TRY(S.q_start.reserve(in_bytes));
+    BXMI_TRY(sequence_fill_table(S, tracks, n_tracks, st));
+    BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of, in_bytes, hipMemcpyHostToDevice, st));
+    BXMI_HIP(hipMemcpyAsync(S.q_start.p, start, in_bytes, hipMemcpyHostToDevice, st));
+    if (row_off) {  // (q_end holds the offsets)
+        BXMI_TRY(S.q_end.reserve(off_bytes));
+        BXMI_HIP(hipMemcpyAsync(S.q_end.p, row_off, off_bytes, hipMemcpyHostToDevice, st));
+    }
+    const int64_t *d_off = row_off ? S.q_end.as<int64_t>() : nullptr;
+    BXMI_TRY(pwm_hits_pass<false>(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), n, width, d_off, total, do_mask != 0, pwm, threshold, mat_hits,
+                                  nullptr, nullptr, nullptr, st));
+    const int64_t hits = mat_hits[pwm->n_mats];
+    if (hits > cap) return fail(BXMI_ERANGE, "%s: %lld hits need larger arrays than cap=%lld", who, (long long)hits, (long long)cap);
+    if (hits == 0) return BXMI_OK;
+    const size_t hit_bytes = (size_t)hits * 4;
+    BXMI_TRY(S.r.reserve(3 * hit_bytes));
+    int32_t *d_row = S.r.as<int32_t>(), *d_pos = d_row + hits;
+    float *d_score = S.r.as<float>() + 2 * hits;
+    BXMI_TRY(pwm_hits_pass<true>(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), n, width, d_off, total, do_mask != 0, pwm, threshold, nullptr,
+                                 d_row, d_pos, d_score, st));
+    BXMI_HIP(hipMemcpyAsync(hit_row, d_row, hit_bytes, hipMemcpyDeviceToHost, st));
+    BXMI_HIP(hipMemcpyAsync(hit_pos, d_pos, hit_bytes, hipMemcpyDeviceToHost, st));
+    BXMI_HIP(hipMemcpyAsync(hit_score, d_score, hit_bytes, hipMemcpyDeviceToHost, st));
     BXMI_HIP(hipStreamSynchronize(st));
     return BXMI_OK;
 }

@@ -623,6 +623,31 @@ int bxmi_twobit_pwm_best(bxmi_twobit_t *const *tracks, int32_t n_tracks, const i
 int bxmi_twobit_pwm_best_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
                              const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score, int32_t *best_pos,
                              void *stream);
+/* The hits of a scan: every element of the planes of bxmi_twobit_pwm_scores that is scored, whose score is not a NaN and is >=
+ * threshold[m] (float32 comparison; m its matrix), as one compact list -- the planes themselves are never written.  In the
+ * reference's terms, numpy.nonzero(pwms[m].score_string(row i) >= threshold[m]) and the scores there.  An unscoreable element and
+ * an arithmetic NaN are never hits; a -inf score is a hit only under a -inf threshold.  hit_row int32 (the row), hit_pos int32
+ * (the offset within the row, as best_pos) and hit_score float32 (bit for bit the plane's element) are parallel arrays holding
+ * all hits in ascending (matrix, row, offset), the same on every run; matrix m's hits are [mat_hits[m], mat_hits[m + 1]) of
+ * them, mat_hits int64 [n_mats + 1], mat_hits[0] == 0.  threshold[n_mats] and mat_hits are HOST arrays in both forms.  Rows as
+ * for bxmi_twobit_pwm_scores, `total` exact.  The hit arrays hold `cap` entries: with mat_hits[n_mats] > cap the call returns
+ * BXMI_ERANGE with mat_hits valid and the hit arrays untouched (the contract of bxmi_ivl_find); cap == 0 with NULL hit arrays
+ * asks for the counts alone.  n == 0 or total == 0: no launch, mat_hits all zero.  Refused with BXMI_EINVAL, naming the
+ * condition, before any device call: everything bxmi_twobit_pwm_scores refuses about the rows (n above 2^31-1 among it: hit_row
+ * is int32), NULL threshold, NULL mat_hits, cap < 0, a NULL hit array with cap > 0, a NULL matrix set, a NaN threshold (its
+ * index is named), total * n_mats beyond what the hit index holds.  The work is two scoring passes, one that counts per (matrix,
+ * tile of 1024 elements) and one that places; the scratch is 12 bytes per (matrix, tile).  Table, scratch and rule of the other
+ * 2bit calls: bases, composition, pwm scores, best hits and these hits, one at a time per process.  Host arrays; BLOCKS until
+ * everything is written. */
+int bxmi_twobit_pwm_hits(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                         const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, const float *threshold, int64_t cap,
+                         int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos, float *hit_score);
+/* Device variant: track_of, start, row_off and the three hit arrays are device pointers; threshold and mat_hits stay host arrays.
+ * It BLOCKS once, on `stream`, until the counts are known (as bxmi_ivl_find_dev); the hits are then queued on `stream` and may
+ * still be in flight when it returns.  Nothing outside [0, mat_hits[n_mats]) of the hit arrays is written. */
+int bxmi_twobit_pwm_hits_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                             const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, const float *threshold, int64_t cap,
+                             int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos, float *hit_score, void *stream);
 
 /* ---- BED text -> SoA columns on the host (the step before the hot path) ------
  * Strict single-pass parser for what lib/bx/bitset_builders.py:33-46 and

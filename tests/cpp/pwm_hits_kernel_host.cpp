@@ -1,0 +1,169 @@
+// The kernels of bx-python_amd/csrc/pwm_hits.hpp run on the host, their text compiled as it stands over kernel_host.hpp:
+// pw_hits_kernel<false> counting the hits per (matrix, tile), the scan of the counts in plain C++ here, ph_heads_kernel, and
+// pw_hits_kernel<true> placing the hits.  What this checks is everything in the kernels: the segments of a tile, the staging,
+// the order of every accumulator's additions, the comparison with the threshold, the ranks -- the wave totals through LDS, the
+// two sets of them, the running count per matrix across a tile's segments -- the tiles a workgroup of a smaller grid takes, the
+// launches of ph_each_launch, every index and every store (build it with -fsanitize=address,undefined and -ffp-contract=off;
+// every table, the counts and the bases are held in buffers of exactly their size, the hit arrays between two guard bands).
+//
+// usage: pwm_hits_kernel_host IN OUT
+//   IN:  int32 n_tracks, n, width, ragged, do_mask, n_mats, n_cols, grid, launch_tiles; int64 total, cap; float32 threshold[n_mats];
+//        int8 letter_col[10]; int32 mat_off[n_mats + 1]; float32 values[mat_off[n_mats]][n_cols];
+//        per track int64 size, n_blocks, m_blocks, then packed[(size + 3) / 4] (uint8), n_start[], n_size[], m_start[], m_size[]
+//        (int32); then track_of[n], start[n] (int32) and, when ragged, row_off[n + 1] (int64)
+//        grid: the workgroups of a launch at most (0: one per tile); launch_tiles: the tiles of a launch at most (0:
+//        PH_TILES_PER_LAUNCH); cap: the entries of the hit arrays (-1: exactly as many as there are hits)
+//   OUT: int64 mat_hits[n_mats + 1], int64 filled (1: the fill pass ran); then hit_row, hit_pos (int32) and hit_score (float32),
+//        each [GUARD + cap + GUARD], the guard bands as they were filled (bits 0xEEEEEEEE) -- and all of it when the hits
+//        outnumber cap
+#include "kernel_host.hpp"
+
+#include <cstdlib>
+#include <cstring>
+
+// what the kernels use that kernel_host.hpp lacks
+struct int4 {
+    int x, y, z, w;
+};
+static int4 load_int4(const int32_t *p) { return int4{p[0], p[1], p[2], p[3]}; }
+static void store_int4(int32_t *p, int a, int b, int c, int d) { p[0] = a, p[1] = b, p[2] = c, p[3] = d; }
+static Dim gridDim;
+// TB_WAVE_SUM4 and PW_WAVE_MAX64 are not run here.  PH_WAVE_PREFIX for a workgroup of host threads: everyone leaves its value,
+// meets at the barrier, sums its wave's lanes up to itself, meets again
+static void host_wave_sum4(int v[4]) { (void)v; abort(); }
+#define TB_WAVE_SUM4(v) host_wave_sum4(v)
+static unsigned long long host_wave_max64(unsigned long long key) { (void)key; abort(); }
+#define PW_WAVE_MAX64(key) host_wave_max64(key)
+#define PW_ATOMIC_MAX64(at, key) abort()
+static int g_lane_values[1024];
+static int host_wave_prefix(int v)
+{
+    g_lane_values[threadIdx.x] = v;
+    g_barrier.wait();
+    int sum = 0;
+    for (unsigned lane = threadIdx.x & ~63u; lane <= threadIdx.x; lane++) sum += g_lane_values[lane];
+    g_barrier.wait();
+    return sum;
+}
+#define PH_WAVE_PREFIX(v) host_wave_prefix(v)
+#include "pwm_hits.hpp"
+using namespace bxmi;
+
+constexpr size_t GUARD = 64;
+constexpr uint32_t GUARD_BITS = 0xEEEEEEEEu;
+
+struct Track {
+    int64_t size = 0, n_blocks = 0, m_blocks = 0;
+    std::vector<uint32_t> packed;
+    std::vector<int32_t> n_start, n_end, m_start, m_end;
+};
+
+static bool read_track(FILE *f, Track &t)
+{
+    std::vector<int64_t> head;
+    std::vector<uint8_t> bytes;
+    std::vector<int32_t> n_size, m_size;
+    if (!read_n(f, head, 3)) return false;
+    t.size = head[0], t.n_blocks = head[1], t.m_blocks = head[2];
+    if (!read_n(f, bytes, (size_t)(t.size + 3) / 4) || !read_n(f, t.n_start, t.n_blocks) || !read_n(f, n_size, t.n_blocks) ||
+        !read_n(f, t.m_start, t.m_blocks) || !read_n(f, m_size, t.m_blocks))
+        return false;
+    t.packed.assign((bytes.size() + 3) / 4, 0u);  // whole words, the rest of the last one zero
+    if (!bytes.empty()) memcpy(t.packed.data(), bytes.data(), bytes.size());
+    t.n_end.resize(t.n_start.size());
+    t.m_end.resize(t.m_start.size());
+    for (size_t i = 0; i < t.n_start.size(); i++) t.n_end[i] = t.n_start[i] + n_size[i];
+    for (size_t i = 0; i < t.m_start.size(); i++) t.m_end[i] = t.m_start[i] + m_size[i];
+    return true;
+}
+
+// [GUARD][cells][GUARD] of 32-bit words, the allocation ending where the second band ends
+struct Banded {
+    std::vector<uint32_t> raw;
+    size_t cells;
+    explicit Banded(size_t cells_) : raw(2 * GUARD + cells_, GUARD_BITS), cells(cells_) {}
+    uint32_t *body() { return raw.data() + GUARD; }
+    bool write(FILE *f) { return fwrite(raw.data(), 4, raw.size(), f) == raw.size(); }
+};
+
+int main(int argc, char **argv)
+{
+    if (argc != 3) return 2;
+    FILE *f = fopen(argv[1], "rb");
+    if (!f) return 2;
+    std::vector<int32_t> head, mat_off;
+    std::vector<int64_t> wide;
+    std::vector<int8_t> letter_col;
+    std::vector<float> values, threshold;
+    if (!read_n(f, head, 9) || !read_n(f, wide, 2)) return 2;
+    const int n_tracks = head[0], n = head[1], width = head[2], ragged = head[3], do_mask = head[4], n_mats = head[5], n_cols = head[6];
+    const int grid = head[7], launch_tiles = head[8];
+    const int64_t total = wide[0];
+    if (n_mats < 1 || n_mats > PW_MATS_MAX) return 2;
+    if (!read_n(f, threshold, n_mats) || !read_n(f, letter_col, PW_LETTERS) || !read_n(f, mat_off, (size_t)n_mats + 1) ||
+        !read_n(f, values, (size_t)mat_off[n_mats] * n_cols))
+        return 2;
+    std::vector<Track> tracks(n_tracks);
+    std::vector<TbTrack> table(n_tracks + 1);
+    for (int t = 0; t < n_tracks; t++) {
+        if (!read_track(f, tracks[t])) return 2;
+        const Track &k = tracks[t];
+        table[t] = TbTrack{k.packed.data(), k.n_start.data(), k.n_end.data(), k.m_start.data(), k.m_end.data(), nullptr, nullptr, nullptr, nullptr,
+                           k.size, k.n_blocks, k.m_blocks};
+    }
+    table[n_tracks] = TbTrack{};
+    std::vector<int32_t> track_of, start;
+    std::vector<int64_t> row_off;
+    if (!read_n(f, track_of, n) || !read_n(f, start, n) || (ragged && !read_n(f, row_off, (size_t)n + 1))) return 2;
+    fclose(f);
+
+    PwSet pw{values.data(), mat_off.data(), n_mats, n_cols, 0, 0ull};
+    for (int m = 0; m < n_mats; m++) pw.max_width = mat_off[m + 1] - mat_off[m] > pw.max_width ? mat_off[m + 1] - mat_off[m] : pw.max_width;
+    for (int k = 0; k < PW_LETTERS; k++) pw.letters |= (unsigned long long)(letter_col[k] + 1) << (5 * k);
+    PhThresholds thr{};
+    for (int m = 0; m < n_mats; m++) thr.t[m] = threshold[m];
+    const int64_t *offsets = ragged ? row_off.data() : nullptr;
+
+    const int64_t tiles = n > 0 ? (total + PW_TILE - 1) / PW_TILE : 0, cells = tiles * n_mats;
+    const int64_t per_launch = launch_tiles > 0 ? launch_tiles : PH_TILES_PER_LAUNCH, fill = grid > 0 ? grid : (tiles > 0 ? tiles : 1);
+    std::vector<int32_t> counts((size_t)cells, -1);  // (a count the kernel does not store shows)
+    std::vector<int64_t> bases((size_t)cells + 1, 0), mat_hits((size_t)n_mats + 1, 0);
+    long launches = 0;
+    ph_each_launch(tiles, per_launch, fill, [&](int64_t first, int64_t count, unsigned blocks) {
+        gridDim.x = blocks;
+        launches++;
+        run_grid(PW_THREADS, blocks, [&] {
+            pw_hits_kernel<false>(table.data(), n_tracks, track_of.data(), start.data(), n, width, offsets, total, do_mask, pw, thr, first, count, tiles,
+                                  counts.data(), nullptr, nullptr, nullptr, nullptr);
+        });
+        return 0;
+    });
+    for (int64_t k = 0; k < cells; k++) {
+        if (counts[k] < 0 || counts[k] > PW_TILE) return 3;
+        bases[k + 1] = bases[k] + counts[k];
+    }
+    gridDim.x = 1;
+    run_grid(64, 1, [&] { ph_heads_kernel(bases.data(), tiles, n_mats + 1, mat_hits.data()); });
+    const int64_t hits = mat_hits[n_mats], cap = wide[1] < 0 ? hits : wide[1];
+    if (hits != bases[cells]) return 3;
+    Banded rows((size_t)cap), pos((size_t)cap), score((size_t)cap);
+    const int64_t filled = hits <= cap && hits > 0;
+    if (filled)
+        ph_each_launch(tiles, per_launch, fill, [&](int64_t first, int64_t count, unsigned blocks) {
+            gridDim.x = blocks;
+            run_grid(PW_THREADS, blocks, [&] {
+                pw_hits_kernel<true>(table.data(), n_tracks, track_of.data(), start.data(), n, width, offsets, total, do_mask, pw, thr, first, count, tiles,
+                                     counts.data(), bases.data(), reinterpret_cast<int32_t *>(rows.body()), reinterpret_cast<int32_t *>(pos.body()),
+                                     reinterpret_cast<float *>(score.body()));
+            });
+            return 0;
+        });
+    f = fopen(argv[2], "wb");
+    if (!f || fwrite(mat_hits.data(), 8, mat_hits.size(), f) != mat_hits.size() || fwrite(&filled, 8, 1, f) != 1 || !rows.write(f) || !pos.write(f) ||
+        !score.write(f))
+        return 2;
+    fclose(f);
+    printf("launches %ld\n", launches);
+    puts("pwm hits kernel host ok");
+    return 0;
+}
