@@ -286,3 +286,24 @@ class TwoBitSet:
         from . import motif
 
         return motif.hits_dev(self.tracks.values(), track_of, starts, ends, pwms, thresholds, self.do_mask, max_hits, stream)
+
+    # the k-mer spectrum of the rows (bxmi.kmers, which builds on this module)
+    def kmer_counts(self, chroms, starts, ends, k, alphabet="ACGT", case_sensitive=True, drop_last=False):
+        from . import kmers
+
+        return kmers.counts(self.tracks.values(), self._track_of(chroms), starts, ends, k, alphabet, case_sensitive, self.do_mask, drop_last)
+
+    def kmer_count_matrix(self, chroms, starts, width, k, alphabet="ACGT", case_sensitive=True, drop_last=False):
+        from . import kmers
+
+        return kmers.count_matrix(self.tracks.values(), self._track_of(chroms), starts, width, k, alphabet, case_sensitive, self.do_mask, drop_last)
+
+    def kmer_counts_dev(self, track_of, starts, ends, k, alphabet="ACGT", case_sensitive=True, drop_last=False, stream=None, out=None):
+        from . import kmers
+
+        return kmers.counts_dev(self.tracks.values(), track_of, starts, ends, k, alphabet, case_sensitive, self.do_mask, drop_last, stream, out)
+
+    def kmer_count_matrix_dev(self, track_of, starts, width, k, alphabet="ACGT", case_sensitive=True, drop_last=False, stream=None, out=None):
+        from . import kmers
+
+        return kmers.count_matrix_dev(self.tracks.values(), track_of, starts, width, k, alphabet, case_sensitive, self.do_mask, drop_last, stream, out)

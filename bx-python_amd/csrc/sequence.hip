@@ -4,6 +4,8 @@
 // is this unit's own, so these calls do not share the one-call-at-a-time rule with the summaries, only with each other.
 // Position weight matrices scored over those rows (bxmi_pwm_*, bxmi_twobit_pwm_*): kernels and semantics in pwm.hpp, those of the
 // thresholded hits (bxmi_twobit_pwm_hits*) in pwm_hits.hpp; they use the same table and scratch and so the same rule.
+// The k-mer spectrum of those rows (bxmi_twobit_kmer_counts*): kernel and semantics in kmer.hpp; the same table, scratch and rule.
+#include <atomic>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -22,6 +24,7 @@
 #include "twobit.hpp"
 #include "pwm.hpp"
 #include "pwm_hits.hpp"
+#include "kmer.hpp"
 #include "track_batch.hpp"
 
 using namespace bxmi;
@@ -44,6 +47,8 @@ constexpr int64_t TB_COMP_SLAB = 1 << 22;             // rows per slab of the ho
 constexpr int64_t PW_SLAB = (int64_t)PW_TILE << 12;   // output elements of ALL planes per slab of the host form of the scores (16 MiB): whole tiles per plane
 constexpr int64_t PW_TILES_PER_LAUNCH = 1 << 22;      // (2^22 workgroups of 256)
 constexpr int64_t PW_OUT_MAX = INT64_MAX / 8;         // elements of all planes: their byte offsets stay far inside int64
+constexpr int64_t KM_SLAB_CELLS = 1 << 24;            // counters per slab of rows of the host form of the k-mer counts (64 MiB); at least one row
+constexpr int64_t KM_OUT_MAX = INT64_MAX / 8;         // counters of all rows: their byte offsets stay far inside int64
 
 struct SequenceBufs {
     DevBuf table;                         // TbTrack [n_tracks + 1], the last one the spare entry
@@ -672,5 +677,104 @@ extern "C" int bxmi_twobit_pwm_hits(bxmi_twobit_t *const *tracks, int32_t n_trac
     BXMI_HIP(hipMemcpyAsync(hit_pos, d_pos, hit_bytes, hipMemcpyDeviceToHost, st));
     BXMI_HIP(hipMemcpyAsync(hit_score, d_score, hit_bytes, hipMemcpyDeviceToHost, st));
     BXMI_HIP(hipStreamSynchronize(st));
+    return BXMI_OK;
+}
+
+// ---- k-mer counts (kmer.hpp) ----
+static std::atomic<int> g_km_force{KM_PLAN};
+
+extern "C" int bxmi_twobit_kmer_force(int way)
+{
+    if (way != KM_PLAN && way != KM_FORCE_LDS && way != KM_FORCE_DIRECT)
+        return fail(BXMI_EINVAL, "bxmi_twobit_kmer_force: way = %d is none of 0 (plan), 1 (LDS histogram), 2 (straight to HBM)", way);
+    g_km_force.store(way);
+    return BXMI_OK;
+}
+
+// what both forms check, and the kernel's description of the words; `row_off` is only tested for being there
+static int kmer_check(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const void *track_of, const void *start, int64_t n, int32_t width,
+                      const void *row_off, int64_t total, int k, int radix, const int8_t *digits, const void *counts, KmSpec &spec)
+{
+    BXMI_TRY(rows_check(who, tracks, n_tracks, n, width, row_off, total));
+    if (k < 1) return fail(BXMI_EINVAL, "%s: k = %d, must be at least 1", who, k);
+    if (radix < 2 || radix > 4) return fail(BXMI_EINVAL, "%s: radix = %d outside [2, 4]", who, radix);
+    const int bins = km_bins(k, radix);
+    if (bins > KM_BINS_MAX) return fail(BXMI_EINVAL, "%s: radix^k = %d^%d is more than KM_BINS_MAX = %d bins", who, radix, k, KM_BINS_MAX);
+    if (!digits) return fail(BXMI_EINVAL, "%s: NULL digits", who);
+    for (int c = 0; c < 8; c++)
+        if (digits[c] < -1 || digits[c] >= radix)
+            return fail(BXMI_EINVAL, "%s: digits[%d] = %d outside [-1, radix = %d)", who, c, (int)digits[c], radix);
+    if (n > KM_OUT_MAX / bins)
+        return fail(BXMI_EINVAL, "%s: n = %lld rows of %d bins are more than the output index holds", who, (long long)n, bins);
+    if (n > 0 && !counts) return fail(BXMI_EINVAL, "%s: NULL counts", who);
+    if (n > 0 && (!track_of || !start)) return fail(BXMI_EINVAL, "%s: NULL array", who);
+    spec = KmSpec{k, radix, bins, km_pack_digits(digits), g_km_force.load()};
+    return BXMI_OK;
+}
+
+// counts [n_rows][bins] = 0, then the windows that start at elements [o_first, o_first + count) of rows [row_base, row_base + n_rows):
+// one launch of at most a device's fill of workgroups, each walking every gridDim.x-th tile (`count` may be a bound)
+static int kmer_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n_rows, int64_t row_base, int32_t width,
+                       const int64_t *row_off, int64_t o_first, int64_t count, int do_mask, const KmSpec &spec, int32_t *counts, hipStream_t st)
+{
+    BXMI_HIP(hipMemsetAsync(counts, 0, (size_t)n_rows * (size_t)spec.bins * sizeof(int32_t), st));
+    if (count <= 0) return BXMI_OK;
+    const int64_t tiles = div_up(count, KM_TILE), fill = (int64_t)device_props().cus * 8;
+    hipLaunchKernelGGL(km_counts_kernel, dim3((unsigned)(tiles < fill ? tiles : fill)), dim3(KM_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of,
+                       start, n_rows, row_base, (int)width, row_off, o_first, count, do_mask, spec, counts);
+    BXMI_LAUNCH_CHECK();
+    return BXMI_OK;
+}
+
+extern "C" int bxmi_twobit_kmer_counts_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
+                                           int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, int k, int radix,
+                                           const int8_t *digits, int32_t *counts, void *stream)
+{
+    const char *who = "bxmi_twobit_kmer_counts_dev";
+    KmSpec spec{};
+    BXMI_TRY(kmer_check(who, tracks, n_tracks, track_of, start, n, width, row_off_or_null, total, k, radix, digits, counts, spec));
+    if (n == 0) return BXMI_OK;
+    std::lock_guard<std::mutex> hold(g_sequence.lock);
+    BXMI_TRY(g_sequence.enter());
+    BXMI_TRY(sequence_fill_table(g_sequence.bufs, tracks, n_tracks, as_stream(stream)));
+    return kmer_launch(g_sequence.bufs, n_tracks, track_of, start, n, 0, width, row_off_or_null, 0, total, do_mask != 0, spec, counts, as_stream(stream));
+}
+
+extern "C" int bxmi_twobit_kmer_counts(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                                       const int64_t *row_off_or_null, int64_t total, int do_mask, int k, int radix, const int8_t *digits, int32_t *counts)
+{
+    const char *who = "bxmi_twobit_kmer_counts";
+    const int64_t *row_off = row_off_or_null;
+    KmSpec spec{};
+    BXMI_TRY(kmer_check(who, tracks, n_tracks, track_of, start, n, width, row_off, total, k, radix, digits, counts, spec));
+    BXMI_TRY(offsets_check(who, row_off, n, total));
+    BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    if (n == 0) return BXMI_OK;
+    std::lock_guard<std::mutex> hold(g_sequence.lock);
+    BXMI_TRY(g_sequence.enter(true));
+    SequenceBufs &S = g_sequence.bufs;
+    const hipStream_t st = g_sequence.stream;
+    BXMI_TRY(sequence_fill_table(S, tracks, n_tracks, st));
+    // slabs of whole rows, KM_SLAB_CELLS counters each (at least one row): the bases of a slab's rows are one stretch of the flat axis
+    const int64_t slab = KM_SLAB_CELLS / spec.bins;
+    for (int64_t r0 = 0; r0 < n; r0 += slab) {
+        const int64_t m = n - r0 < slab ? n - r0 : slab;
+        const int64_t o0 = row_off ? row_off[r0] : r0 * (int64_t)width, o1 = row_off ? row_off[r0 + m] : (r0 + m) * (int64_t)width;
+        const size_t in_bytes = (size_t)m * sizeof(int32_t), off_bytes = (size_t)(m + 1) * sizeof(int64_t);
+        const size_t out_bytes = (size_t)m * (size_t)spec.bins * sizeof(int32_t);
+        BXMI_TRY(S.q_track.reserve(in_bytes));
+        BXMI_TRY(S.q_start.reserve(in_bytes));
+        BXMI_TRY(S.r.reserve(out_bytes));
+        BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of + r0, in_bytes, hipMemcpyHostToDevice, st));
+        BXMI_HIP(hipMemcpyAsync(S.q_start.p, start + r0, in_bytes, hipMemcpyHostToDevice, st));
+        if (row_off) {  // (q_end holds the slab's offsets)
+            BXMI_TRY(S.q_end.reserve(off_bytes));
+            BXMI_HIP(hipMemcpyAsync(S.q_end.p, row_off + r0, off_bytes, hipMemcpyHostToDevice, st));
+        }
+        BXMI_TRY(kmer_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), m, r0, width, row_off ? S.q_end.as<int64_t>() : nullptr, o0, o1 - o0,
+                             do_mask != 0, spec, S.r.as<int32_t>(), st));
+        BXMI_HIP(hipMemcpyAsync(counts + r0 * (int64_t)spec.bins, S.r.p, out_bytes, hipMemcpyDeviceToHost, st));
+        BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
+    }
     return BXMI_OK;
 }

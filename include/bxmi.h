@@ -34,6 +34,8 @@
  *                                TwoBitSequence.get / __getitem__, a batch of regions per call -> bxmi_twobit_*
  *   lib/bx/motif/_pwm.pyx:23-55, pwm.py:141-149
  *                                ScoringMatrix.score_string over the sequence of a batch of regions -> bxmi_pwm_*, bxmi_twobit_pwm_*
+ *   lib/bx/intseq/ngramcount.pyx:34-85, seqmapping.py:36-48, _seqmapping.pyx:24-67
+ *                                count_ngrams(mapping.translate(...)) over the sequence of a batch of regions -> bxmi_twobit_kmer_*
  *   (intersection.pyx has no C ABI of its own: its cdef classes are the
  *    interface, so the entry points below are what a Cython/ctypes shim of
  *    those classes binds; see INTEGRATION.md.)
@@ -648,6 +650,36 @@ int bxmi_twobit_pwm_hits(bxmi_twobit_t *const *tracks, int32_t n_tracks, const i
 int bxmi_twobit_pwm_hits_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
                              const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, const float *threshold, int64_t cap,
                              int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos, float *hit_score, void *stream);
+
+/* ---- k-mer counts over 2bit rows  (lib/bx/intseq/ngramcount.pyx:34-85 over lib/bx/seqmapping.py:36-48, _seqmapping.pyx:24-67) ----
+ * The reference's count_ngrams(mapping.translate(twobit[chrom].get(s, e)), k, radix) for a batch of n rows described exactly as
+ * for bxmi_twobit_pwm_best (matrix form: width >= 1, row_off NULL, total == n * width; ragged form: width == 0 and row_off[n + 1];
+ * track_of, start, do_mask).  Row i is the string of the letters bxmi_twobit_bases gives.  `digits` is int8[8], indexed by
+ * 4 * lower_case + code with codes T=0, C=1, A=2, G=3: the digit of that letter in [0, radix), or -1 for no digit; several letters
+ * may share a digit (purine/pyrimidine words are radix 2).  'N', positions outside [0, size) and rows that name no track have no
+ * digit; with do_mask == 0 nothing is lower case.  2 <= radix <= 4, k >= 1, bins = radix^k <= 16384 (KM_BINS_MAX of csrc/kmer.hpp:
+ * k = 7 at radix 4, k = 14 at radix 2).  The window at offset j of row i counts if and only if all k letters j .. j + k - 1 lie in
+ * the row and have a digit; its index is sum(digit[j + t] * radix^t for t in 0 .. k - 1), the first letter least significant
+ * (ngramcount.pyx:73-82).  `counts` is int32 [n][bins], written whole whatever it held.  EVERY window of a row is counted, the
+ * last one included; the reference's loop stops one window early (`for i from 0 <= i < (n_ints - n)`, ngramcount.pyx:71), which is
+ * reproduced by the caller shortening every row by one base (bxmi.kmers: drop_last=True), not here.  Integer work: the counts are
+ * the reference's bit for bit.  Refused with BXMI_EINVAL, naming the condition, before any device call: everything
+ * bxmi_twobit_pwm_best refuses about the rows; k < 1; radix outside [2, 4]; bins above 16384; a digit outside [-1, radix); NULL
+ * digits, NULL counts with n > 0; n * bins beyond what the output index holds.  n == 0 succeeds without a launch.  These calls use
+ * the track table and the scratch of the 2bit calls: one 2bit call (bases, composition, pwm, kmer) at a time per process.  Host
+ * arrays; goes through the device in slabs of rows and BLOCKS until `counts` is written. */
+int bxmi_twobit_kmer_counts(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                            const int64_t *row_off_or_null, int64_t total, int do_mask, int k, int radix, const int8_t *digits, int32_t *counts);
+/* Device variant: `tracks` stay host handles and `digits` a host array; track_of, start, row_off and counts are device pointers.
+ * `counts` is zeroed and filled on `stream`: stream-ordered, no host synchronisation.  It reads where the rows end from
+ * row_off[n] itself: in its ragged form `total` may be any bound >= row_off[n], as for bxmi_twobit_pwm_best_dev.  Unchecked
+ * entries as bxmi_twobit_bases_dev.  A row's cost is its bases, whatever its length. */
+int bxmi_twobit_kmer_counts_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                                const int64_t *row_off_or_null, int64_t total, int do_mask, int k, int radix, const int8_t *digits, int32_t *counts,
+                                void *stream);
+/* For measurements and tests: how the calls after this one accumulate, whatever csrc/kmer.hpp's km_use_lds would choose -- 0 its
+ * choice (the default), 1 the LDS histogram wherever bins allow it, 2 straight to HBM.  The counts are the same. */
+int bxmi_twobit_kmer_force(int way);
 
 /* ---- BED text -> SoA columns on the host (the step before the hot path) ------
  * Strict single-pass parser for what lib/bx/bitset_builders.py:33-46 and
