@@ -15,9 +15,10 @@
 //                      KM_RUN * i.  A grid smaller than the tiles loops.  A tile is walked ROW SEGMENT by row segment; everything
 //                      about a segment is uniform over the workgroup.  A thread's windows in a segment need its KM_RUN letters and a
 //                      halo of k - 1 more (k - 1 <= 6 at radix 4, <= 13 at radix 2): at most 21 letters from at most three aligned
-//                      32-bit words of packed bytes (tb_word).  The run of N blocks and of mask blocks that meets the segment and
-//                      its halo is found by two searches per list and staged TB_CHUNK at a time (tb_covered), which gives the
-//                      thread a bit per letter; from the bits and the codes it builds `bad`, a bit per position without a digit
+//                      32-bit words of packed bytes (tb_word).  The segment, its track and the N and mask blocks over a thread's
+//                      letters come from twobit.hpp's row-segment layer: tb_segment (sa_row_of), tb_letters with the halo, and
+//                      tb_block_bits (two sm_first_above searches per list, the run staged TB_CHUNK at a time, tb_covered), which gives
+//                      the thread a bit per letter; from the bits and the codes it builds `bad`, a bit per position without a digit
 //                      (positions past the row's end or outside the sequence included: a -1 digit is nothing special), and `dig`,
 //                      two bits per position.  Window j is bad where any of bits j .. j + k - 1 of `bad` is set.
 //   accumulation       per segment, one of two ways (km_use_lds):
@@ -103,29 +104,13 @@ __global__ __launch_bounds__(KM_THREADS) void km_counts_kernel(const TbTrack *__
         const int64_t t1 = t0 + KM_TILE < o_end ? t0 + KM_TILE : o_end;
         const int64_t e0 = t0 + KM_RUN * tid;  // this thread's window starts: [e0, e0 + KM_RUN)
         for (int64_t o = t0; o < t1;) {  // the segment [o, seg1) of row r, whose elements are [r_lo, r_hi)
-            int64_t r, r_lo, r_hi;
-            if (row_off) {
-                r = sa_row_of(g_off, n_rows, o);
-                r_lo = g_off[r];
-                r_hi = g_off[r + 1];
-            } else {
-                const int64_t row = o / width;
-                r = row - row_base;
-                r_lo = row * width;
-                r_hi = r_lo + width;
-            }
-            int64_t seg1 = r_hi < t1 ? r_hi : t1;
-            if (seg1 <= o) seg1 = o + 1;  // (offsets that are not what they should be: the walk still ends)
+            const TbSegment sg = tb_segment(g_off, n_rows, row_base, width, o, t1);
+            const int64_t r = sg.r, seg1 = sg.seg1;
             const int seg_len = (int)(seg1 - o);
-            const int t = g_track[r];
-            const bool named = t >= 0 && t < n_tracks;
-            const TbTrack tr = table[named ? t : n_tracks];  // (the spare entry: size 0)
-            const int64_t p0 = (int64_t)g_start[r] + (o - r_lo);  // the position of the segment's first window start
-            // the positions under the segment's windows that are letters of the row: before the row's end, inside the sequence
-            int64_t c1 = p0 + seg_len + k - 1;
-            if (c1 > (int64_t)g_start[r] + (r_hi - r_lo)) c1 = (int64_t)g_start[r] + (r_hi - r_lo);
-            if (c1 > tr.size) c1 = tr.size;
-            const int64_t c0 = p0 > 0 ? p0 : 0;
+            // p0: the position of the segment's first window start; [c0, c1): the positions under the segment's windows that are
+            // letters of the row
+            const TbLetters lt = tb_letters(table, n_tracks, g_track[r], g_start[r], sg.r_lo, sg.r_hi, o, seg_len + k - 1);
+            const int64_t p0 = lt.p0, c0 = lt.c0, c1 = lt.c1;
             // this thread's window starts of the segment: [lo_el, lo_el + n_win), the positions under them [first, first + span)
             const int64_t lo_el = e0 > o ? e0 : o, hi_el = e0 + KM_RUN < seg1 ? e0 + KM_RUN : seg1;
             const int n_win = lo_el < hi_el ? (int)(hi_el - lo_el) : 0;
@@ -141,39 +126,19 @@ __global__ __launch_bounds__(KM_THREADS) void km_counts_kernel(const TbTrack *__
                 const int b = pf & 15;
                 uint32_t w0 = 0, w1 = 0, w2 = 0;  // base pf + i at bits 31 - 2 ((b + i) & 15) .. of word (b + i) >> 4
                 if (cnt) {
-                    const uint32_t BX_GLOBAL *packed = as_global(tr.packed);
+                    const uint32_t BX_GLOBAL *packed = as_global(lt.tr.packed);
                     const int64_t w = pf >> 4, last = (pf + cnt - 1) >> 4;
                     w0 = tb_word(packed, w);
                     if (last > w) w1 = tb_word(packed, w + 1);
                     if (last > w + 1) w2 = tb_word(packed, w + 2);
                 }
-                unsigned is_n = 0, is_m = 0;
-                for (int list = 0; list < (do_mask ? 2 : 1); list++) {
-                    const int64_t blocks = list ? tr.m_blocks : tr.n_blocks;
-                    if (blocks == 0) continue;
-                    const int32_t BX_GLOBAL *b_st = as_global(list ? tr.m_start : tr.n_start), *b_en = as_global(list ? tr.m_end : tr.n_end);
-                    const int64_t lo = sm_first_above(b_en, 0, blocks, (int)c0);        // the first block that ends after the letters start
-                    const int64_t hi = sm_first_above(b_st, lo, blocks, (int)(c1 - 1));  // the first that starts at or after their end
-                    unsigned bits = 0;
-                    for (int64_t at = lo; at < hi; at += TB_CHUNK) {
-                        const int staged = hi - at < TB_CHUNK ? (int)(hi - at) : TB_CHUNK;
-                        __syncthreads();  // the previous chunk has been searched
-                        for (int q = tid; q < staged; q += KM_THREADS) {
-                            l_st[q] = b_st[at + q];
-                            l_en[q] = b_en[at + q];
-                        }
-                        __syncthreads();
-                        if (cnt) bits |= tb_covered(l_st, l_en, staged, pf, cnt);
-                    }
-                    if (list) is_m = bits;
-                    else is_n = bits;
-                }
+                const TbBits bits = tb_block_bits<KM_THREADS>(lt.tr, do_mask, c0, c1, pf, cnt, tid, l_st, l_en);
                 for (int i = 0; i < cnt; i++) {
                     const int at = b + i;
                     const uint32_t word = at < 16 ? w0 : at < 32 ? w1 : w2;
                     const unsigned code = (word >> (30 - 2 * (at & 15))) & 3u;
-                    const unsigned cls = code + ((is_m >> i) & 1u ? 4u : 0u);
-                    const unsigned d1 = (is_n >> i) & 1u ? 0u : (spec.digits >> (4 * cls)) & 15u;  // digit + 1
+                    const unsigned cls = code + ((bits.is_m >> i) & 1u ? 4u : 0u);
+                    const unsigned d1 = (bits.is_n >> i) & 1u ? 0u : (spec.digits >> (4 * cls)) & 15u;  // digit + 1
                     if (d1 == 0) continue;
                     bad &= ~(1u << (qa + i));
                     dig |= (uint64_t)(d1 - 1u) << (2 * (qa + i));

@@ -215,6 +215,32 @@ static int offsets_check(const char *who, const int64_t *row_off, int64_t n, int
     return BXMI_OK;
 }
 
+// What the host forms put on the device of rows [r0, r0 + m): track and start into S.q_track and S.q_start and, with row_off, their
+// m + 1 offsets into S.q_end -> *d_off, the offsets on the device (nullptr without).  Queued on st: the caller waits before the next use.
+static int stage_rows(SequenceBufs &S, const int32_t *track_of, const int32_t *start, const int64_t *row_off, int64_t r0, int64_t m, const int64_t **d_off,
+                      hipStream_t st)
+{
+    const size_t in_bytes = (size_t)m * sizeof(int32_t), off_bytes = (size_t)(m + 1) * sizeof(int64_t);
+    BXMI_TRY(S.q_track.reserve(in_bytes));
+    BXMI_TRY(S.q_start.reserve(in_bytes));
+    BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of + r0, in_bytes, hipMemcpyHostToDevice, st));
+    BXMI_HIP(hipMemcpyAsync(S.q_start.p, start + r0, in_bytes, hipMemcpyHostToDevice, st));
+    *d_off = nullptr;
+    if (row_off) {
+        BXMI_TRY(S.q_end.reserve(off_bytes));
+        BXMI_HIP(hipMemcpyAsync(S.q_end.p, row_off + r0, off_bytes, hipMemcpyHostToDevice, st));
+        *d_off = S.q_end.as<int64_t>();
+    }
+    return BXMI_OK;
+}
+
+// the workgroups of a launch that strides over `tiles` tiles: at most a device's fill, 8 per compute unit
+static unsigned fill_grid(int64_t tiles)
+{
+    const int64_t fill = (int64_t)device_props().cus * 8;
+    return (unsigned)(tiles < fill ? tiles : fill);
+}
+
 // output bytes [o_first, o_first + count) of rows [row_base, row_base + n_rows); `out` is byte o_first's address
 static int bases_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n_rows, int64_t row_base, int32_t width,
                         const int64_t *row_off, int64_t o_first, int64_t count, int do_mask, int pad, uint8_t *out, hipStream_t st)
@@ -259,19 +285,11 @@ extern "C" int bxmi_twobit_bases(bxmi_twobit_t *const *tracks, int32_t n_tracks,
     for (int64_t o0 = 0; o0 < total; o0 += TB_SLAB) {  // slabs of whole tiles; a row may lie in several
         const int64_t count = total - o0 < TB_SLAB ? total - o0 : TB_SLAB;
         const SaRows rows = sa_rows_of(row_off, n, width, o0, count);  // the slab's rows
-        const int64_t r0 = rows.r0, m = rows.m;
-        const size_t in_bytes = (size_t)m * sizeof(int32_t), off_bytes = (size_t)(m + 1) * sizeof(int64_t);
-        BXMI_TRY(S.q_track.reserve(in_bytes));
-        BXMI_TRY(S.q_start.reserve(in_bytes));
+        const int64_t *d_off;
+        BXMI_TRY(stage_rows(S, track_of, start, row_off, rows.r0, rows.m, &d_off, st));
         BXMI_TRY(S.r.reserve((size_t)count));
-        BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of + r0, in_bytes, hipMemcpyHostToDevice, st));
-        BXMI_HIP(hipMemcpyAsync(S.q_start.p, start + r0, in_bytes, hipMemcpyHostToDevice, st));
-        if (row_off) {  // (q_end holds the slab's offsets)
-            BXMI_TRY(S.q_end.reserve(off_bytes));
-            BXMI_HIP(hipMemcpyAsync(S.q_end.p, row_off + r0, off_bytes, hipMemcpyHostToDevice, st));
-        }
-        BXMI_TRY(bases_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), m, r0, width, row_off ? S.q_end.as<int64_t>() : nullptr, o0, count,
-                              do_mask != 0, pad, S.r.as<uint8_t>(), st));
+        BXMI_TRY(bases_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), rows.m, rows.r0, width, d_off, o0, count, do_mask != 0, pad,
+                              S.r.as<uint8_t>(), st));
         BXMI_HIP(hipMemcpyAsync(out + o0, S.r.p, (size_t)count, hipMemcpyDeviceToHost, st));
         BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
     }
@@ -418,8 +436,7 @@ static int pwm_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of
                       unsigned long long *keys, hipStream_t st)
 {
     if (keys) {  // one launch of at most a device's fill of workgroups, each walking every gridDim.x-th tile: `count` may be a bound
-        const int64_t tiles = div_up(count, PW_TILE), fill = (int64_t)device_props().cus * 8;
-        hipLaunchKernelGGL(pw_scores_kernel<true>, dim3((unsigned)(tiles < fill ? tiles : fill)), dim3(PW_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks,
+        hipLaunchKernelGGL(pw_scores_kernel<true>, dim3(fill_grid(div_up(count, PW_TILE))), dim3(PW_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks,
                            track_of, start, n_rows, row_base, (int)width, row_off, o_first, count, do_mask, pwm->set(), (float *)nullptr, (int64_t)0, keys, n_rows);
         BXMI_LAUNCH_CHECK();
         return BXMI_OK;
@@ -470,19 +487,11 @@ extern "C" int bxmi_twobit_pwm_scores(bxmi_twobit_t *const *tracks, int32_t n_tr
     for (int64_t o0 = 0; o0 < total; o0 += slab) {
         const int64_t count = total - o0 < slab ? total - o0 : slab;
         const SaRows rows = sa_rows_of(row_off, n, width, o0, count);  // the slab's rows
-        const int64_t r0 = rows.r0, m = rows.m;
-        const size_t in_bytes = (size_t)m * sizeof(int32_t), off_bytes = (size_t)(m + 1) * sizeof(int64_t);
-        BXMI_TRY(S.q_track.reserve(in_bytes));
-        BXMI_TRY(S.q_start.reserve(in_bytes));
+        const int64_t *d_off;
+        BXMI_TRY(stage_rows(S, track_of, start, row_off, rows.r0, rows.m, &d_off, st));
         BXMI_TRY(S.r.reserve((size_t)count * sizeof(float) * (size_t)pwm->n_mats));
-        BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of + r0, in_bytes, hipMemcpyHostToDevice, st));
-        BXMI_HIP(hipMemcpyAsync(S.q_start.p, start + r0, in_bytes, hipMemcpyHostToDevice, st));
-        if (row_off) {  // (q_end holds the slab's offsets)
-            BXMI_TRY(S.q_end.reserve(off_bytes));
-            BXMI_HIP(hipMemcpyAsync(S.q_end.p, row_off + r0, off_bytes, hipMemcpyHostToDevice, st));
-        }
-        BXMI_TRY(pwm_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), m, r0, width, row_off ? S.q_end.as<int64_t>() : nullptr, o0, count,
-                            do_mask != 0, pwm, S.r.as<float>(), count, nullptr, st));
+        BXMI_TRY(pwm_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), rows.m, rows.r0, width, d_off, o0, count, do_mask != 0, pwm,
+                            S.r.as<float>(), count, nullptr, st));
         for (int32_t k = 0; k < pwm->n_mats; k++)  // each plane's part of the slab
             BXMI_HIP(hipMemcpyAsync(out + (int64_t)k * total + o0, S.r.as<float>() + (int64_t)k * count, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, st));
         BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
@@ -536,21 +545,14 @@ extern "C" int bxmi_twobit_pwm_best(bxmi_twobit_t *const *tracks, int32_t n_trac
     const hipStream_t st = g_sequence.stream;
     // nothing per base comes back: the rows go to the device whole and the walk is one launch
     const int64_t cells = (int64_t)pwm->n_mats * n;
-    const size_t in_bytes = (size_t)n * sizeof(int32_t), off_bytes = (size_t)(n + 1) * sizeof(int64_t), cell_bytes = (size_t)cells * 4;
-    BXMI_TRY(S.q_track.reserve(in_bytes));
-    BXMI_TRY(S.q_start.reserve(in_bytes));
+    const size_t cell_bytes = (size_t)cells * 4;
+    const int64_t *d_off;
     BXMI_TRY(S.r.reserve(2 * cell_bytes));
     BXMI_TRY(sequence_fill_table(S, tracks, n_tracks, st));
-    BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of, in_bytes, hipMemcpyHostToDevice, st));
-    BXMI_HIP(hipMemcpyAsync(S.q_start.p, start, in_bytes, hipMemcpyHostToDevice, st));
-    if (row_off) {  // (q_end holds the offsets)
-        BXMI_TRY(S.q_end.reserve(off_bytes));
-        BXMI_HIP(hipMemcpyAsync(S.q_end.p, row_off, off_bytes, hipMemcpyHostToDevice, st));
-    }
+    BXMI_TRY(stage_rows(S, track_of, start, row_off, 0, n, &d_off, st));
     float *d_score = S.r.as<float>();
     int32_t *d_pos = S.r.as<int32_t>() + cells;
-    BXMI_TRY(pwm_best_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), n, width, row_off ? S.q_end.as<int64_t>() : nullptr, total,
-                             do_mask != 0, pwm, d_score, d_pos, st));
+    BXMI_TRY(pwm_best_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), n, width, d_off, total, do_mask != 0, pwm, d_score, d_pos, st));
     BXMI_HIP(hipMemcpyAsync(best_score, d_score, cell_bytes, hipMemcpyDeviceToHost, st));
     BXMI_HIP(hipMemcpyAsync(best_pos, d_pos, cell_bytes, hipMemcpyDeviceToHost, st));
     BXMI_HIP(hipStreamSynchronize(st));
@@ -651,17 +653,9 @@ extern "C" int bxmi_twobit_pwm_hits(bxmi_twobit_t *const *tracks, int32_t n_trac
     SequenceBufs &S = g_sequence.bufs;
     const hipStream_t st = g_sequence.stream;
     // nothing per base comes back: the rows go to the device whole, as for the best hits
-    const size_t in_bytes = (size_t)n * sizeof(int32_t), off_bytes = (size_t)(n + 1) * sizeof(int64_t);
-    BXMI_TRY(S.q_track.reserve(in_bytes));
-    BXMI_TRY(S.q_start.reserve(in_bytes));
+    const int64_t *d_off;
     BXMI_TRY(sequence_fill_table(S, tracks, n_tracks, st));
-    BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of, in_bytes, hipMemcpyHostToDevice, st));
-    BXMI_HIP(hipMemcpyAsync(S.q_start.p, start, in_bytes, hipMemcpyHostToDevice, st));
-    if (row_off) {  // (q_end holds the offsets)
-        BXMI_TRY(S.q_end.reserve(off_bytes));
-        BXMI_HIP(hipMemcpyAsync(S.q_end.p, row_off, off_bytes, hipMemcpyHostToDevice, st));
-    }
-    const int64_t *d_off = row_off ? S.q_end.as<int64_t>() : nullptr;
+    BXMI_TRY(stage_rows(S, track_of, start, row_off, 0, n, &d_off, st));
     BXMI_TRY(pwm_hits_pass<false>(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), n, width, d_off, total, do_mask != 0, pwm, threshold, mat_hits,
                                   nullptr, nullptr, nullptr, st));
     const int64_t hits = mat_hits[pwm->n_mats];
@@ -719,8 +713,7 @@ static int kmer_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_o
 {
     BXMI_HIP(hipMemsetAsync(counts, 0, (size_t)n_rows * (size_t)spec.bins * sizeof(int32_t), st));
     if (count <= 0) return BXMI_OK;
-    const int64_t tiles = div_up(count, KM_TILE), fill = (int64_t)device_props().cus * 8;
-    hipLaunchKernelGGL(km_counts_kernel, dim3((unsigned)(tiles < fill ? tiles : fill)), dim3(KM_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of,
+    hipLaunchKernelGGL(km_counts_kernel, dim3(fill_grid(div_up(count, KM_TILE))), dim3(KM_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of,
                        start, n_rows, row_base, (int)width, row_off, o_first, count, do_mask, spec, counts);
     BXMI_LAUNCH_CHECK();
     return BXMI_OK;
@@ -760,19 +753,12 @@ extern "C" int bxmi_twobit_kmer_counts(bxmi_twobit_t *const *tracks, int32_t n_t
     for (int64_t r0 = 0; r0 < n; r0 += slab) {
         const int64_t m = n - r0 < slab ? n - r0 : slab;
         const int64_t o0 = row_off ? row_off[r0] : r0 * (int64_t)width, o1 = row_off ? row_off[r0 + m] : (r0 + m) * (int64_t)width;
-        const size_t in_bytes = (size_t)m * sizeof(int32_t), off_bytes = (size_t)(m + 1) * sizeof(int64_t);
         const size_t out_bytes = (size_t)m * (size_t)spec.bins * sizeof(int32_t);
-        BXMI_TRY(S.q_track.reserve(in_bytes));
-        BXMI_TRY(S.q_start.reserve(in_bytes));
+        const int64_t *d_off;
+        BXMI_TRY(stage_rows(S, track_of, start, row_off, r0, m, &d_off, st));
         BXMI_TRY(S.r.reserve(out_bytes));
-        BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of + r0, in_bytes, hipMemcpyHostToDevice, st));
-        BXMI_HIP(hipMemcpyAsync(S.q_start.p, start + r0, in_bytes, hipMemcpyHostToDevice, st));
-        if (row_off) {  // (q_end holds the slab's offsets)
-            BXMI_TRY(S.q_end.reserve(off_bytes));
-            BXMI_HIP(hipMemcpyAsync(S.q_end.p, row_off + r0, off_bytes, hipMemcpyHostToDevice, st));
-        }
-        BXMI_TRY(kmer_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), m, r0, width, row_off ? S.q_end.as<int64_t>() : nullptr, o0, o1 - o0,
-                             do_mask != 0, spec, S.r.as<int32_t>(), st));
+        BXMI_TRY(kmer_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), m, r0, width, d_off, o0, o1 - o0, do_mask != 0, spec,
+                             S.r.as<int32_t>(), st));
         BXMI_HIP(hipMemcpyAsync(counts + r0 * (int64_t)spec.bins, S.r.p, out_bytes, hipMemcpyDeviceToHost, st));
         BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
     }

@@ -18,6 +18,10 @@
 //                      that meet it; the run is streamed through LDS TB_CHUNK blocks at a time, every thread searching the staged
 //                      ends for the first block that ends after its first position and walking on while blocks start before its
 //                      last: a 16-bit mask of its positions.  A segment that meets no block of a list runs no chunk loop for it.
+//   the row-segment layer   tb_segment, tb_letters, tb_block_bits, tb_codes: the walk above as this kernel and km_counts_kernel
+//                      (kmer.hpp) share it; the latter's `want` positions per segment hold a halo beyond the segment.  Described
+//                      once, at the helpers.  (pw_scores_kernel and pw_hits_kernel still carry the same walk as their own text:
+//                      on the helpers they measured 1 - 3 % slower at unchanged register counts)
 //   tb_count_kernel    (creation) the four code counts of every checkpoint block of TB_CKPT bases, one wave per block, as four
 //                      planes; a device scan per plane (primitives.hpp) and tb_interleave_kernel turn them into the running totals
 //                      ckpt[k] = counts of bases [0, TB_CKPT * k) as one 16-byte entry (T, C, A, G).
@@ -185,6 +189,102 @@ __device__ __forceinline__ unsigned tb_covered(const int32_t *l_st, const int32_
     return bits;
 }
 
+// ---- the row-segment layer ----
+// What tb_bases_kernel and km_counts_kernel (kmer.hpp) share, and what a further kernel over 2bit rows starts from: a tile of the
+// flat axis is walked row segment by row segment, and per segment -- everything here is uniform over the workgroup but pf, cnt and
+// tid -- tb_segment finds the row, tb_letters its track and the positions that are letters, tb_block_bits the N and mask blocks
+// over a thread's letters, tb_codes the letters' codes.
+
+// The segment [o, seg1) of the tile that ends at t1: it lies in row r of the rows given, whose elements are [r_lo, r_hi).
+struct TbSegment {
+    int64_t r, r_lo, r_hi, seg1;
+};
+__device__ __forceinline__ TbSegment tb_segment(const int64_t BX_GLOBAL *g_off, int64_t n_rows, int64_t row_base, int width, int64_t o, int64_t t1)
+{
+    TbSegment s;
+    if (g_off) {
+        s.r = sa_row_of(g_off, n_rows, o);
+        s.r_lo = g_off[s.r];
+        s.r_hi = g_off[s.r + 1];
+    } else {
+        const int64_t row = o / width;
+        s.r = row - row_base;
+        s.r_lo = row * width;
+        s.r_hi = s.r_lo + width;
+    }
+    s.seg1 = s.r_hi < t1 ? s.r_hi : t1;
+    if (s.seg1 <= o) s.seg1 = o + 1;  // (offsets that are not what they should be: the walk still ends)
+    return s;
+}
+
+// The track of a row that names track `t` and starts at `start`, and of the `want` positions from p0, the position of element o,
+// those that are letters: [c0, c1), inside the sequence and before the position of element r_end -- the row's end r_hi for a caller
+// whose `want` holds a halo, seg1 for one that wants the segment alone.  A row that names no track gets the spare entry behind the
+// table, of size 0: c0 >= c1.
+struct TbLetters {
+    TbTrack tr;
+    int64_t p0, c0, c1;
+};
+__device__ __forceinline__ TbLetters tb_letters(const TbTrack *table, int n_tracks, int t, int start, int64_t r_lo, int64_t r_end, int64_t o, int64_t want)
+{
+    const bool named = t >= 0 && t < n_tracks;
+    TbLetters s{table[named ? t : n_tracks], 0, 0, 0};
+    s.p0 = (int64_t)start + (o - r_lo);
+    s.c1 = s.p0 + want;
+    if (s.c1 > (int64_t)start + (r_end - r_lo)) s.c1 = (int64_t)start + (r_end - r_lo);
+    if (s.c1 > s.tr.size) s.c1 = s.tr.size;
+    s.c0 = s.p0 > 0 ? s.p0 : 0;
+    return s;
+}
+
+// A bit per position of this thread's letters [pf, pf + cnt) that an N block covers, and one that a mask block covers (0 without
+// do_mask), of the letters [c0, c1), c0 < c1, of a segment.  Per list two searches find the run of blocks that meets [c0, c1); the run
+// goes through l_st / l_en TB_CHUNK blocks at a time, between two barriers.  So EVERY thread of the workgroup of THREADS calls this,
+// and with the same tr, do_mask, c0 and c1 -- a thread without letters (cnt == 0) too; the callers skip the call where a segment has
+// no letter (c0 >= c1), which is the same for the whole workgroup.  A list that does not meet [c0, c1) takes no barrier.
+struct TbBits {
+    unsigned is_n, is_m;
+};
+template <int THREADS>
+__device__ __forceinline__ TbBits tb_block_bits(const TbTrack &tr, int do_mask, int64_t c0, int64_t c1, int pf, int cnt, int tid, int32_t *l_st, int32_t *l_en)
+{
+    TbBits s{0, 0};
+    for (int list = 0; list < (do_mask ? 2 : 1); list++) {
+        const int64_t blocks = list ? tr.m_blocks : tr.n_blocks;
+        if (blocks == 0) continue;
+        const int32_t BX_GLOBAL *b_st = as_global(list ? tr.m_start : tr.n_start), *b_en = as_global(list ? tr.m_end : tr.n_end);
+        const int64_t lo = sm_first_above(b_en, 0, blocks, (int)c0);        // the first block that ends after the letters start
+        const int64_t hi = sm_first_above(b_st, lo, blocks, (int)(c1 - 1));  // the first that starts at or after their end
+        unsigned bits = 0;
+        for (int64_t at = lo; at < hi; at += TB_CHUNK) {
+            const int staged = hi - at < TB_CHUNK ? (int)(hi - at) : TB_CHUNK;
+            __syncthreads();  // the previous chunk has been searched
+            for (int k = tid; k < staged; k += THREADS) {
+                l_st[k] = b_st[at + k];
+                l_en[k] = b_en[at + k];
+            }
+            __syncthreads();
+            if (cnt) bits |= tb_covered(l_st, l_en, staged, pf, cnt);
+        }
+        if (list) s.is_m = bits;
+        else s.is_n = bits;
+    }
+    return s;
+}
+
+// The codes of letters [pf, pf + cnt), cnt <= 17, from at most two words: letter pf + i at bits 63 - 2 (b + i) .. 62 - 2 (b + i),
+// b = pf & 15, which tb_code takes out.  Nothing is read for cnt == 0.
+__device__ __forceinline__ uint64_t tb_codes(const TbTrack &tr, int pf, int cnt)
+{
+    if (cnt == 0) return 0;
+    const uint32_t BX_GLOBAL *packed = as_global(tr.packed);
+    const int64_t w = pf >> 4;
+    uint64_t codes = (uint64_t)tb_word(packed, w) << 32;
+    if (((pf + cnt - 1) >> 4) > w) codes |= tb_word(packed, w + 1);
+    return codes;
+}
+__device__ __forceinline__ unsigned tb_code(uint64_t codes, int at) { return (unsigned)(codes >> (62 - 2 * at)) & 3u; }
+
 // track_of, start: rows [row_base, row_base + n_rows) of the batch; row_off (ragged; else nullptr and `width` >= 1): the n_rows + 1
 // offsets of those rows, absolute.  The launch covers output bytes [o_first, o_first + count), TB_TILE per workgroup.
 __global__ __launch_bounds__(TB_THREADS) void tb_bases_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
@@ -202,24 +302,10 @@ __global__ __launch_bounds__(TB_THREADS) void tb_bases_kernel(const TbTrack *__r
     const uint32_t pad4 = (uint32_t)(pad & 0xFF) * 0x01010101u;
     uint32_t v[4] = {pad4, pad4, pad4, pad4};
     for (int64_t o = t0; o < t1;) {  // the segment [o, seg1) of row r, whose bytes are [r_lo, r_hi)
-        int64_t r, r_lo, r_hi;
-        if (row_off) {
-            r = sa_row_of(g_off, n_rows, o);
-            r_lo = g_off[r];
-            r_hi = g_off[r + 1];
-        } else {
-            const int64_t row = o / width;
-            r = row - row_base;
-            r_lo = row * width;
-            r_hi = r_lo + width;
-        }
-        int64_t seg1 = r_hi < t1 ? r_hi : t1;
-        if (seg1 <= o) seg1 = o + 1;  // (offsets that are not what they should be: the walk still ends)
-        const int t = g_track[r];
-        const bool named = t >= 0 && t < n_tracks;
-        const TbTrack tr = table[named ? t : n_tracks];  // (the spare entry: size 0)
-        const int64_t p0 = (int64_t)g_start[r] + (o - r_lo), p1 = p0 + (seg1 - o);  // the segment's positions
-        const int64_t c0 = p0 > 0 ? p0 : 0, c1 = p1 < tr.size ? p1 : tr.size;      // those inside the sequence
+        const TbSegment sg = tb_segment(g_off, n_rows, row_base, width, o, t1);
+        const int64_t seg1 = sg.seg1;
+        const TbLetters lt = tb_letters(table, n_tracks, g_track[sg.r], g_start[sg.r], sg.r_lo, seg1, o, seg1 - o);  // the segment's positions
+        const int64_t p0 = lt.p0, c0 = lt.c0, c1 = lt.c1;
         if (c0 < c1) {
             // this thread's bytes that are bases of the segment: [lo_el, hi_el), positions [pf, pf + cnt), bits [qa, qa + cnt) of 16
             int64_t lo_el = e0 > o ? e0 : o, hi_el = e0 + 16 < seg1 ? e0 + 16 : seg1;
@@ -227,42 +313,15 @@ __global__ __launch_bounds__(TB_THREADS) void tb_bases_kernel(const TbTrack *__r
             if (hi_el > o + (c1 - p0)) hi_el = o + (c1 - p0);
             const int cnt = lo_el < hi_el ? (int)(hi_el - lo_el) : 0;
             const int qa = cnt ? (int)(lo_el - e0) : 0, pf = cnt ? (int)(p0 + (lo_el - o)) : 0;
-            uint64_t codes = 0;  // base pf + i at bits 63 - 2 (b + i) .. 62 - 2 (b + i), b = pf & 15
-            if (cnt) {
-                const uint32_t BX_GLOBAL *packed = as_global(tr.packed);
-                const int64_t w = pf >> 4;
-                codes = (uint64_t)tb_word(packed, w) << 32;
-                if (((pf + cnt - 1) >> 4) > w) codes |= tb_word(packed, w + 1);
-            }
-            unsigned is_n = 0, is_m = 0;
-            for (int list = 0; list < (do_mask ? 2 : 1); list++) {
-                const int64_t blocks = list ? tr.m_blocks : tr.n_blocks;
-                if (blocks == 0) continue;
-                const int32_t BX_GLOBAL *b_st = as_global(list ? tr.m_start : tr.n_start), *b_en = as_global(list ? tr.m_end : tr.n_end);
-                const int64_t lo = sm_first_above(b_en, 0, blocks, (int)c0);        // the first block that ends after the segment starts
-                const int64_t hi = sm_first_above(b_st, lo, blocks, (int)(c1 - 1));  // the first that starts at or after its end
-                unsigned bits = 0;
-                for (int64_t at = lo; at < hi; at += TB_CHUNK) {
-                    const int staged = hi - at < TB_CHUNK ? (int)(hi - at) : TB_CHUNK;
-                    __syncthreads();  // the previous chunk has been searched
-                    for (int k = tid; k < staged; k += TB_THREADS) {
-                        l_st[k] = b_st[at + k];
-                        l_en[k] = b_en[at + k];
-                    }
-                    __syncthreads();
-                    if (cnt) bits |= tb_covered(l_st, l_en, staged, pf, cnt);
-                }
-                if (list) is_m = bits;
-                else is_n = bits;
-            }
+            const uint64_t codes = tb_codes(lt.tr, pf, cnt);
+            const TbBits bits = tb_block_bits<TB_THREADS>(lt.tr, do_mask, c0, c1, pf, cnt, tid, l_st, l_en);
             const int b = pf & 15;
 #pragma unroll
             for (int q = 0; q < 16; q++) {
                 const int i = q - qa;  // the base's place among this thread's
                 if (i < 0 || i >= cnt) continue;
-                const unsigned code = (unsigned)(codes >> (62 - 2 * (b + i))) & 3u;
-                unsigned letter = (is_n >> i) & 1u ? (unsigned)'N' : (TB_LETTERS >> (8 * code)) & 0xFFu;
-                if ((is_m >> i) & 1u) letter |= 0x20u;
+                unsigned letter = (bits.is_n >> i) & 1u ? (unsigned)'N' : (TB_LETTERS >> (8 * tb_code(codes, b + i))) & 0xFFu;
+                if ((bits.is_m >> i) & 1u) letter |= 0x20u;
                 v[q >> 2] = (v[q >> 2] & ~(0xFFu << (8 * (q & 3)))) | (letter << (8 * (q & 3)));
             }
         }

@@ -18,20 +18,9 @@
 //        outnumber cap
 #include "kernel_host.hpp"
 
-#include <cstdlib>
-#include <cstring>
-
-// what the kernels use that kernel_host.hpp lacks
-struct int4 {
-    int x, y, z, w;
-};
-static int4 load_int4(const int32_t *p) { return int4{p[0], p[1], p[2], p[3]}; }
-static void store_int4(int32_t *p, int a, int b, int c, int d) { p[0] = a, p[1] = b, p[2] = c, p[3] = d; }
-static Dim gridDim;
-// TB_WAVE_SUM4 and PW_WAVE_MAX64 are not run here.  PH_WAVE_PREFIX for a workgroup of host threads: everyone leaves its value,
-// meets at the barrier, sums its wave's lanes up to itself, meets again
-static void host_wave_sum4(int v[4]) { (void)v; abort(); }
-#define TB_WAVE_SUM4(v) host_wave_sum4(v)
+#include "twobit_host.hpp"
+// PW_WAVE_MAX64 is not run here.  PH_WAVE_PREFIX for a workgroup of host threads: everyone leaves its value, meets at the barrier,
+// sums its wave's lanes up to itself, meets again
 static unsigned long long host_wave_max64(unsigned long long key) { (void)key; abort(); }
 #define PW_WAVE_MAX64(key) host_wave_max64(key)
 #define PW_ATOMIC_MAX64(at, key) abort()
@@ -48,43 +37,6 @@ static int host_wave_prefix(int v)
 #define PH_WAVE_PREFIX(v) host_wave_prefix(v)
 #include "pwm_hits.hpp"
 using namespace bxmi;
-
-constexpr size_t GUARD = 64;
-constexpr uint32_t GUARD_BITS = 0xEEEEEEEEu;
-
-struct Track {
-    int64_t size = 0, n_blocks = 0, m_blocks = 0;
-    std::vector<uint32_t> packed;
-    std::vector<int32_t> n_start, n_end, m_start, m_end;
-};
-
-static bool read_track(FILE *f, Track &t)
-{
-    std::vector<int64_t> head;
-    std::vector<uint8_t> bytes;
-    std::vector<int32_t> n_size, m_size;
-    if (!read_n(f, head, 3)) return false;
-    t.size = head[0], t.n_blocks = head[1], t.m_blocks = head[2];
-    if (!read_n(f, bytes, (size_t)(t.size + 3) / 4) || !read_n(f, t.n_start, t.n_blocks) || !read_n(f, n_size, t.n_blocks) ||
-        !read_n(f, t.m_start, t.m_blocks) || !read_n(f, m_size, t.m_blocks))
-        return false;
-    t.packed.assign((bytes.size() + 3) / 4, 0u);  // whole words, the rest of the last one zero
-    if (!bytes.empty()) memcpy(t.packed.data(), bytes.data(), bytes.size());
-    t.n_end.resize(t.n_start.size());
-    t.m_end.resize(t.m_start.size());
-    for (size_t i = 0; i < t.n_start.size(); i++) t.n_end[i] = t.n_start[i] + n_size[i];
-    for (size_t i = 0; i < t.m_start.size(); i++) t.m_end[i] = t.m_start[i] + m_size[i];
-    return true;
-}
-
-// [GUARD][cells][GUARD] of 32-bit words, the allocation ending where the second band ends
-struct Banded {
-    std::vector<uint32_t> raw;
-    size_t cells;
-    explicit Banded(size_t cells_) : raw(2 * GUARD + cells_, GUARD_BITS), cells(cells_) {}
-    uint32_t *body() { return raw.data() + GUARD; }
-    bool write(FILE *f) { return fwrite(raw.data(), 4, raw.size(), f) == raw.size(); }
-};
 
 int main(int argc, char **argv)
 {
