@@ -118,6 +118,12 @@ _SIGNATURES = {
     "bxmi_twobit_kmer_counts": [vp, i32, vp, vp, i64, i32, vp, i64, C.c_int, C.c_int, C.c_int, vp, vp],
     "bxmi_twobit_kmer_counts_dev": [vp, i32, vp, vp, i64, i32, vp, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp],
     "bxmi_twobit_kmer_force": [C.c_int],
+    "bxmi_twobit_bases_strand": [vp, i32, vp, vp, vp, i64, i32, vp, i64, C.c_int, C.c_int, vp],
+    "bxmi_twobit_bases_strand_dev": [vp, i32, vp, vp, vp, i64, i32, vp, i64, C.c_int, C.c_int, vp, vp],
+    "bxmi_twobit_composition_strand": [vp, i32, vp, vp, vp, vp, i64, C.c_int, vp],
+    "bxmi_twobit_composition_strand_dev": [vp, i32, vp, vp, vp, vp, i64, C.c_int, vp, vp],
+    "bxmi_twobit_kmer_counts_strand": [vp, i32, vp, vp, vp, i64, i32, vp, i64, C.c_int, C.c_int, C.c_int, vp, vp],
+    "bxmi_twobit_kmer_counts_strand_dev": [vp, i32, vp, vp, vp, i64, i32, vp, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp],
     "bxmi_bits_create": [i64, i64, _p(vp)],
     "bxmi_bits_destroy": [vp],
     "bxmi_bits_info": [vp, _p(i32), _p(i32), _p(i32)],

@@ -15,18 +15,24 @@ the digit of upper case, as ``bx.seqmapping.DNA`` does.  Every window of a regio
 window early (ngramcount.pyx:71), and ``drop_last=True`` reproduces that by shortening every region by one base.  The work is
 integer: the counts are the reference's bit for bit.  The ``_dev`` forms take and return torch tensors on the caller's stream.
 
-``index_of`` / ``word_of`` / ``words`` name the columns; ``fold_reverse_complement`` collapses the two strands.
+``strands`` (None: all plus; given as for ``bxmi.sequence``) counts the minus regions over their reverse complement, the string
+``sequence.strings(..., strands=...)`` gives: the digits of the complemented letters in reverse order, under ANY alphabet.  With
+``drop_last`` the last window of the STRAND's string is dropped, so a minus region is shortened at its start.
+
+``index_of`` / ``word_of`` / ``words`` name the columns; ``fold_reverse_complement`` collapses the two strands;
+``strand_columns`` gives, for an alphabet closed under complement, the column of every column's reverse-complement word.
 """
 import numpy as np
 
 from . import _ffi
 from ._ffi import as_i32, call, ptr
-from .sequence import _clip, _clip_dev, _record
+from .sequence import _clip, _clip_dev, _record, _strands, _strands_dev
 from .summary import _rows_i32
 
 BINS_MAX = 16384          # KM_BINS_MAX of csrc/kmer.hpp
 LETTERS = "TCAGtcag"      # the eight letters that can have a digit, in the order of the digits table: 4 * lower_case + code
 _COMPLEMENT = {"A": "T", "C": "G", "G": "C", "T": "A"}
+_COMPLEMENT.update({a.lower(): b.lower() for a, b in list(_COMPLEMENT.items())})
 
 
 def _letter_digits(alphabet):
@@ -135,6 +141,31 @@ def reverse_complement_columns(k, alphabet="ACGT"):
     return out
 
 
+def strand_columns(k, alphabet="ACGT", case_sensitive=True):
+    """int64 [radix ** k]: w -> index_of(reverse_complement(word_of(w))), for an alphabet closed under complement -- the
+    complements of the letters of one digit all have one digit, and every digit is some letter's.  Then the counts of the minus
+    strand are a gather of the plus strand's: minus[:, strand_columns(k)[w]] == plus[:, w], that is, minus == plus[:, rc] with rc
+    its own inverse.  An alphabet that is not closed (a letter whose complement has no digit, or another one than its digit-mates')
+    is a ValueError: no permutation of the columns gives its minus counts."""
+    digits, radix = digits_of(alphabet, case_sensitive)
+    comp = {}
+    for ch, d in zip(LETTERS, digits.tolist()):
+        if d < 0:
+            continue
+        c = int(digits[LETTERS.index(_COMPLEMENT[ch])])
+        if c < 0 or comp.setdefault(d, c) != c:
+            raise ValueError("the alphabet is not closed under complement at %r" % ch)
+    if sorted(comp) != list(range(radix)):
+        raise ValueError("no letter of this alphabet has digit %d" % min(set(range(radix)) - set(comp)))
+    table = np.array([comp[d] for d in range(radix)], dtype=np.int64)
+    k = int(k)
+    index = np.arange(bins_of(k, radix), dtype=np.int64)
+    out = np.zeros_like(index)
+    for t in range(k):  # letter t of the word becomes letter k - 1 - t of its reverse complement
+        out += table[(index // radix ** t) % radix] * radix ** (k - 1 - t)
+    return out
+
+
 def canonical_columns(k, alphabet="ACGT"):
     """the columns `fold_reverse_complement` keeps: those not above their reverse complement's"""
     rc = reverse_complement_columns(k, alphabet)
@@ -171,7 +202,7 @@ def _offsets(lengths, drop_last):
     return offsets
 
 
-def counts(tracks, track_of, starts, ends, k, alphabet="ACGT", case_sensitive=True, do_mask=True, drop_last=False):
+def counts(tracks, track_of, starts, ends, k, alphabet="ACGT", case_sensitive=True, do_mask=True, drop_last=False, strands=None):
     """The words of regions [starts[i], ends[i]) of tracks[track_of[i]], clipped as `sequence.sequences` clips them -> int32
     [n, radix ** k].  An empty region, one shorter than k, or one on an unknown sequence gives zeros.  With drop_last every region
     loses its last base first: then row i equals the reference's count_ngrams(mapping.translate(seq.get(start, end)), k, radix)."""
@@ -183,12 +214,19 @@ def counts(tracks, track_of, starts, ends, k, alphabet="ACGT", case_sensitive=Tr
     s64, lengths = _clip([tr.size for tr in tracks], t, s, e)
     offsets = _offsets(lengths, drop_last)
     out = np.empty((len(t), bins), dtype=np.int32)
-    call("bxmi_twobit_kmer_counts", _ffi.handles(tracks), len(tracks), ptr(t), ptr(as_i32(s64)), len(t), 0, ptr(offsets), int(offsets[-1]),
-         int(bool(do_mask)), int(k), radix, ptr(digits), ptr(out))
+    strand = _strands(strands, len(t))
+    if strand is None:
+        call("bxmi_twobit_kmer_counts", _ffi.handles(tracks), len(tracks), ptr(t), ptr(as_i32(s64)), len(t), 0, ptr(offsets), int(offsets[-1]),
+             int(bool(do_mask)), int(k), radix, ptr(digits), ptr(out))
+        return out
+    if drop_last:  # the last window of a minus region's string lies at the region's start
+        s64 = s64 + ((strand != 0) & (lengths > 0))
+    call("bxmi_twobit_kmer_counts_strand", _ffi.handles(tracks), len(tracks), ptr(t), ptr(as_i32(s64)), ptr(strand), len(t), 0, ptr(offsets),
+         int(offsets[-1]), int(bool(do_mask)), int(k), radix, ptr(digits), ptr(out))
     return out
 
 
-def count_matrix(tracks, track_of, starts, width, k, alphabet="ACGT", case_sensitive=True, do_mask=True, drop_last=False):
+def count_matrix(tracks, track_of, starts, width, k, alphabet="ACGT", case_sensitive=True, do_mask=True, drop_last=False, strands=None):
     """The words of windows [starts[i], starts[i] + width) of tracks[track_of[i]] -> int32 [n, radix ** k]; a position outside the
     sequence has no digit, as has every position of a row that names no track.  width < 1 raises BxmiError (EINVAL)."""
     _ffi.require_gpu()
@@ -197,12 +235,20 @@ def count_matrix(tracks, track_of, starts, width, k, alphabet="ACGT", case_sensi
     digits, radix = digits_of(alphabet, case_sensitive)
     bins = bins_of(k, radix)
     width = int(width)
+    strand = _strands(strands, len(t))
     if drop_last and width == 1:  # (nothing is left of a window of one base)
         return np.zeros((len(t), bins), dtype=np.int32)
-    width -= 1 if drop_last and width > 1 else 0
+    shorter = drop_last and width > 1
+    width -= 1 if shorter else 0
     out = np.empty((len(t), bins), dtype=np.int32)
-    call("bxmi_twobit_kmer_counts", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), len(t), width, None, len(t) * max(width, 0), int(bool(do_mask)),
-         int(k), radix, ptr(digits), ptr(out))
+    if strand is None:
+        call("bxmi_twobit_kmer_counts", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), len(t), width, None, len(t) * max(width, 0),
+             int(bool(do_mask)), int(k), radix, ptr(digits), ptr(out))
+        return out
+    if shorter:  # the last window of a minus row's string lies at the window's start
+        s = as_i32(s.astype(np.int64) + (strand != 0))
+    call("bxmi_twobit_kmer_counts_strand", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), ptr(strand), len(t), width, None, len(t) * max(width, 0),
+         int(bool(do_mask)), int(k), radix, ptr(digits), ptr(out))
     return out
 
 
@@ -218,7 +264,8 @@ def _out_dev(out, n, bins, dev):
     return out, ()
 
 
-def counts_dev(tracks, track_of, starts, ends, k, alphabet="ACGT", case_sensitive=True, do_mask=True, drop_last=False, stream=None, out=None):
+def counts_dev(tracks, track_of, starts, ends, k, alphabet="ACGT", case_sensitive=True, do_mask=True, drop_last=False, stream=None, out=None,
+               strands=None):
     """`counts` on device arrays: int32 torch tensors on the GPU in, the int32 [n, radix ** k] tensor out -- `out` if given
     (contiguous, on the rows' device), else a new one -- queued on torch's current stream (or `stream`).  The clipping and the
     offsets are torch's, on its current stream, and the host waits for NOTHING and reads nothing back: the kernel reads where the
@@ -232,20 +279,29 @@ def counts_dev(tracks, track_of, starts, ends, k, alphabet="ACGT", case_sensitiv
     digits, radix = digits_of(alphabet, case_sensitive)
     bins = bins_of(k, radix)
     first, offsets = _clip_dev(tracks, track_of, starts, ends, n, dev)
+    strand = _strands_dev(strands, n, dev, "counts_dev")
     if drop_last and n:
+        if strand is not None:  # the last window of a minus region's string lies at the region's start
+            first = first + ((strand != 0) & (offsets[1:] > offsets[:-1])).to(first.dtype)
         torch.cumsum((offsets[1:] - offsets[:-1] - 1).clamp_(min=0), 0, out=offsets[1:])
     if stream != torch.cuda.current_stream(dev).cuda_stream:  # the kernel reads what torch's current stream is still writing
         torch.cuda.ExternalStream(stream, device=dev).wait_stream(torch.cuda.current_stream(dev))
     out, made = _out_dev(out, n, bins, dev)
     bound = n * max([tr.size for tr in tracks] + [0])
-    call("bxmi_twobit_kmer_counts_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), first.data_ptr(), n, 0, offsets.data_ptr(), bound,
-         int(bool(do_mask)), int(k), radix, ptr(digits), out.data_ptr(), stream)
+    if strand is None:
+        call("bxmi_twobit_kmer_counts_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), first.data_ptr(), n, 0, offsets.data_ptr(), bound,
+             int(bool(do_mask)), int(k), radix, ptr(digits), out.data_ptr(), stream)
+    else:
+        call("bxmi_twobit_kmer_counts_strand_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), first.data_ptr(), strand.data_ptr(), n, 0,
+             offsets.data_ptr(), bound, int(bool(do_mask)), int(k), radix, ptr(digits), out.data_ptr(), stream)
+        made = made + ((strand,) if strand is not strands else ())
     if n:
         _record(stream, dev, (first, offsets) + made)
     return out
 
 
-def count_matrix_dev(tracks, track_of, starts, width, k, alphabet="ACGT", case_sensitive=True, do_mask=True, drop_last=False, stream=None, out=None):
+def count_matrix_dev(tracks, track_of, starts, width, k, alphabet="ACGT", case_sensitive=True, do_mask=True, drop_last=False, stream=None, out=None,
+                     strands=None):
     """`count_matrix` on device arrays: the int32 [n, radix ** k] tensor (`out` if given), queued on torch's current stream (or
     `stream`), nothing is waited for."""
     tracks = list(tracks)
@@ -254,11 +310,25 @@ def count_matrix_dev(tracks, track_of, starts, width, k, alphabet="ACGT", case_s
     bins = bins_of(k, radix)
     width = int(width)
     out, made = _out_dev(out, n, bins, dev)
+    strand = _strands_dev(strands, n, dev, "count_matrix_dev")
     if drop_last and width == 1:
         return out.zero_()
-    width -= 1 if drop_last and width > 1 else 0
-    call("bxmi_twobit_kmer_counts_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), n, width, None, n * max(width, 0),
-         int(bool(do_mask)), int(k), radix, ptr(digits), out.data_ptr(), stream)
+    shorter = drop_last and width > 1
+    width -= 1 if shorter else 0
+    if strand is None:
+        call("bxmi_twobit_kmer_counts_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), n, width, None, n * max(width, 0),
+             int(bool(do_mask)), int(k), radix, ptr(digits), out.data_ptr(), stream)
+    else:
+        if shorter:  # the last window of a minus row's string lies at the window's start (torch's current stream, as counts_dev's offsets)
+            import torch
+
+            starts = starts + (strand != 0).to(starts.dtype)
+            made = made + (starts,)
+            if stream != torch.cuda.current_stream(dev).cuda_stream:
+                torch.cuda.ExternalStream(stream, device=dev).wait_stream(torch.cuda.current_stream(dev))
+        call("bxmi_twobit_kmer_counts_strand_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), strand.data_ptr(), n, width,
+             None, n * max(width, 0), int(bool(do_mask)), int(k), radix, ptr(digits), out.data_ptr(), stream)
+        made = made + ((strand,) if strand is not strands else ())
     if made and n:
         _record(stream, dev, made)
     return out

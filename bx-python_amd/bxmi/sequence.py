@@ -10,6 +10,12 @@ A, C, G, T, N, masked of every row at a cost that does not depend on the row's l
 tensors on the caller's stream; the matrix stays on the device, where a lookup on the byte tensor gives codes or one-hot planes.
 Everything is integer work: the outputs are the reference's byte for byte.
 
+``strands`` (every function and method here; None: all plus) gives the minus rows as their reverse complement, the reference's
+``SeqFile.reverse_complement`` (lib/bx/seq/seq.py:108-109: ``text.translate(DNA_COMP)[::-1]``): the letters reversed and
+complemented with the case kept and N left N, the pad of ``matrix`` mirrored with them and never complemented; the base counts with
+A and T, C and G exchanged.  The host forms take a sequence of "+" / "-", bools or 0 / 1, the ``_dev`` forms an int8, uint8 or bool
+tensor on the device (any non-zero entry is minus; nothing is read back).
+
 Only files whose blocks are sorted, non-empty, disjoint and inside the sequence are accepted -- every real file; for those the
 reference's walk over the blocks is plain coverage.  Anything else raises BxmiError (EINVAL) naming the condition.
 """
@@ -57,6 +63,42 @@ def _pad_byte(pad):
     return int(pad)
 
 
+def _strands(strands, n):
+    """None, or int8 [n] of 0 (plus) and 1 (minus) from a sequence of "+" / "-", bools or 0 / 1; anything else is a ValueError"""
+    if strands is None:
+        return None
+    given = strands.tolist() if isinstance(strands, np.ndarray) else list(strands)
+    if len(given) != n:
+        raise ValueError("strands must have one entry per row: %d for %d rows" % (len(given), n))
+    out = np.zeros(n, dtype=np.int8)
+    for i, v in enumerate(given):
+        if isinstance(v, (bytes, np.bytes_)):
+            v = v.decode("ascii", "replace")
+        if isinstance(v, str):
+            if v not in ("+", "-"):
+                raise ValueError("strands[%d] = %r is neither '+' nor '-'" % (i, v))
+            out[i] = v == "-"
+        elif isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and v in (0, 1)):
+            out[i] = int(v)
+        else:
+            raise ValueError("strands[%d] = %r is none of '+', '-', a bool, 0 or 1" % (i, v))
+    return out
+
+
+def _strands_dev(strands, n, dev, who):
+    """None, or the int8 view / copy of an int8, uint8 or bool tensor [n] on `dev` (nothing is read back: any non-zero entry is minus)"""
+    if strands is None:
+        return None
+    import torch
+
+    if not isinstance(strands, torch.Tensor) or strands.dtype not in (torch.int8, torch.uint8, torch.bool):
+        raise ValueError("%s: strands must be an int8, uint8 or bool tensor on the device" % who)
+    if strands.device != dev or tuple(strands.shape) != (n,):
+        raise ValueError("%s: strands must be a tensor of %d entries on the device of the rows" % (who, n))
+    strands = strands.contiguous()
+    return strands.view(torch.int8) if strands.dtype != torch.int8 else strands
+
+
 def _clip(sizes, track_of, s, e):
     """the rows as TwoBitSequence.get clips them (twobit.py:44-51): start below 0 is 0, end beyond the size is the size; a row the
     reference refuses ("end before start") or whose sequence is unknown is empty -> (starts, lengths) int64.  A track_of beyond
@@ -68,7 +110,7 @@ def _clip(sizes, track_of, s, e):
     return first, np.maximum(np.minimum(e.astype(np.int64), size) - first, 0)
 
 
-def sequences(tracks, track_of, starts, ends, do_mask=True):
+def sequences(tracks, track_of, starts, ends, do_mask=True, strands=None):
     """The letters of regions [starts[i], ends[i]) of tracks[track_of[i]], clipped as TwoBitSequence.get clips them -> (bytes
     uint8[total], offsets int64[n + 1]): row i is bytes[offsets[i]:offsets[i + 1]].  Where the reference raises "end before start"
     the row is empty; track_of[i] < 0 (unknown name) gives an empty row.  One device pass over the OUTPUT."""
@@ -79,19 +121,24 @@ def sequences(tracks, track_of, starts, ends, do_mask=True):
     offsets = np.zeros(len(s) + 1, dtype=np.int64)
     np.cumsum(lengths, out=offsets[1:])
     out = np.empty(int(offsets[-1]), dtype=np.uint8)
-    call("bxmi_twobit_bases", _ffi.handles(tracks), len(tracks), ptr(t), ptr(as_i32(s64)), len(t), 0, ptr(offsets), len(out), int(bool(do_mask)), ord("N"),
-         ptr(out))
+    strand = _strands(strands, len(t))
+    if strand is None:
+        call("bxmi_twobit_bases", _ffi.handles(tracks), len(tracks), ptr(t), ptr(as_i32(s64)), len(t), 0, ptr(offsets), len(out), int(bool(do_mask)),
+             ord("N"), ptr(out))
+    else:  # (a minus row: the reverse complement of the clipped region)
+        call("bxmi_twobit_bases_strand", _ffi.handles(tracks), len(tracks), ptr(t), ptr(as_i32(s64)), ptr(strand), len(t), 0, ptr(offsets), len(out),
+             int(bool(do_mask)), ord("N"), ptr(out))
     return out, offsets
 
 
-def strings(tracks, track_of, starts, ends, do_mask=True):
+def strings(tracks, track_of, starts, ends, do_mask=True, strands=None):
     """`sequences` as a list of str"""
-    data, offsets = sequences(tracks, track_of, starts, ends, do_mask)
+    data, offsets = sequences(tracks, track_of, starts, ends, do_mask, strands)
     text = data.tobytes().decode("ascii")
     return [text[a:b] for a, b in zip(offsets[:-1].tolist(), offsets[1:].tolist())]
 
 
-def matrix(tracks, track_of, starts, width, pad=b"N", do_mask=True):
+def matrix(tracks, track_of, starts, width, pad=b"N", do_mask=True, strands=None):
     """The windows [starts[i], starts[i] + width) of tracks[track_of[i]] -> uint8 [n, width] of letters, the byte `pad` where a
     position is outside the sequence or the row names no track.  width < 1 raises BxmiError (EINVAL)."""
     _ffi.require_gpu()
@@ -99,11 +146,17 @@ def matrix(tracks, track_of, starts, width, pad=b"N", do_mask=True):
     t, s = _rows_i32("track_of and starts", track_of, starts)
     width = int(width)
     out = np.empty((len(t), max(width, 0)), dtype=np.uint8)
-    call("bxmi_twobit_bases", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), len(t), width, None, out.size, int(bool(do_mask)), _pad_byte(pad), ptr(out))
+    strand = _strands(strands, len(t))
+    if strand is None:
+        call("bxmi_twobit_bases", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), len(t), width, None, out.size, int(bool(do_mask)), _pad_byte(pad),
+             ptr(out))
+    else:
+        call("bxmi_twobit_bases_strand", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), ptr(strand), len(t), width, None, out.size, int(bool(do_mask)),
+             _pad_byte(pad), ptr(out))
     return out
 
 
-def composition(tracks, track_of, starts, ends, do_mask=True):
+def composition(tracks, track_of, starts, ends, do_mask=True, strands=None):
     """int32 [n, 6] = A, C, G, T, N, masked of [starts[i], ends[i]) clipped to the sequence: what counting the characters of the
     reference's string gives (case folded for the first five, the lower-case ones for the sixth; masked is 0 without do_mask).  An
     unknown sequence or an empty row gives zeros.  A row's cost does not depend on its length."""
@@ -111,11 +164,15 @@ def composition(tracks, track_of, starts, ends, do_mask=True):
     tracks = list(tracks)
     t, s, e = _rows_i32("track_of, starts and ends", track_of, starts, ends)
     out = np.zeros((len(t), 6), dtype=np.int32)
-    call("bxmi_twobit_composition", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), ptr(e), len(t), int(bool(do_mask)), ptr(out))
+    strand = _strands(strands, len(t))
+    if strand is None:
+        call("bxmi_twobit_composition", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), ptr(e), len(t), int(bool(do_mask)), ptr(out))
+    else:
+        call("bxmi_twobit_composition_strand", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), ptr(strand), ptr(e), len(t), int(bool(do_mask)), ptr(out))
     return out
 
 
-def matrix_dev(tracks, track_of, starts, width, pad=b"N", do_mask=True, stream=None, out=None):
+def matrix_dev(tracks, track_of, starts, width, pad=b"N", do_mask=True, stream=None, out=None, strands=None):
     """`matrix` on device arrays: int32 torch tensors on the GPU in, the uint8 [n, width] tensor out -- `out` if given (contiguous
     uint8 [n, width] on the same device; 16-byte aligned it is written by 16-byte stores, otherwise byte by byte, with the same
     result), else a new one.  Queued on torch's current stream (or `stream`), nothing is waited for.  A track_of outside
@@ -130,8 +187,15 @@ def matrix_dev(tracks, track_of, starts, width, pad=b"N", do_mask=True, stream=N
         out = torch.empty((n, max(width, 0)), dtype=torch.uint8, device=dev)
     elif out.dtype != torch.uint8 or tuple(out.shape) != (n, width) or not out.is_contiguous() or out.device != dev:
         raise ValueError("out must be a contiguous uint8 [n, width] tensor on the device of the rows")
-    call("bxmi_twobit_bases_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), n, width, None, out.numel(),
-         int(bool(do_mask)), _pad_byte(pad), out.data_ptr(), stream)
+    strand = _strands_dev(strands, n, dev, "matrix_dev")
+    if strand is None:
+        call("bxmi_twobit_bases_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), n, width, None, out.numel(),
+             int(bool(do_mask)), _pad_byte(pad), out.data_ptr(), stream)
+    else:
+        call("bxmi_twobit_bases_strand_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), strand.data_ptr(), n, width, None,
+             out.numel(), int(bool(do_mask)), _pad_byte(pad), out.data_ptr(), stream)
+        if n and strand is not strands:
+            _record(stream, dev, (strand,))
     return out
 
 
@@ -161,7 +225,7 @@ def _record(stream, dev, tensors):
             t.record_stream(used_on)
 
 
-def sequences_dev(tracks, track_of, starts, ends, do_mask=True, stream=None):
+def sequences_dev(tracks, track_of, starts, ends, do_mask=True, stream=None, strands=None):
     """`sequences` on device arrays: int32 torch tensors on the GPU in, (bytes uint8[total], offsets int64[n + 1]) tensors out.
     The clipping and the offsets are computed by torch on its current stream and `total` is read back to size the output -- ONE
     synchronisation; the letters are then queued on torch's current stream (or `stream`: the tensors made here are then recorded
@@ -173,14 +237,19 @@ def sequences_dev(tracks, track_of, starts, ends, do_mask=True, stream=None):
     first, offsets = _clip_dev(tracks, track_of, starts, ends, n, dev)
     total = int(offsets[-1].item()) if n else 0  # (the synchronisation: `first` and `offsets` are complete after it)
     out = torch.empty(total, dtype=torch.uint8, device=dev)
-    call("bxmi_twobit_bases_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), first.data_ptr(), n, 0, offsets.data_ptr(), total,
-         int(bool(do_mask)), ord("N"), out.data_ptr(), stream)
+    strand = _strands_dev(strands, n, dev, "sequences_dev")
+    if strand is None:
+        call("bxmi_twobit_bases_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), first.data_ptr(), n, 0, offsets.data_ptr(), total,
+             int(bool(do_mask)), ord("N"), out.data_ptr(), stream)
+    else:
+        call("bxmi_twobit_bases_strand_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), first.data_ptr(), strand.data_ptr(), n, 0,
+             offsets.data_ptr(), total, int(bool(do_mask)), ord("N"), out.data_ptr(), stream)
     if total:
-        _record(stream, dev, (first, offsets, out))
+        _record(stream, dev, (first, offsets, out) + ((strand,) if strand is not None and strand is not strands else ()))
     return out, offsets
 
 
-def composition_dev(tracks, track_of, starts, ends, do_mask=True, stream=None):
+def composition_dev(tracks, track_of, starts, ends, do_mask=True, stream=None, strands=None):
     """`composition` on device arrays: int32 torch tensors in, the int32 [n, 6] tensor out, queued on torch's current stream (or
     `stream`), nothing waited for.  One 2bit call at a time, as `matrix_dev`."""
     import torch
@@ -188,8 +257,15 @@ def composition_dev(tracks, track_of, starts, ends, do_mask=True, stream=None):
     tracks = list(tracks)
     (track_of, starts, ends), n, dev, stream = _ffi.device_args("composition_dev", "composition", ("track_of", "starts", "ends"), (track_of, starts, ends), stream)
     out = torch.zeros((n, 6), dtype=torch.int32, device=dev)
-    call("bxmi_twobit_composition_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), ends.data_ptr(), n, int(bool(do_mask)),
-         out.data_ptr(), stream)
+    strand = _strands_dev(strands, n, dev, "composition_dev")
+    if strand is None:
+        call("bxmi_twobit_composition_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), ends.data_ptr(), n,
+             int(bool(do_mask)), out.data_ptr(), stream)
+    else:
+        call("bxmi_twobit_composition_strand_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), strand.data_ptr(),
+             ends.data_ptr(), n, int(bool(do_mask)), out.data_ptr(), stream)
+        if n and strand is not strands:
+            _record(stream, dev, (strand,))
     return out
 
 
@@ -224,26 +300,26 @@ class TwoBitSet:
             raise ValueError("a sequence position beyond the file's %d sequences" % len(self.chroms))
         return track_of
 
-    def sequences(self, chroms, starts, ends):
-        return sequences(self.tracks.values(), self._track_of(chroms), starts, ends, self.do_mask)
+    def sequences(self, chroms, starts, ends, strands=None):
+        return sequences(self.tracks.values(), self._track_of(chroms), starts, ends, self.do_mask, strands)
 
-    def strings(self, chroms, starts, ends):
-        return strings(self.tracks.values(), self._track_of(chroms), starts, ends, self.do_mask)
+    def strings(self, chroms, starts, ends, strands=None):
+        return strings(self.tracks.values(), self._track_of(chroms), starts, ends, self.do_mask, strands)
 
-    def matrix(self, chroms, starts, width, pad=b"N"):
-        return matrix(self.tracks.values(), self._track_of(chroms), starts, width, pad, self.do_mask)
+    def matrix(self, chroms, starts, width, pad=b"N", strands=None):
+        return matrix(self.tracks.values(), self._track_of(chroms), starts, width, pad, self.do_mask, strands)
 
-    def composition(self, chroms, starts, ends):
-        return composition(self.tracks.values(), self._track_of(chroms), starts, ends, self.do_mask)
+    def composition(self, chroms, starts, ends, strands=None):
+        return composition(self.tracks.values(), self._track_of(chroms), starts, ends, self.do_mask, strands)
 
-    def matrix_dev(self, track_of, starts, width, pad=b"N", stream=None, out=None):
-        return matrix_dev(self.tracks.values(), track_of, starts, width, pad, self.do_mask, stream, out)
+    def matrix_dev(self, track_of, starts, width, pad=b"N", stream=None, out=None, strands=None):
+        return matrix_dev(self.tracks.values(), track_of, starts, width, pad, self.do_mask, stream, out, strands)
 
-    def sequences_dev(self, track_of, starts, ends, stream=None):
-        return sequences_dev(self.tracks.values(), track_of, starts, ends, self.do_mask, stream)
+    def sequences_dev(self, track_of, starts, ends, stream=None, strands=None):
+        return sequences_dev(self.tracks.values(), track_of, starts, ends, self.do_mask, stream, strands)
 
-    def composition_dev(self, track_of, starts, ends, stream=None):
-        return composition_dev(self.tracks.values(), track_of, starts, ends, self.do_mask, stream)
+    def composition_dev(self, track_of, starts, ends, stream=None, strands=None):
+        return composition_dev(self.tracks.values(), track_of, starts, ends, self.do_mask, stream, strands)
 
     # position weight matrices over the rows (bxmi.motif, which builds on this module); `pwms`: a motif.MatrixSet, for the host
     # forms also a list of motif.ScoringMatrix
@@ -288,22 +364,25 @@ class TwoBitSet:
         return motif.hits_dev(self.tracks.values(), track_of, starts, ends, pwms, thresholds, self.do_mask, max_hits, stream)
 
     # the k-mer spectrum of the rows (bxmi.kmers, which builds on this module)
-    def kmer_counts(self, chroms, starts, ends, k, alphabet="ACGT", case_sensitive=True, drop_last=False):
+    def kmer_counts(self, chroms, starts, ends, k, alphabet="ACGT", case_sensitive=True, drop_last=False, strands=None):
         from . import kmers
 
-        return kmers.counts(self.tracks.values(), self._track_of(chroms), starts, ends, k, alphabet, case_sensitive, self.do_mask, drop_last)
+        return kmers.counts(self.tracks.values(), self._track_of(chroms), starts, ends, k, alphabet, case_sensitive, self.do_mask, drop_last, strands)
 
-    def kmer_count_matrix(self, chroms, starts, width, k, alphabet="ACGT", case_sensitive=True, drop_last=False):
+    def kmer_count_matrix(self, chroms, starts, width, k, alphabet="ACGT", case_sensitive=True, drop_last=False, strands=None):
         from . import kmers
 
-        return kmers.count_matrix(self.tracks.values(), self._track_of(chroms), starts, width, k, alphabet, case_sensitive, self.do_mask, drop_last)
+        return kmers.count_matrix(self.tracks.values(), self._track_of(chroms), starts, width, k, alphabet, case_sensitive, self.do_mask, drop_last,
+                                  strands)
 
-    def kmer_counts_dev(self, track_of, starts, ends, k, alphabet="ACGT", case_sensitive=True, drop_last=False, stream=None, out=None):
+    def kmer_counts_dev(self, track_of, starts, ends, k, alphabet="ACGT", case_sensitive=True, drop_last=False, stream=None, out=None, strands=None):
         from . import kmers
 
-        return kmers.counts_dev(self.tracks.values(), track_of, starts, ends, k, alphabet, case_sensitive, self.do_mask, drop_last, stream, out)
+        return kmers.counts_dev(self.tracks.values(), track_of, starts, ends, k, alphabet, case_sensitive, self.do_mask, drop_last, stream, out, strands)
 
-    def kmer_count_matrix_dev(self, track_of, starts, width, k, alphabet="ACGT", case_sensitive=True, drop_last=False, stream=None, out=None):
+    def kmer_count_matrix_dev(self, track_of, starts, width, k, alphabet="ACGT", case_sensitive=True, drop_last=False, stream=None, out=None,
+                              strands=None):
         from . import kmers
 
-        return kmers.count_matrix_dev(self.tracks.values(), track_of, starts, width, k, alphabet, case_sensitive, self.do_mask, drop_last, stream, out)
+        return kmers.count_matrix_dev(self.tracks.values(), track_of, starts, width, k, alphabet, case_sensitive, self.do_mask, drop_last, stream, out,
+                                      strands)

@@ -32,6 +32,8 @@
 //                      takes (a) where the segment has at least KM_CUT window starts, and (b) always where bins > KM_LDS_BINS,
 //                      the counters a workgroup keeps in LDS (16 KiB; with the 2 KiB of staged blocks 8 workgroups fit a CU's
 //                      160 KiB, which is also what 256 threads each allow).  `force` overrides the cut-off for measurements and tests.
+//   strand             km_counts_strand_kernel takes a strand per row and counts a minus row over its reverse complement, without
+//                      mirroring the flat axis: described at km_counts_body.  km_counts_kernel is the STRAND == false instantiation.
 //   `counts` must be zero before the launch (the library zeroes it on the stream).  Nothing outside counts[0 .. n_rows * bins) is
 //   written: a word is below bins by construction (every digit is below radix).
 #pragma once
@@ -82,18 +84,32 @@ __host__ __device__ inline bool km_use_lds(int bins, int64_t windows, int force)
     return windows >= KM_CUT;
 }
 
-// track_of, start, row_off, row_base, width, o_first, count: as tb_bases_kernel; with row_off the walk ends at row_off[n_rows] where
-// that is below o_first + count (`count` may be a bound).  counts is [n_rows][bins], row r of the rows given is entry r.
-__global__ __launch_bounds__(KM_THREADS) void km_counts_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
-                                                               const int32_t *__restrict__ start, int64_t n_rows, int64_t row_base, int width,
-                                                               const int64_t *__restrict__ row_off, int64_t o_first, int64_t count, int do_mask,
-                                                               KmSpec spec, int32_t *__restrict__ counts)
+// the k two-bit digits of x, 2 k <= 16 bits, in reverse order
+__host__ __device__ inline unsigned km_reverse4(unsigned x, int k)
 {
-    __shared__ int32_t l_st[TB_CHUNK], l_en[TB_CHUNK];
-    __shared__ int32_t l_hist[KM_LDS_BINS];
+    x = ((x & 0x3333u) << 2) | ((x >> 2) & 0x3333u);
+    x = ((x & 0x0F0Fu) << 4) | ((x >> 4) & 0x0F0Fu);
+    x = ((x & 0x00FFu) << 8) | ((x >> 8) & 0x00FFu);
+    return x >> (16 - 2 * k);
+}
+
+// The text of km_counts_kernel (STRAND == false: `strand` is not read) and of km_counts_strand_kernel.  The string of a minus row is
+// the reverse complement of the plus row's (twobit.hpp, strand in the row-segment layer), and its windows are the plus string's
+// windows one to one: the window at offset j of the plus string is the one at offset len - k - j of the minus string, over the same
+// positions, so it counts under the same condition.  Only its word differs: the digits are those of the COMPLEMENTED letters (the
+// table need not be closed under complement: a letter's complement may have no digit, and then the window does not count), taken in
+// reverse order.  So a minus row walks the flat axis as a plus row does; strand is uniform over a segment, rows of either strand
+// share a tile, and both ways of accumulating are untouched.
+template <bool STRAND>
+__device__ __forceinline__ void km_counts_body(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
+                                               const int32_t *__restrict__ start, const int8_t *__restrict__ strand, int64_t n_rows, int64_t row_base,
+                                               int width, const int64_t *__restrict__ row_off, int64_t o_first, int64_t count, int do_mask,
+                                               const KmSpec &spec, int32_t *__restrict__ counts, int32_t *l_st, int32_t *l_en, int32_t *l_hist)
+{
     const int tid = (int)threadIdx.x;
     const int32_t BX_GLOBAL *g_track = as_global(track_of), *g_start = as_global(start);
     const int64_t BX_GLOBAL *g_off = as_global(row_off);
+    const int8_t BX_GLOBAL *g_strand = as_global(strand);
     const int k = spec.k, radix = spec.radix, bins = spec.bins;
     const unsigned k_bits = (1u << k) - 1u;
     int64_t o_end = o_first + count;
@@ -107,6 +123,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_counts_kernel(const TbTrack *__
             const TbSegment sg = tb_segment(g_off, n_rows, row_base, width, o, t1);
             const int64_t r = sg.r, seg1 = sg.seg1;
             const int seg_len = (int)(seg1 - o);
+            const bool minus = tb_minus<STRAND>(g_strand, r);
             // p0: the position of the segment's first window start; [c0, c1): the positions under the segment's windows that are
             // letters of the row
             const TbLetters lt = tb_letters(table, n_tracks, g_track[r], g_start[r], sg.r_lo, sg.r_hi, o, seg_len + k - 1);
@@ -136,7 +153,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_counts_kernel(const TbTrack *__
                 for (int i = 0; i < cnt; i++) {
                     const int at = b + i;
                     const uint32_t word = at < 16 ? w0 : at < 32 ? w1 : w2;
-                    const unsigned code = (word >> (30 - 2 * (at & 15))) & 3u;
+                    const unsigned code = tb_complement((word >> (30 - 2 * (at & 15))) & 3u, minus);
                     const unsigned cls = code + ((bits.is_m >> i) & 1u ? 4u : 0u);
                     const unsigned d1 = (bits.is_n >> i) & 1u ? 0u : (spec.digits >> (4 * cls)) & 15u;  // digit + 1
                     if (d1 == 0) continue;
@@ -156,6 +173,10 @@ __global__ __launch_bounds__(KM_THREADS) void km_counts_kernel(const TbTrack *__
                 int word;
                 if (radix == 4) {
                     word = (int)(dig >> (2 * j)) & (bins - 1);  // the digits as they lie
+                    if (minus) word = (int)km_reverse4((unsigned)word, k);
+                } else if (minus) {
+                    word = 0;
+                    for (int q = 0; q < k; q++) word = word * radix + (int)((dig >> (2 * (j + q))) & 3u);  // the last letter least significant
                 } else {
                     word = 0;
                     int factor = 1;
@@ -177,6 +198,29 @@ __global__ __launch_bounds__(KM_THREADS) void km_counts_kernel(const TbTrack *__
             o = seg1;
         }
     }
+}
+
+// track_of, start, row_off, row_base, width, o_first, count: as tb_bases_kernel; with row_off the walk ends at row_off[n_rows] where
+// that is below o_first + count (`count` may be a bound).  counts is [n_rows][bins], row r of the rows given is entry r.
+__global__ __launch_bounds__(KM_THREADS) void km_counts_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
+                                                               const int32_t *__restrict__ start, int64_t n_rows, int64_t row_base, int width,
+                                                               const int64_t *__restrict__ row_off, int64_t o_first, int64_t count, int do_mask,
+                                                               KmSpec spec, int32_t *__restrict__ counts)
+{
+    __shared__ int32_t l_st[TB_CHUNK], l_en[TB_CHUNK];
+    __shared__ int32_t l_hist[KM_LDS_BINS];
+    km_counts_body<false>(table, n_tracks, track_of, start, nullptr, n_rows, row_base, width, row_off, o_first, count, do_mask, spec, counts, l_st, l_en, l_hist);
+}
+
+// the same with strand[n_rows] of the rows given: any non-zero entry is a minus row, counted as its reverse complement
+__global__ __launch_bounds__(KM_THREADS) void km_counts_strand_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
+                                                                      const int32_t *__restrict__ start, const int8_t *__restrict__ strand, int64_t n_rows,
+                                                                      int64_t row_base, int width, const int64_t *__restrict__ row_off, int64_t o_first,
+                                                                      int64_t count, int do_mask, KmSpec spec, int32_t *__restrict__ counts)
+{
+    __shared__ int32_t l_st[TB_CHUNK], l_en[TB_CHUNK];
+    __shared__ int32_t l_hist[KM_LDS_BINS];
+    km_counts_body<true>(table, n_tracks, track_of, start, strand, n_rows, row_base, width, row_off, o_first, count, do_mask, spec, counts, l_st, l_en, l_hist);
 }
 
 }  // namespace bxmi

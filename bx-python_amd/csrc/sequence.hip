@@ -5,6 +5,9 @@
 // Position weight matrices scored over those rows (bxmi_pwm_*, bxmi_twobit_pwm_*): kernels and semantics in pwm.hpp, those of the
 // thresholded hits (bxmi_twobit_pwm_hits*) in pwm_hits.hpp; they use the same table and scratch and so the same rule.
 // The k-mer spectrum of those rows (bxmi_twobit_kmer_counts*): kernel and semantics in kmer.hpp; the same table, scratch and rule.
+// Strand (bxmi_twobit_bases_strand*, bxmi_twobit_composition_strand*, bxmi_twobit_kmer_counts_strand*): the unstranded entry points
+// are the stranded ones with a NULL strand, which launch the kernels they always launched; a strand array launches the *_strand_kernel
+// of twobit.hpp and kmer.hpp.  The host forms check the entries (0 or 1) and slice the array with the rows of every slab.
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -53,6 +56,7 @@ constexpr int64_t KM_OUT_MAX = INT64_MAX / 8;         // counters of all rows: t
 struct SequenceBufs {
     DevBuf table;                         // TbTrack [n_tracks + 1], the last one the spare entry
     DevBuf q_track, q_start, q_end, r;    // staging of the host forms
+    DevBuf q_strand;                      // int8 [rows of a slab] of the stranded host forms
     DevBuf keys;                          // uint64 [n_mats][n] of the best hits
     DevBuf hit_counts, hit_bases, hit_scan;  // of the thresholded hits: int32 [n_mats][tiles], int64 bases of them + total + heads, the scan's sums
 };
@@ -215,6 +219,27 @@ static int offsets_check(const char *who, const int64_t *row_off, int64_t n, int
     return BXMI_OK;
 }
 
+// what the host forms check of a strand array they can read (nullptr: all plus)
+static int strand_check(const char *who, const int8_t *strand, int64_t n)
+{
+    if (!strand) return BXMI_OK;
+    for (int64_t i = 0; i < n; i++)
+        if (strand[i] != 0 && strand[i] != 1)
+            return fail(BXMI_EINVAL, "%s: strand[%lld] = %d of row %lld is neither 0 (plus) nor 1 (minus)", who, (long long)i, (int)strand[i], (long long)i);
+    return BXMI_OK;
+}
+
+// strand[r0 .. r0 + m) into S.q_strand -> *d_strand (nullptr without a strand array); queued on st
+static int stage_strand(SequenceBufs &S, const int8_t *strand, int64_t r0, int64_t m, const int8_t **d_strand, hipStream_t st)
+{
+    *d_strand = nullptr;
+    if (!strand) return BXMI_OK;
+    BXMI_TRY(S.q_strand.reserve((size_t)(m > 0 ? m : 1)));
+    if (m > 0) BXMI_HIP(hipMemcpyAsync(S.q_strand.p, strand + r0, (size_t)m, hipMemcpyHostToDevice, st));
+    *d_strand = S.q_strand.as<int8_t>();
+    return BXMI_OK;
+}
+
 // What the host forms put on the device of rows [r0, r0 + m): track and start into S.q_track and S.q_start and, with row_off, their
 // m + 1 offsets into S.q_end -> *d_off, the offsets on the device (nullptr without).  Queued on st: the caller waits before the next use.
 static int stage_rows(SequenceBufs &S, const int32_t *track_of, const int32_t *start, const int64_t *row_off, int64_t r0, int64_t m, const int64_t **d_off,
@@ -242,40 +267,58 @@ static unsigned fill_grid(int64_t tiles)
 }
 
 // output bytes [o_first, o_first + count) of rows [row_base, row_base + n_rows); `out` is byte o_first's address
-static int bases_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n_rows, int64_t row_base, int32_t width,
-                        const int64_t *row_off, int64_t o_first, int64_t count, int do_mask, int pad, uint8_t *out, hipStream_t st)
+static int bases_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand, int64_t n_rows,
+                        int64_t row_base, int32_t width, const int64_t *row_off, int64_t o_first, int64_t count, int do_mask, int pad, uint8_t *out,
+                        hipStream_t st)
 {
     const int vec = (reinterpret_cast<uintptr_t>(out) & 15) == 0;  // else the kernel stores byte by byte
     constexpr int64_t PER_LAUNCH = TB_TILES_PER_LAUNCH * TB_TILE;
     for (int64_t done = 0; done < count; done += PER_LAUNCH) {
         const int64_t m = count - done < PER_LAUNCH ? count - done : PER_LAUNCH;
-        hipLaunchKernelGGL(tb_bases_kernel, dim3((unsigned)div_up(m, TB_TILE)), dim3(TB_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of,
-                           start, n_rows, row_base, (int)width, row_off, o_first + done, m, do_mask, pad, out + done, vec);
+        if (strand)
+            hipLaunchKernelGGL(tb_bases_strand_kernel, dim3((unsigned)div_up(m, TB_TILE)), dim3(TB_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks,
+                               track_of, start, strand, n_rows, row_base, (int)width, row_off, o_first + done, m, do_mask, pad, out + done, vec);
+        else
+            hipLaunchKernelGGL(tb_bases_kernel, dim3((unsigned)div_up(m, TB_TILE)), dim3(TB_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of,
+                               start, n_rows, row_base, (int)width, row_off, o_first + done, m, do_mask, pad, out + done, vec);
         BXMI_LAUNCH_CHECK();
     }
     return BXMI_OK;
 }
 
-extern "C" int bxmi_twobit_bases_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
-                                     int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, int pad, uint8_t *out, void *stream)
+static int bases_dev(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand,
+                     int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, int pad, uint8_t *out, void *stream)
 {
-    const char *who = "bxmi_twobit_bases_dev";
     BXMI_TRY(bases_check(who, tracks, n_tracks, track_of, start, n, width, row_off_or_null, total, pad, out));
     if (n == 0 || total == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_sequence.lock);
     BXMI_TRY(g_sequence.enter());
     BXMI_TRY(sequence_fill_table(g_sequence.bufs, tracks, n_tracks, as_stream(stream)));
-    return bases_launch(g_sequence.bufs, n_tracks, track_of, start, n, 0, width, row_off_or_null, 0, total, do_mask != 0, pad, out, as_stream(stream));
+    return bases_launch(g_sequence.bufs, n_tracks, track_of, start, strand, n, 0, width, row_off_or_null, 0, total, do_mask != 0, pad, out, as_stream(stream));
 }
 
-extern "C" int bxmi_twobit_bases(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
-                                 const int64_t *row_off_or_null, int64_t total, int do_mask, int pad, uint8_t *out)
+extern "C" int bxmi_twobit_bases_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
+                                     int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, int pad, uint8_t *out, void *stream)
 {
-    const char *who = "bxmi_twobit_bases";
+    return bases_dev("bxmi_twobit_bases_dev", tracks, n_tracks, track_of, start, nullptr, n, width, row_off_or_null, total, do_mask, pad, out, stream);
+}
+
+extern "C" int bxmi_twobit_bases_strand_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                            const int8_t *strand_or_null, int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total,
+                                            int do_mask, int pad, uint8_t *out, void *stream)
+{
+    return bases_dev("bxmi_twobit_bases_strand_dev", tracks, n_tracks, track_of, start, strand_or_null, n, width, row_off_or_null, total, do_mask, pad, out,
+                     stream);
+}
+
+static int bases_host(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand,
+                      int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, int pad, uint8_t *out)
+{
     const int64_t *row_off = row_off_or_null;
     BXMI_TRY(bases_check(who, tracks, n_tracks, track_of, start, n, width, row_off, total, pad, out));
     BXMI_TRY(offsets_check(who, row_off, n, total));
     BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    BXMI_TRY(strand_check(who, strand, n));
     if (n == 0 || total == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_sequence.lock);
     BXMI_TRY(g_sequence.enter(true));
@@ -286,14 +329,29 @@ extern "C" int bxmi_twobit_bases(bxmi_twobit_t *const *tracks, int32_t n_tracks,
         const int64_t count = total - o0 < TB_SLAB ? total - o0 : TB_SLAB;
         const SaRows rows = sa_rows_of(row_off, n, width, o0, count);  // the slab's rows
         const int64_t *d_off;
+        const int8_t *d_strand;
         BXMI_TRY(stage_rows(S, track_of, start, row_off, rows.r0, rows.m, &d_off, st));
+        BXMI_TRY(stage_strand(S, strand, rows.r0, rows.m, &d_strand, st));
         BXMI_TRY(S.r.reserve((size_t)count));
-        BXMI_TRY(bases_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), rows.m, rows.r0, width, d_off, o0, count, do_mask != 0, pad,
-                              S.r.as<uint8_t>(), st));
+        BXMI_TRY(bases_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), d_strand, rows.m, rows.r0, width, d_off, o0, count, do_mask != 0,
+                              pad, S.r.as<uint8_t>(), st));
         BXMI_HIP(hipMemcpyAsync(out + o0, S.r.p, (size_t)count, hipMemcpyDeviceToHost, st));
         BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
     }
     return BXMI_OK;
+}
+
+extern "C" int bxmi_twobit_bases(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                                 const int64_t *row_off_or_null, int64_t total, int do_mask, int pad, uint8_t *out)
+{
+    return bases_host("bxmi_twobit_bases", tracks, n_tracks, track_of, start, nullptr, n, width, row_off_or_null, total, do_mask, pad, out);
+}
+
+extern "C" int bxmi_twobit_bases_strand(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                        const int8_t *strand_or_null, int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask,
+                                        int pad, uint8_t *out)
+{
+    return bases_host("bxmi_twobit_bases_strand", tracks, n_tracks, track_of, start, strand_or_null, n, width, row_off_or_null, total, do_mask, pad, out);
 }
 
 // ---- base counts (tb_composition_kernel) ----
@@ -305,36 +363,51 @@ static int composition_check(const char *who, bxmi_twobit_t *const *tracks, int3
     return BXMI_OK;
 }
 
-static int composition_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, int64_t n, int do_mask,
-                              int32_t *counts, hipStream_t st)
+static int composition_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end, const int8_t *strand,
+                              int64_t n, int do_mask, int32_t *counts, hipStream_t st)
 {
     for (int64_t first = 0; first < n; first += TB_ROWS_PER_LAUNCH) {
         const int64_t m = n - first < TB_ROWS_PER_LAUNCH ? n - first : TB_ROWS_PER_LAUNCH;
-        hipLaunchKernelGGL(tb_composition_kernel, dim3((unsigned)m), dim3(TB_WAVE), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of + first,
-                           start + first, end + first, do_mask, counts + 6 * first);
+        if (strand)
+            hipLaunchKernelGGL(tb_composition_strand_kernel, dim3((unsigned)m), dim3(TB_WAVE), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of + first,
+                               start + first, end + first, strand + first, do_mask, counts + 6 * first);
+        else
+            hipLaunchKernelGGL(tb_composition_kernel, dim3((unsigned)m), dim3(TB_WAVE), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of + first,
+                               start + first, end + first, do_mask, counts + 6 * first);
         BXMI_LAUNCH_CHECK();
     }
     return BXMI_OK;
 }
 
-extern "C" int bxmi_twobit_composition_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
-                                           const int32_t *end, int64_t n, int do_mask, int32_t *counts, void *stream)
+static int composition_dev(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                           const int8_t *strand, const int32_t *end, int64_t n, int do_mask, int32_t *counts, void *stream)
 {
-    const char *who = "bxmi_twobit_composition_dev";
     BXMI_TRY(composition_check(who, tracks, n_tracks, track_of, start, end, n, counts));
     if (n == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_sequence.lock);
     BXMI_TRY(g_sequence.enter());
     BXMI_TRY(sequence_fill_table(g_sequence.bufs, tracks, n_tracks, as_stream(stream)));
-    return composition_launch(g_sequence.bufs, n_tracks, track_of, start, end, n, do_mask != 0, counts, as_stream(stream));
+    return composition_launch(g_sequence.bufs, n_tracks, track_of, start, end, strand, n, do_mask != 0, counts, as_stream(stream));
 }
 
-extern "C" int bxmi_twobit_composition(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
-                                       int64_t n, int do_mask, int32_t *counts)
+extern "C" int bxmi_twobit_composition_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                           const int32_t *end, int64_t n, int do_mask, int32_t *counts, void *stream)
 {
-    const char *who = "bxmi_twobit_composition";
+    return composition_dev("bxmi_twobit_composition_dev", tracks, n_tracks, track_of, start, nullptr, end, n, do_mask, counts, stream);
+}
+
+extern "C" int bxmi_twobit_composition_strand_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                                  const int8_t *strand_or_null, const int32_t *end, int64_t n, int do_mask, int32_t *counts, void *stream)
+{
+    return composition_dev("bxmi_twobit_composition_strand_dev", tracks, n_tracks, track_of, start, strand_or_null, end, n, do_mask, counts, stream);
+}
+
+static int composition_host(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                            const int8_t *strand, const int32_t *end, int64_t n, int do_mask, int32_t *counts)
+{
     BXMI_TRY(composition_check(who, tracks, n_tracks, track_of, start, end, n, counts));
     BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    BXMI_TRY(strand_check(who, strand, n));
     if (n == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_sequence.lock);
     BXMI_TRY(g_sequence.enter(true));
@@ -353,11 +426,26 @@ extern "C" int bxmi_twobit_composition(bxmi_twobit_t *const *tracks, int32_t n_t
         BXMI_HIP(hipMemcpyAsync(S.q_track.p, track_of + first, in_bytes, hipMemcpyHostToDevice, st));
         BXMI_HIP(hipMemcpyAsync(S.q_start.p, start + first, in_bytes, hipMemcpyHostToDevice, st));
         BXMI_HIP(hipMemcpyAsync(S.q_end.p, end + first, in_bytes, hipMemcpyHostToDevice, st));
-        BXMI_TRY(composition_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), S.q_end.as<int32_t>(), m, do_mask != 0, S.r.as<int32_t>(), st));
+        const int8_t *d_strand;
+        BXMI_TRY(stage_strand(S, strand, first, m, &d_strand, st));
+        BXMI_TRY(composition_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), S.q_end.as<int32_t>(), d_strand, m, do_mask != 0,
+                                    S.r.as<int32_t>(), st));
         BXMI_HIP(hipMemcpyAsync(counts + 6 * first, S.r.p, in_bytes * 6, hipMemcpyDeviceToHost, st));
         BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
     }
     return BXMI_OK;
+}
+
+extern "C" int bxmi_twobit_composition(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int32_t *end,
+                                       int64_t n, int do_mask, int32_t *counts)
+{
+    return composition_host("bxmi_twobit_composition", tracks, n_tracks, track_of, start, nullptr, end, n, do_mask, counts);
+}
+
+extern "C" int bxmi_twobit_composition_strand(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                              const int8_t *strand_or_null, const int32_t *end, int64_t n, int do_mask, int32_t *counts)
+{
+    return composition_host("bxmi_twobit_composition_strand", tracks, n_tracks, track_of, start, strand_or_null, end, n, do_mask, counts);
 }
 
 // ---- position weight matrices (pwm.hpp) ----
@@ -708,40 +796,62 @@ static int kmer_check(const char *who, bxmi_twobit_t *const *tracks, int32_t n_t
 
 // counts [n_rows][bins] = 0, then the windows that start at elements [o_first, o_first + count) of rows [row_base, row_base + n_rows):
 // one launch of at most a device's fill of workgroups, each walking every gridDim.x-th tile (`count` may be a bound)
-static int kmer_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n_rows, int64_t row_base, int32_t width,
-                       const int64_t *row_off, int64_t o_first, int64_t count, int do_mask, const KmSpec &spec, int32_t *counts, hipStream_t st)
+static int kmer_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand, int64_t n_rows,
+                       int64_t row_base, int32_t width, const int64_t *row_off, int64_t o_first, int64_t count, int do_mask, const KmSpec &spec,
+                       int32_t *counts, hipStream_t st)
 {
     BXMI_HIP(hipMemsetAsync(counts, 0, (size_t)n_rows * (size_t)spec.bins * sizeof(int32_t), st));
     if (count <= 0) return BXMI_OK;
-    hipLaunchKernelGGL(km_counts_kernel, dim3(fill_grid(div_up(count, KM_TILE))), dim3(KM_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of,
-                       start, n_rows, row_base, (int)width, row_off, o_first, count, do_mask, spec, counts);
+    if (strand)
+        hipLaunchKernelGGL(km_counts_strand_kernel, dim3(fill_grid(div_up(count, KM_TILE))), dim3(KM_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks,
+                           track_of, start, strand, n_rows, row_base, (int)width, row_off, o_first, count, do_mask, spec, counts);
+    else
+        hipLaunchKernelGGL(km_counts_kernel, dim3(fill_grid(div_up(count, KM_TILE))), dim3(KM_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of,
+                           start, n_rows, row_base, (int)width, row_off, o_first, count, do_mask, spec, counts);
     BXMI_LAUNCH_CHECK();
     return BXMI_OK;
 }
 
-extern "C" int bxmi_twobit_kmer_counts_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
-                                           int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, int k, int radix,
-                                           const int8_t *digits, int32_t *counts, void *stream)
+static int kmer_dev(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand,
+                    int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, int k, int radix, const int8_t *digits,
+                    int32_t *counts, void *stream)
 {
-    const char *who = "bxmi_twobit_kmer_counts_dev";
     KmSpec spec{};
     BXMI_TRY(kmer_check(who, tracks, n_tracks, track_of, start, n, width, row_off_or_null, total, k, radix, digits, counts, spec));
     if (n == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_sequence.lock);
     BXMI_TRY(g_sequence.enter());
     BXMI_TRY(sequence_fill_table(g_sequence.bufs, tracks, n_tracks, as_stream(stream)));
-    return kmer_launch(g_sequence.bufs, n_tracks, track_of, start, n, 0, width, row_off_or_null, 0, total, do_mask != 0, spec, counts, as_stream(stream));
+    return kmer_launch(g_sequence.bufs, n_tracks, track_of, start, strand, n, 0, width, row_off_or_null, 0, total, do_mask != 0, spec, counts,
+                       as_stream(stream));
 }
 
-extern "C" int bxmi_twobit_kmer_counts(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
-                                       const int64_t *row_off_or_null, int64_t total, int do_mask, int k, int radix, const int8_t *digits, int32_t *counts)
+extern "C" int bxmi_twobit_kmer_counts_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
+                                           int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, int k, int radix,
+                                           const int8_t *digits, int32_t *counts, void *stream)
 {
-    const char *who = "bxmi_twobit_kmer_counts";
+    return kmer_dev("bxmi_twobit_kmer_counts_dev", tracks, n_tracks, track_of, start, nullptr, n, width, row_off_or_null, total, do_mask, k, radix, digits,
+                    counts, stream);
+}
+
+extern "C" int bxmi_twobit_kmer_counts_strand_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                                  const int8_t *strand_or_null, int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total,
+                                                  int do_mask, int k, int radix, const int8_t *digits, int32_t *counts, void *stream)
+{
+    return kmer_dev("bxmi_twobit_kmer_counts_strand_dev", tracks, n_tracks, track_of, start, strand_or_null, n, width, row_off_or_null, total, do_mask, k,
+                    radix, digits, counts, stream);
+}
+
+static int kmer_host(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand,
+                     int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, int k, int radix, const int8_t *digits,
+                     int32_t *counts)
+{
     const int64_t *row_off = row_off_or_null;
     KmSpec spec{};
     BXMI_TRY(kmer_check(who, tracks, n_tracks, track_of, start, n, width, row_off, total, k, radix, digits, counts, spec));
     BXMI_TRY(offsets_check(who, row_off, n, total));
     BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    BXMI_TRY(strand_check(who, strand, n));
     if (n == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_sequence.lock);
     BXMI_TRY(g_sequence.enter(true));
@@ -755,12 +865,28 @@ extern "C" int bxmi_twobit_kmer_counts(bxmi_twobit_t *const *tracks, int32_t n_t
         const int64_t o0 = row_off ? row_off[r0] : r0 * (int64_t)width, o1 = row_off ? row_off[r0 + m] : (r0 + m) * (int64_t)width;
         const size_t out_bytes = (size_t)m * (size_t)spec.bins * sizeof(int32_t);
         const int64_t *d_off;
+        const int8_t *d_strand;
         BXMI_TRY(stage_rows(S, track_of, start, row_off, r0, m, &d_off, st));
+        BXMI_TRY(stage_strand(S, strand, r0, m, &d_strand, st));
         BXMI_TRY(S.r.reserve(out_bytes));
-        BXMI_TRY(kmer_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), m, r0, width, d_off, o0, o1 - o0, do_mask != 0, spec,
+        BXMI_TRY(kmer_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), d_strand, m, r0, width, d_off, o0, o1 - o0, do_mask != 0, spec,
                              S.r.as<int32_t>(), st));
         BXMI_HIP(hipMemcpyAsync(counts + r0 * (int64_t)spec.bins, S.r.p, out_bytes, hipMemcpyDeviceToHost, st));
         BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
     }
     return BXMI_OK;
+}
+
+extern "C" int bxmi_twobit_kmer_counts(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                                       const int64_t *row_off_or_null, int64_t total, int do_mask, int k, int radix, const int8_t *digits, int32_t *counts)
+{
+    return kmer_host("bxmi_twobit_kmer_counts", tracks, n_tracks, track_of, start, nullptr, n, width, row_off_or_null, total, do_mask, k, radix, digits, counts);
+}
+
+extern "C" int bxmi_twobit_kmer_counts_strand(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                              const int8_t *strand_or_null, int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total,
+                                              int do_mask, int k, int radix, const int8_t *digits, int32_t *counts)
+{
+    return kmer_host("bxmi_twobit_kmer_counts_strand", tracks, n_tracks, track_of, start, strand_or_null, n, width, row_off_or_null, total, do_mask, k,
+                     radix, digits, counts);
 }

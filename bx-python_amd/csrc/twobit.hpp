@@ -22,6 +22,11 @@
 //                      (kmer.hpp) share it; the latter's `want` positions per segment hold a halo beyond the segment.  Described
 //                      once, at the helpers.  (pw_scores_kernel and pw_hits_kernel still carry the same walk as their own text:
 //                      on the helpers they measured 1 - 3 % slower at unchanged register counts)
+//   strand             tb_bases_strand_kernel, tb_composition_strand_kernel (and km_counts_strand_kernel of kmer.hpp) take a strand
+//                      per row: a minus row is the reverse complement of the plus row (the reference's SeqFile.reverse_complement,
+//                      lib/bx/seq/seq.py:108-109), the pad mirrored with it and not complemented.  Strand sits in the row-segment layer
+//                      (tb_minus, tb_letters_minus, tb_complement; described there); each kernel's text is a body templated on
+//                      STRAND with two thin wrappers, and the unstranded kernels are the STRAND == false instantiations.
 //   tb_count_kernel    (creation) the four code counts of every checkpoint block of TB_CKPT bases, one wave per block, as four
 //                      planes; a device scan per plane (primitives.hpp) and tb_interleave_kernel turn them into the running totals
 //                      ckpt[k] = counts of bases [0, TB_CKPT * k) as one 16-byte entry (T, C, A, G).
@@ -285,42 +290,81 @@ __device__ __forceinline__ uint64_t tb_codes(const TbTrack &tr, int pf, int cnt)
 }
 __device__ __forceinline__ unsigned tb_code(uint64_t codes, int at) { return (unsigned)(codes >> (62 - 2 * at)) & 3u; }
 
-// track_of, start: rows [row_base, row_base + n_rows) of the batch; row_off (ragged; else nullptr and `width` >= 1): the n_rows + 1
-// offsets of those rows, absolute.  The launch covers output bytes [o_first, o_first + count), TB_TILE per workgroup.
-__global__ __launch_bounds__(TB_THREADS) void tb_bases_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
-                                                              const int32_t *__restrict__ start, int64_t n_rows, int64_t row_base, int width,
-                                                              const int64_t *__restrict__ row_off, int64_t o_first, int64_t count, int do_mask,
-                                                              int pad, uint8_t *__restrict__ out, int vec)
+// ---- strand in the row-segment layer ----
+// A batch may carry a strand per row (int8; 0: as stored, anything else: the reverse complement, the reference's
+// SeqFile.reverse_complement, lib/bx/seq/seq.py:108-109 over DNA_COMP, seq.py:9-14).  Element j of a minus row of len elements is the
+// COMPLEMENT of the letter at position start + (len - 1 - j); pad stays pad.  Strand is uniform over a segment like everything else
+// about it, and a segment of a minus row is still one ascending run of positions, so the loads, the searches and the chunk walk
+// (tb_block_bits, tb_codes) are what they are for a plus row: tb_minus says whether the segment's row is a minus row,
+// tb_letters_minus gives its positions (the mirror of tb_letters without a halo), tb_complement the code (T=0 C=1 A=2 G=3: code ^ 2;
+// 'N' and the case bit are their own complements).  A kernel that only counts what lies under a row (km_counts_kernel) keeps
+// tb_letters: the positions of a minus row are those of the plus row.  STRAND == false folds all of it away.
+template <bool STRAND>
+__device__ __forceinline__ bool tb_minus(const int8_t BX_GLOBAL *g_strand, int64_t r)
 {
-    __shared__ int32_t l_st[TB_CHUNK], l_en[TB_CHUNK];
+    if constexpr (STRAND) return g_strand[r] != 0;
+    else return false;
+}
+// The segment [o, seg1) of a minus row whose elements end at r_hi: element e of it is position p0 + (seg1 - 1 - e), in 64 bits; of
+// those positions [c0, c1) are letters.
+__device__ __forceinline__ TbLetters tb_letters_minus(const TbTrack *table, int n_tracks, int t, int start, int64_t r_hi, int64_t o, int64_t seg1)
+{
+    const bool named = t >= 0 && t < n_tracks;
+    TbLetters s{table[named ? t : n_tracks], 0, 0, 0};
+    s.p0 = (int64_t)start + (r_hi - seg1);
+    s.c1 = s.p0 + (seg1 - o);
+    if (s.c1 > s.tr.size) s.c1 = s.tr.size;
+    s.c0 = s.p0 > 0 ? s.p0 : 0;
+    return s;
+}
+__device__ __forceinline__ unsigned tb_complement(unsigned code, bool minus) { return minus ? code ^ 2u : code; }
+
+// The text of tb_bases_kernel (STRAND == false: `strand` is not read) and of tb_bases_strand_kernel (STRAND == true: strand[r] of
+// the rows given).  In a segment of a minus row a thread's bytes are still one ascending run of positions [pf, pf + cnt); letter i of
+// them goes to place cnt - 1 - i of the thread's bytes of the segment, complemented.
+template <bool STRAND>
+__device__ __forceinline__ void tb_bases_body(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
+                                              const int32_t *__restrict__ start, const int8_t *__restrict__ strand, int64_t n_rows, int64_t row_base,
+                                              int width, const int64_t *__restrict__ row_off, int64_t o_first, int64_t count, int do_mask, int pad,
+                                              uint8_t *__restrict__ out, int vec, int32_t *l_st, int32_t *l_en)
+{
     const int tid = (int)threadIdx.x;
     const int64_t t0 = o_first + (int64_t)blockIdx.x * TB_TILE;
     const int64_t t1 = t0 + TB_TILE < o_first + count ? t0 + TB_TILE : o_first + count;
     const int64_t e0 = t0 + 16 * tid;  // this thread's bytes: [e0, e0 + 16)
     const int32_t BX_GLOBAL *g_track = as_global(track_of), *g_start = as_global(start);
     const int64_t BX_GLOBAL *g_off = as_global(row_off);
+    const int8_t BX_GLOBAL *g_strand = as_global(strand);
     const uint32_t pad4 = (uint32_t)(pad & 0xFF) * 0x01010101u;
     uint32_t v[4] = {pad4, pad4, pad4, pad4};
     for (int64_t o = t0; o < t1;) {  // the segment [o, seg1) of row r, whose bytes are [r_lo, r_hi)
         const TbSegment sg = tb_segment(g_off, n_rows, row_base, width, o, t1);
         const int64_t seg1 = sg.seg1;
-        const TbLetters lt = tb_letters(table, n_tracks, g_track[sg.r], g_start[sg.r], sg.r_lo, seg1, o, seg1 - o);  // the segment's positions
+        const bool minus = tb_minus<STRAND>(g_strand, sg.r);
+        const TbLetters lt = minus ? tb_letters_minus(table, n_tracks, g_track[sg.r], g_start[sg.r], sg.r_hi, o, seg1)
+                                   : tb_letters(table, n_tracks, g_track[sg.r], g_start[sg.r], sg.r_lo, seg1, o, seg1 - o);  // the segment's positions
         const int64_t p0 = lt.p0, c0 = lt.c0, c1 = lt.c1;
         if (c0 < c1) {
             // this thread's bytes that are bases of the segment: [lo_el, hi_el), positions [pf, pf + cnt), bits [qa, qa + cnt) of 16
             int64_t lo_el = e0 > o ? e0 : o, hi_el = e0 + 16 < seg1 ? e0 + 16 : seg1;
-            if (lo_el < o + (c0 - p0)) lo_el = o + (c0 - p0);
-            if (hi_el > o + (c1 - p0)) hi_el = o + (c1 - p0);
+            if (minus) {  // (position p is element seg1 - 1 - (p - p0))
+                if (lo_el < seg1 - (c1 - p0)) lo_el = seg1 - (c1 - p0);
+                if (hi_el > seg1 - (c0 - p0)) hi_el = seg1 - (c0 - p0);
+            } else {
+                if (lo_el < o + (c0 - p0)) lo_el = o + (c0 - p0);
+                if (hi_el > o + (c1 - p0)) hi_el = o + (c1 - p0);
+            }
             const int cnt = lo_el < hi_el ? (int)(hi_el - lo_el) : 0;
-            const int qa = cnt ? (int)(lo_el - e0) : 0, pf = cnt ? (int)(p0 + (lo_el - o)) : 0;
+            const int qa = cnt ? (int)(lo_el - e0) : 0, pf = cnt ? (int)(minus ? p0 + (seg1 - hi_el) : p0 + (lo_el - o)) : 0;
             const uint64_t codes = tb_codes(lt.tr, pf, cnt);
             const TbBits bits = tb_block_bits<TB_THREADS>(lt.tr, do_mask, c0, c1, pf, cnt, tid, l_st, l_en);
             const int b = pf & 15;
 #pragma unroll
             for (int q = 0; q < 16; q++) {
-                const int i = q - qa;  // the base's place among this thread's
+                int i = q - qa;  // the base's place among this thread's
                 if (i < 0 || i >= cnt) continue;
-                unsigned letter = (bits.is_n >> i) & 1u ? (unsigned)'N' : (TB_LETTERS >> (8 * tb_code(codes, b + i))) & 0xFFu;
+                if (minus) i = cnt - 1 - i;
+                unsigned letter = (bits.is_n >> i) & 1u ? (unsigned)'N' : (TB_LETTERS >> (8 * tb_complement(tb_code(codes, b + i), minus))) & 0xFFu;
                 if ((bits.is_m >> i) & 1u) letter |= 0x20u;
                 v[q >> 2] = (v[q >> 2] & ~(0xFFu << (8 * (q & 3)))) | (letter << (8 * (q & 3)));
             }
@@ -336,6 +380,27 @@ __global__ __launch_bounds__(TB_THREADS) void tb_bases_kernel(const TbTrack *__r
         for (int q = 0; q < 16; q++)
             if (e0 + q < t1) g_out[q] = (uint8_t)(v[q >> 2] >> (8 * (q & 3)));
     }
+}
+
+// track_of, start: rows [row_base, row_base + n_rows) of the batch; row_off (ragged; else nullptr and `width` >= 1): the n_rows + 1
+// offsets of those rows, absolute.  The launch covers output bytes [o_first, o_first + count), TB_TILE per workgroup.
+__global__ __launch_bounds__(TB_THREADS) void tb_bases_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
+                                                              const int32_t *__restrict__ start, int64_t n_rows, int64_t row_base, int width,
+                                                              const int64_t *__restrict__ row_off, int64_t o_first, int64_t count, int do_mask,
+                                                              int pad, uint8_t *__restrict__ out, int vec)
+{
+    __shared__ int32_t l_st[TB_CHUNK], l_en[TB_CHUNK];
+    tb_bases_body<false>(table, n_tracks, track_of, start, nullptr, n_rows, row_base, width, row_off, o_first, count, do_mask, pad, out, vec, l_st, l_en);
+}
+
+// the same with strand[n_rows] of the rows given: any non-zero entry is a minus row
+__global__ __launch_bounds__(TB_THREADS) void tb_bases_strand_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
+                                                                     const int32_t *__restrict__ start, const int8_t *__restrict__ strand, int64_t n_rows,
+                                                                     int64_t row_base, int width, const int64_t *__restrict__ row_off, int64_t o_first,
+                                                                     int64_t count, int do_mask, int pad, uint8_t *__restrict__ out, int vec)
+{
+    __shared__ int32_t l_st[TB_CHUNK], l_en[TB_CHUNK];
+    tb_bases_body<true>(table, n_tracks, track_of, start, strand, n_rows, row_base, width, row_off, o_first, count, do_mask, pad, out, vec, l_st, l_en);
 }
 
 // ---- base counts ----
@@ -357,10 +422,11 @@ __device__ __forceinline__ TbMeet tb_meet(const int32_t BX_GLOBAL *b_st, const i
     return m;
 }
 
-// counts[row] = A, C, G, T, N, masked of [start[row], end[row]) clipped to the sequence; one wave per row
-__global__ __launch_bounds__(TB_WAVE) void tb_composition_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
-                                                                 const int32_t *__restrict__ start, const int32_t *__restrict__ end, int do_mask,
-                                                                 int32_t *__restrict__ counts)
+// The text of tb_composition_kernel and of tb_composition_strand_kernel: the strand of a row is a swap at the final store.
+template <bool STRAND>
+__device__ __forceinline__ void tb_composition_body(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
+                                                    const int32_t *__restrict__ start, const int32_t *__restrict__ end, const int8_t *__restrict__ strand,
+                                                    int do_mask, int32_t *__restrict__ counts)
 {
     const int lane = (int)threadIdx.x;
     const int64_t row = blockIdx.x;
@@ -397,9 +463,27 @@ __global__ __launch_bounds__(TB_WAVE) void tb_composition_kernel(const TbTrack *
     TB_WAVE_SUM4(acc);
     if (lane == 0) {
         int32_t BX_GLOBAL *o = as_global(counts) + 6 * row;
-        o[0] = acc[2], o[1] = acc[1], o[2] = acc[3], o[3] = acc[0];  // A, C, G, T of codes T=0 C=1 A=2 G=3
+        if (tb_minus<STRAND>(as_global(strand), row)) o[0] = acc[0], o[1] = acc[3], o[2] = acc[1], o[3] = acc[2];  // the complements' counts
+        else o[0] = acc[2], o[1] = acc[1], o[2] = acc[3], o[3] = acc[0];  // A, C, G, T of codes T=0 C=1 A=2 G=3
         o[4] = n_count, o[5] = m_count;
     }
+}
+
+// counts[row] = A, C, G, T, N, masked of [start[row], end[row]) clipped to the sequence; one wave per row
+__global__ __launch_bounds__(TB_WAVE) void tb_composition_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
+                                                                 const int32_t *__restrict__ start, const int32_t *__restrict__ end, int do_mask,
+                                                                 int32_t *__restrict__ counts)
+{
+    tb_composition_body<false>(table, n_tracks, track_of, start, end, nullptr, do_mask, counts);
+}
+
+// the same of the reverse complement where strand[row] is not zero: A, C, G, T of a minus row are T, G, C, A of the plus row
+__global__ __launch_bounds__(TB_WAVE) void tb_composition_strand_kernel(const TbTrack *__restrict__ table, int n_tracks,
+                                                                        const int32_t *__restrict__ track_of, const int32_t *__restrict__ start,
+                                                                        const int32_t *__restrict__ end, const int8_t *__restrict__ strand, int do_mask,
+                                                                        int32_t *__restrict__ counts)
+{
+    tb_composition_body<true>(table, n_tracks, track_of, start, end, strand, do_mask, counts);
 }
 
 }  // namespace bxmi

@@ -36,6 +36,8 @@
  *                                ScoringMatrix.score_string over the sequence of a batch of regions -> bxmi_pwm_*, bxmi_twobit_pwm_*
  *   lib/bx/intseq/ngramcount.pyx:34-85, seqmapping.py:36-48, _seqmapping.pyx:24-67
  *                                count_ngrams(mapping.translate(...)) over the sequence of a batch of regions -> bxmi_twobit_kmer_*
+ *   lib/bx/seq/seq.py:108-109, DNA_COMP at seq.py:9-14
+ *                                SeqFile.reverse_complement: text.translate(DNA_COMP)[::-1] of a row -> bxmi_twobit_*_strand
  *   (intersection.pyx has no C ABI of its own: its cdef classes are the
  *    interface, so the entry points below are what a Cython/ctypes shim of
  *    those classes binds; see INTEGRATION.md.)
@@ -680,6 +682,43 @@ int bxmi_twobit_kmer_counts_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, 
 /* For measurements and tests: how the calls after this one accumulate, whatever csrc/kmer.hpp's km_use_lds would choose -- 0 its
  * choice (the default), 1 the LDS histogram wherever bins allow it, 2 straight to HBM.  The counts are the same. */
 int bxmi_twobit_kmer_force(int way);
+
+/* ---- strand-aware 2bit rows  (lib/bx/seq/seq.py:108-109: reverse_complement = text.translate(DNA_COMP)[::-1], seq.py:9-14) ----
+ * Each call is its unstranded sibling with `strand_or_null` after `start`: int8 [n], 0 = the row as stored (plus), 1 = its reverse
+ * complement (minus).  NULL means all plus and gives exactly what the sibling gives.  For a minus row i of len elements (matrix
+ * form: width; ragged form: row_off[i + 1] - row_off[i]):
+ *   letters   element j is taken at position p = start[i] + (len - 1 - j), in 64 bits.  Where p is in [0, size) of a named track it
+ *             is the COMPLEMENT of the letter the plus call writes for p: A<->T, C<->G, a<->t, c<->g, N->N, n->n (the case follows
+ *             the base; the code is complemented: T=0 C=1 A=2 G=3, code ^ 2).  Elsewhere it is `pad`, untouched: pad is never
+ *             complemented, even if it is a letter.  So a minus row is the plus row reversed and complemented, the pad mirrored.
+ *   counts    A, C, G, T of a minus row are T, G, C, A of the plus row; N and masked are unchanged.
+ *   k-mers    the row's string is the one the stranded letters call gives; everything else of bxmi_twobit_kmer_counts holds as
+ *             written (EVERY window, the first letter least significant, any digits[8]: the table need not be closed under
+ *             complement).  A caller that reproduces the reference's loop (drop_last) drops the last window of the STRAND's string,
+ *             that is, shortens a minus row at its start: start + 1, one element fewer.
+ * Every refusal of the sibling applies unchanged.  The host forms also refuse, with BXMI_EINVAL naming the row, before any device
+ * call and with the output untouched, a strand entry other than 0 or 1.  The device forms take `strand_or_null` as a device pointer
+ * and do not check it, like track_of: ANY NON-ZERO ENTRY IS MINUS.  Track table, scratch, slabs and the one-call-at-a-time rule:
+ * as the siblings.  Strand for the pwm calls is not there yet; it will take this same argument. */
+int bxmi_twobit_bases_strand(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                             const int8_t *strand_or_null, int64_t n, int32_t width,
+                      const int64_t *row_off_or_null, int64_t total, int do_mask, int pad, uint8_t *out);
+int bxmi_twobit_bases_strand_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                 const int8_t *strand_or_null, int64_t n, int32_t width,
+                          const int64_t *row_off_or_null, int64_t total, int do_mask, int pad, uint8_t *out, void *stream);
+int bxmi_twobit_composition_strand(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                   const int8_t *strand_or_null, const int32_t *end,
+                            int64_t n, int do_mask, int32_t *counts);
+int bxmi_twobit_composition_strand_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                       const int8_t *strand_or_null, const int32_t *end,
+                                int64_t n, int do_mask, int32_t *counts, void *stream);
+int bxmi_twobit_kmer_counts_strand(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                   const int8_t *strand_or_null, int64_t n, int32_t width,
+                            const int64_t *row_off_or_null, int64_t total, int do_mask, int k, int radix, const int8_t *digits, int32_t *counts);
+int bxmi_twobit_kmer_counts_strand_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                       const int8_t *strand_or_null, int64_t n, int32_t width,
+                                const int64_t *row_off_or_null, int64_t total, int do_mask, int k, int radix, const int8_t *digits, int32_t *counts,
+                                void *stream);
 
 /* ---- BED text -> SoA columns on the host (the step before the hot path) ------
  * Strict single-pass parser for what lib/bx/bitset_builders.py:33-46 and
