@@ -124,6 +124,12 @@ _SIGNATURES = {
     "bxmi_twobit_composition_strand_dev": [vp, i32, vp, vp, vp, vp, i64, C.c_int, vp, vp],
     "bxmi_twobit_kmer_counts_strand": [vp, i32, vp, vp, vp, i64, i32, vp, i64, C.c_int, C.c_int, C.c_int, vp, vp],
     "bxmi_twobit_kmer_counts_strand_dev": [vp, i32, vp, vp, vp, i64, i32, vp, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp],
+    "bxmi_twobit_pwm_scores_strand": [vp, i32, vp, vp, vp, i64, i32, vp, i64, C.c_int, vp, vp],
+    "bxmi_twobit_pwm_scores_strand_dev": [vp, i32, vp, vp, vp, i64, i32, vp, i64, C.c_int, vp, vp, vp],
+    "bxmi_twobit_pwm_best_strand": [vp, i32, vp, vp, vp, i64, i32, vp, i64, C.c_int, vp, vp, vp],
+    "bxmi_twobit_pwm_best_strand_dev": [vp, i32, vp, vp, vp, i64, i32, vp, i64, C.c_int, vp, vp, vp, vp],
+    "bxmi_twobit_pwm_hits_strand": [vp, i32, vp, vp, vp, i64, i32, vp, i64, C.c_int, vp, vp, i64, vp, vp, vp, vp],
+    "bxmi_twobit_pwm_hits_strand_dev": [vp, i32, vp, vp, vp, i64, i32, vp, i64, C.c_int, vp, vp, i64, vp, vp, vp, vp, vp],
     "bxmi_bits_create": [i64, i64, _p(vp)],
     "bxmi_bits_destroy": [vp],
     "bxmi_bits_info": [vp, _p(i32), _p(i32), _p(i32)],

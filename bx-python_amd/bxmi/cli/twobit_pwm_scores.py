@@ -7,9 +7,13 @@ their sequence; one that is empty, or on a sequence the file does not have, prin
 holds the alphabet's letters on its first line and one row of numbers per matrix position after it.  With -r the reverse
 complement of the matrix is scored as a second matrix.  Masked bases are lower case, and so outside an upper-case alphabet,
 unless -u is given.  With -b one tab-separated line is printed per interval instead: chrom, start, end and, per matrix, the best
-score and the first offset that holds it ("nan" and -1 where nothing could be scored).
+score and the first offset that holds it ("nan" and -1 where nothing could be scored).  With -s column 6 of the BED decides the
+strand (a missing column or "." means "+"): an interval on "-" is scored on its reverse complement, the header line gains the
+strand as a fourth field ("> chrom start end strand"; with -b the line gains it after end), the scores come in the order of the
+strand's string and -b prints the offset in that string.  (-r on a "+" interval is not the same numbers: it adds the same terms in
+the opposite order.)
 
-usage: %prog seq.2bit matrix.txt [-r] [-b] [-u] < bed_file.bed
+usage: %prog seq.2bit matrix.txt [-r] [-b] [-u] [-s] < bed_file.bed
 """
 # The scores are those of the reference's bx.motif.pwm.ScoringMatrix.score_string on each interval's sequence (pwm.py:141-149); here
 # the whole BED file is ONE device call (bxmi.sequence.TwoBitSet.scores / best).  Comment and header lines of the BED are skipped.
@@ -23,7 +27,7 @@ def main(argv=None, stdin=None, out=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     flags = [a for a in argv if a.startswith("-")]
     files = [a for a in argv if not a.startswith("-")]
-    if len(files) != 2 or any(f not in ("-r", "-b", "-u") for f in flags):
+    if len(files) != 2 or any(f not in ("-r", "-b", "-u", "-s") for f in flags):
         sys.exit(__doc__.replace("%prog", "twobit_pwm_scores"))
     out = out or sys.stdout
     with open(files[1]) as f:
@@ -34,15 +38,16 @@ def main(argv=None, stdin=None, out=None):
     try:
         rows, track_of = track_rows(stdin or sys.stdin, genome.tracks)
         starts, ends = [r.start for r in rows], [r.end for r in rows]
+        strands = [r.strand for r in rows] if "-s" in flags else None
         if "-b" in flags:
-            score, pos = genome.best(track_of, starts, ends, matrices)
+            score, pos = genome.best(track_of, starts, ends, matrices, strands)
             for i, r in enumerate(rows):
                 hits = ["%s\t%d" % (repr(float(score[m, i])), pos[m, i]) for m in range(len(matrices))]
-                out.write("\t".join([r.chrom, str(r.start), str(r.end)] + hits) + "\n")
+                out.write("\t".join([r.chrom, str(r.start), str(r.end)] + ([r.strand] if strands is not None else []) + hits) + "\n")
         else:
-            planes, offsets = genome.scores(track_of, starts, ends, matrices)
+            planes, offsets = genome.scores(track_of, starts, ends, matrices, strands)
             for i, r in enumerate(rows):
-                out.write("> %s %d %d\n" % (r.chrom, r.start, r.end))
+                out.write("> %s %d %d%s\n" % (r.chrom, r.start, r.end, " " + r.strand if strands is not None else ""))
                 for m in range(len(matrices)):
                     out.write(" ".join(repr(float(x)) for x in planes[m, offsets[i]:offsets[i + 1]]) + "\n")
         out.flush()

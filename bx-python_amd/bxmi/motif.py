@@ -12,6 +12,12 @@ NaN (numpy's) where a letter of the window has no column -- with the alphabet ``
 ``hits`` lists the offsets whose score reaches a threshold -- a scan -- as (matrix, region, offset, score) in that order, without the
 scores of the other offsets ever being written (``bxmi_twobit_pwm_hits*``; kernels: csrc/pwm_hits.hpp).  The ``_dev`` forms take and
 return torch tensors on the caller's stream.
+
+``strands`` (every function here; None: all plus) scores the minus rows on their reverse complement, the reference's
+``matrix.score_string(seq.get(s, e).translate(DNA_COMP)[::-1])`` bit for bit (``bxmi_twobit_pwm_*_strand``): offsets, the first
+of equal best scores and the order of hits are those of the strand's string, and ``site_starts`` turns such offsets into genomic
+starts.  The reverse-complement matrix on the plus string is a different quantity: the same terms added in the opposite order,
+equal to this one (mirrored) only where every partial sum is exact, as for small integer matrices.
 """
 import ctypes as C
 
@@ -19,7 +25,7 @@ import numpy as np
 
 from . import _ffi
 from ._ffi import as_i32, call, ptr
-from .sequence import _clip, _clip_dev, _record
+from .sequence import _clip, _clip_dev, _record, _strands, _strands_dev
 from .summary import _rows_i32, _Track
 
 LETTERS = "TCAGNtcagn"  # the ten letters a 2bit string can hold, in the order of the handle's letter_col
@@ -99,52 +105,75 @@ class _held:
             self.set.close()
 
 
-def scores(tracks, track_of, starts, ends, pwms, do_mask=True):
+def _stranded(name, strand, args):
+    """the entry point and its arguments: the unstranded call, or its _strand sibling with the strand array after `start`"""
+    if strand is None:
+        return (name,) + tuple(args)
+    head, dev = (name[:-4], "_dev") if name.endswith("_dev") else (name, "")
+    return (head + "_strand" + dev,) + tuple(args[:4]) + (strand.data_ptr() if hasattr(strand, "data_ptr") else ptr(strand),) + tuple(args[4:])
+
+
+def site_starts(starts, lengths, pos, width, strands=None):
+    """The genomic start of the site at offset `pos` of the strand's string of a row that starts at `starts` (after clipping) and
+    holds `lengths` bases, under a matrix of `width` rows: starts + pos on a plus row, starts + lengths - width - pos on a minus
+    row.  Arrays broadcast against the rows; pos < 0 (no scored offset) gives -1.  Pure int64 arithmetic: no device is used."""
+    starts, lengths, pos = (np.asarray(a, dtype=np.int64) for a in (starts, lengths, pos))
+    minus = np.zeros(starts.shape, dtype=bool) if strands is None else _strands(strands, starts.size).astype(bool).reshape(starts.shape)
+    at = np.where(minus, starts + lengths - int(width) - pos, starts + pos)
+    return np.where(pos < 0, -1, at).astype(np.int64)
+
+
+def scores(tracks, track_of, starts, ends, pwms, do_mask=True, strands=None):
     """The scores at every offset of regions [starts[i], ends[i]) of tracks[track_of[i]], clipped as `sequence.sequences` clips
     them -> (float32 [n_mats, total], offsets int64 [n + 1]): row i of plane m is [m, offsets[i]:offsets[i + 1]] and equals
-    pwms[m].score_string(seq.get(start, end)) of the reference.  `pwms`: a MatrixSet, or matrices (put on the device for this call)."""
+    pwms[m].score_string(seq.get(start, end)) of the reference.  `pwms`: a MatrixSet, or matrices (put on the device for this call).
+    A minus row (`strands`) is scored on its reverse complement."""
     _ffi.require_gpu()
     tracks = list(tracks)
     t, s, e = _rows_i32("track_of, starts and ends", track_of, starts, ends)
+    strand = _strands(strands, len(t))
     s64, lengths = _clip([tr.size for tr in tracks], t, s, e)
     offsets = np.zeros(len(s) + 1, dtype=np.int64)
     np.cumsum(lengths, out=offsets[1:])
     with _held(pwms) as ms:
         out = np.empty((ms.n_mats, int(offsets[-1])), dtype=np.float32)
-        call("bxmi_twobit_pwm_scores", _ffi.handles(tracks), len(tracks), ptr(t), ptr(as_i32(s64)), len(t), 0, ptr(offsets), out.shape[1],
-             int(bool(do_mask)), ms._h, ptr(out))
+        call(*_stranded("bxmi_twobit_pwm_scores", strand, (_ffi.handles(tracks), len(tracks), ptr(t), ptr(as_i32(s64)), len(t), 0, ptr(offsets),
+                                                             out.shape[1], int(bool(do_mask)), ms._h, ptr(out))))
     return out, offsets
 
 
-def score_matrix(tracks, track_of, starts, width, pwms, do_mask=True):
+def score_matrix(tracks, track_of, starts, width, pwms, do_mask=True, strands=None):
     """The windows [starts[i], starts[i] + width) of tracks[track_of[i]] -> float32 [n_mats, n, width]; a position outside the
     sequence is unscoreable, as is every position of a row that names no track.  width < 1 raises BxmiError (EINVAL)."""
     _ffi.require_gpu()
     tracks = list(tracks)
     t, s = _rows_i32("track_of and starts", track_of, starts)
+    strand = _strands(strands, len(t))
     width = int(width)
     with _held(pwms) as ms:
         out = np.empty((ms.n_mats, len(t), max(width, 0)), dtype=np.float32)
-        call("bxmi_twobit_pwm_scores", _ffi.handles(tracks), len(tracks), ptr(t), ptr(s), len(t), width, None, len(t) * max(width, 0), int(bool(do_mask)),
-             ms._h, ptr(out))
+        call(*_stranded("bxmi_twobit_pwm_scores", strand, (_ffi.handles(tracks), len(tracks), ptr(t), ptr(s), len(t), width, None, len(t) * max(width, 0),
+                                                             int(bool(do_mask)), ms._h, ptr(out))))
     return out
 
 
-def best(tracks, track_of, starts, ends, pwms, do_mask=True):
+def best(tracks, track_of, starts, ends, pwms, do_mask=True, strands=None):
     """The best hit of every region (clipped as for `scores`) -> (float32 [n_mats, n], int32 [n_mats, n]): the greatest score
     that is not NaN and the first offset within the clipped region that holds it; NaN and -1 where the region has no scored
-    offset.  No per-base output is written anywhere."""
+    offset.  No per-base output is written anywhere.  On a minus row (`strands`) the offset is one of the strand's string, and of
+    equal scores the first THERE wins; `site_starts` gives the genomic start."""
     _ffi.require_gpu()
     tracks = list(tracks)
     t, s, e = _rows_i32("track_of, starts and ends", track_of, starts, ends)
+    strand = _strands(strands, len(t))
     s64, lengths = _clip([tr.size for tr in tracks], t, s, e)
     offsets = np.zeros(len(s) + 1, dtype=np.int64)
     np.cumsum(lengths, out=offsets[1:])
     with _held(pwms) as ms:
         score = np.empty((ms.n_mats, len(t)), dtype=np.float32)
         pos = np.empty((ms.n_mats, len(t)), dtype=np.int32)
-        call("bxmi_twobit_pwm_best", _ffi.handles(tracks), len(tracks), ptr(t), ptr(as_i32(s64)), len(t), 0, ptr(offsets), int(offsets[-1]),
-             int(bool(do_mask)), ms._h, ptr(score), ptr(pos))
+        call(*_stranded("bxmi_twobit_pwm_best", strand, (_ffi.handles(tracks), len(tracks), ptr(t), ptr(as_i32(s64)), len(t), 0, ptr(offsets),
+                                                           int(offsets[-1]), int(bool(do_mask)), ms._h, ptr(score), ptr(pos))))
     return score, pos
 
 
@@ -156,16 +185,18 @@ def _thresholds(thresholds, n_mats):
     return np.ascontiguousarray(np.broadcast_to(t, (n_mats,)))
 
 
-def hits(tracks, track_of, starts, ends, pwms, thresholds, do_mask=True):
+def hits(tracks, track_of, starts, ends, pwms, thresholds, do_mask=True, strands=None):
     """Every offset of regions [starts[i], ends[i]) (clipped as for `scores`) whose score under matrix m is not NaN and is >=
     thresholds[m] (a scalar: one threshold for all) -> (mat_hits int64 [n_mats + 1], rows int32, pos int32, score float32): the
     hits in ascending (matrix, region, offset), matrix m's being [mat_hits[m]:mat_hits[m + 1]] of the three arrays; `pos` is the
     offset within the clipped region, `score` bit for bit the element of `scores`.  In the reference's terms, per matrix and
     region, numpy.nonzero(pwms[m].score_string(seq.get(start, end)) >= thresholds[m]).  No score plane is written anywhere: a
-    call that counts, then a call into arrays of exactly that size."""
+    call that counts, then a call into arrays of exactly that size.  On a minus row (`strands`) `pos` is the offset in the strand's
+    string and the hits of a row ascend in it."""
     _ffi.require_gpu()
     tracks = list(tracks)
     t, s, e = _rows_i32("track_of, starts and ends", track_of, starts, ends)
+    strand = _strands(strands, len(t))
     s64, lengths = _clip([tr.size for tr in tracks], t, s, e)
     offsets = np.zeros(len(s) + 1, dtype=np.int64)
     np.cumsum(lengths, out=offsets[1:])
@@ -173,12 +204,17 @@ def hits(tracks, track_of, starts, ends, pwms, thresholds, do_mask=True):
         least = _thresholds(thresholds, ms.n_mats)
         mat_hits = np.zeros(ms.n_mats + 1, dtype=np.int64)
         rows_of = (_ffi.handles(tracks), len(tracks), ptr(t), ptr(as_i32(s64)), len(t), 0, ptr(offsets), int(offsets[-1]), int(bool(do_mask)), ms._h, ptr(least))
-        call("bxmi_twobit_pwm_hits", *rows_of, 0, ptr(mat_hits), None, None, None, allow=(_ffi.ERANGE,))
+        call(*_stranded("bxmi_twobit_pwm_hits", strand, rows_of + (0, ptr(mat_hits), None, None, None)), allow=(_ffi.ERANGE,))
         found = int(mat_hits[-1])
         rows, pos, score = np.empty(found, dtype=np.int32), np.empty(found, dtype=np.int32), np.empty(found, dtype=np.float32)
         if found:
-            call("bxmi_twobit_pwm_hits", *rows_of, found, ptr(mat_hits), ptr(rows), ptr(pos), ptr(score))
+            call(*_stranded("bxmi_twobit_pwm_hits", strand, rows_of + (found, ptr(mat_hits), ptr(rows), ptr(pos), ptr(score))))
     return mat_hits, rows, pos, score
+
+
+def _copied(strand, strands):
+    """the strand tensor where it is a copy made here (of a non-contiguous one), to be recorded as in use on the stream"""
+    return (strand,) if strand is not None and strand is not strands else ()
 
 
 def _device_set(who, pwms):
@@ -187,7 +223,7 @@ def _device_set(who, pwms):
     return pwms
 
 
-def scores_dev(tracks, track_of, starts, ends, pwms, do_mask=True, stream=None):
+def scores_dev(tracks, track_of, starts, ends, pwms, do_mask=True, stream=None, strands=None):
     """`scores` on device arrays: int32 torch tensors on the GPU in, (float32 [n_mats, total], offsets int64 [n + 1]) tensors out.
     The clipping and the offsets are computed by torch on its current stream and `total` is read back to size the output -- ONE
     synchronisation; the scores are then queued on torch's current stream (or `stream`: the tensors made here are then recorded
@@ -196,23 +232,25 @@ def scores_dev(tracks, track_of, starts, ends, pwms, do_mask=True, stream=None):
 
     tracks, ms = list(tracks), _device_set("scores_dev", pwms)
     (track_of, starts, ends), n, dev, stream = _ffi.device_args("scores_dev", "scores", ("track_of", "starts", "ends"), (track_of, starts, ends), stream)
+    strand = _strands_dev(strands, n, dev, "scores_dev")
     first, offsets = _clip_dev(tracks, track_of, starts, ends, n, dev)
     total = int(offsets[-1].item()) if n else 0  # (the synchronisation: `first` and `offsets` are complete after it)
     out = torch.empty((ms.n_mats, total), dtype=torch.float32, device=dev)
-    call("bxmi_twobit_pwm_scores_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), first.data_ptr(), n, 0, offsets.data_ptr(), total,
-         int(bool(do_mask)), ms._h, out.data_ptr(), stream)
+    call(*_stranded("bxmi_twobit_pwm_scores_dev", strand, (_ffi.handles(tracks), len(tracks), track_of.data_ptr(), first.data_ptr(), n, 0, offsets.data_ptr(),
+                                                             total, int(bool(do_mask)), ms._h, out.data_ptr(), stream)))
     if total:
-        _record(stream, dev, (first, offsets, out))
+        _record(stream, dev, (first, offsets, out) + _copied(strand, strands))
     return out, offsets
 
 
-def score_matrix_dev(tracks, track_of, starts, width, pwms, do_mask=True, stream=None, out=None):
+def score_matrix_dev(tracks, track_of, starts, width, pwms, do_mask=True, stream=None, out=None, strands=None):
     """`score_matrix` on device arrays: the float32 [n_mats, n, width] tensor -- `out` if given (contiguous, on the rows' device),
     else a new one -- queued on torch's current stream (or `stream`), nothing is waited for."""
     import torch
 
     tracks, ms = list(tracks), _device_set("score_matrix_dev", pwms)
     (track_of, starts), n, dev, stream = _ffi.device_args("score_matrix_dev", "score_matrix", ("track_of", "starts"), (track_of, starts), stream)
+    strand = _strands_dev(strands, n, dev, "score_matrix_dev")
     width = int(width)
     shape = (ms.n_mats, n, max(width, 0))
     if out is None:
@@ -222,14 +260,15 @@ def score_matrix_dev(tracks, track_of, starts, width, pwms, do_mask=True, stream
         raise ValueError("out must be a contiguous float32 [n_mats, n, width] tensor on the device of the rows")
     else:
         made = ()
-    call("bxmi_twobit_pwm_scores_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), n, width, None, n * max(width, 0),
-         int(bool(do_mask)), ms._h, out.data_ptr(), stream)
+    call(*_stranded("bxmi_twobit_pwm_scores_dev", strand, (_ffi.handles(tracks), len(tracks), track_of.data_ptr(), starts.data_ptr(), n, width, None,
+                                                             n * max(width, 0), int(bool(do_mask)), ms._h, out.data_ptr(), stream)))
+    made = made + _copied(strand, strands)
     if made and out.numel():
         _record(stream, dev, made)
     return out
 
 
-def best_dev(tracks, track_of, starts, ends, pwms, do_mask=True, stream=None):
+def best_dev(tracks, track_of, starts, ends, pwms, do_mask=True, stream=None, strands=None):
     """`best` on device arrays: (float32 [n_mats, n], int32 [n_mats, n]) tensors, queued on torch's current stream (or `stream`);
     the clipping is torch's, on its current stream, and the host waits for NOTHING: the kernel reads where the rows end from the
     offsets themselves and is given only a bound of it, n times the longest sequence.  Ordering: when `stream` is not torch's
@@ -240,20 +279,21 @@ def best_dev(tracks, track_of, starts, ends, pwms, do_mask=True, stream=None):
 
     tracks, ms = list(tracks), _device_set("best_dev", pwms)
     (track_of, starts, ends), n, dev, stream = _ffi.device_args("best_dev", "best", ("track_of", "starts", "ends"), (track_of, starts, ends), stream)
+    strand = _strands_dev(strands, n, dev, "best_dev")
     first, offsets = _clip_dev(tracks, track_of, starts, ends, n, dev)
     if stream != torch.cuda.current_stream(dev).cuda_stream:  # the kernels read what torch's current stream is still writing
         torch.cuda.ExternalStream(stream, device=dev).wait_stream(torch.cuda.current_stream(dev))
     score = torch.empty((ms.n_mats, n), dtype=torch.float32, device=dev)
     pos = torch.empty((ms.n_mats, n), dtype=torch.int32, device=dev)
     bound = n * max([tr.size for tr in tracks] + [0])
-    call("bxmi_twobit_pwm_best_dev", _ffi.handles(tracks), len(tracks), track_of.data_ptr(), first.data_ptr(), n, 0, offsets.data_ptr(), bound,
-         int(bool(do_mask)), ms._h, score.data_ptr(), pos.data_ptr(), stream)
+    call(*_stranded("bxmi_twobit_pwm_best_dev", strand, (_ffi.handles(tracks), len(tracks), track_of.data_ptr(), first.data_ptr(), n, 0, offsets.data_ptr(),
+                                                           bound, int(bool(do_mask)), ms._h, score.data_ptr(), pos.data_ptr(), stream)))
     if n:
-        _record(stream, dev, (first, offsets, score, pos))
+        _record(stream, dev, (first, offsets, score, pos) + _copied(strand, strands))
     return score, pos
 
 
-def hits_dev(tracks, track_of, starts, ends, pwms, thresholds, do_mask=True, max_hits=None, stream=None):
+def hits_dev(tracks, track_of, starts, ends, pwms, thresholds, do_mask=True, max_hits=None, stream=None, strands=None):
     """`hits` on device arrays: int32 torch tensors on the GPU in -> (mat_hits int64 [n_mats + 1], a HOST numpy array; rows int32,
     pos int32, score float32 tensors on the device).  The clipping is torch's and its total is read back (one synchronisation);
     the call itself waits once more, for the counts.  With `max_hits` the hits go into tensors of that capacity in ONE call -- two
@@ -265,12 +305,13 @@ def hits_dev(tracks, track_of, starts, ends, pwms, thresholds, do_mask=True, max
     tracks, ms = list(tracks), _device_set("hits_dev", pwms)
     (track_of, starts, ends), n, dev, stream = _ffi.device_args("hits_dev", "hits", ("track_of", "starts", "ends"), (track_of, starts, ends), stream)
     least = _thresholds(thresholds, ms.n_mats)
+    strand = _strands_dev(strands, n, dev, "hits_dev")
     first, offsets = _clip_dev(tracks, track_of, starts, ends, n, dev)
     total = int(offsets[-1].item()) if n else 0  # (the synchronisation: `first` and `offsets` are complete after it)
     mat_hits = np.zeros(ms.n_mats + 1, dtype=np.int64)
     rows_of = (_ffi.handles(tracks), len(tracks), track_of.data_ptr(), first.data_ptr(), n, 0, offsets.data_ptr(), total, int(bool(do_mask)), ms._h, ptr(least))
     if max_hits is None:
-        call("bxmi_twobit_pwm_hits_dev", *rows_of, 0, ptr(mat_hits), None, None, None, stream, allow=(_ffi.ERANGE,))
+        call(*_stranded("bxmi_twobit_pwm_hits_dev", strand, rows_of + (0, ptr(mat_hits), None, None, None, stream)), allow=(_ffi.ERANGE,))
         cap = int(mat_hits[-1])
     else:
         cap = int(max_hits)
@@ -281,13 +322,13 @@ def hits_dev(tracks, track_of, starts, ends, pwms, thresholds, do_mask=True, max
     score = torch.empty(cap, dtype=torch.float32, device=dev)
     if cap or max_hits is not None:
         try:
-            call("bxmi_twobit_pwm_hits_dev", *rows_of, cap, ptr(mat_hits), rows.data_ptr() if cap else None, pos.data_ptr() if cap else None,
-                 score.data_ptr() if cap else None, stream)
+            call(*_stranded("bxmi_twobit_pwm_hits_dev", strand, rows_of + (cap, ptr(mat_hits), rows.data_ptr() if cap else None,
+                                                                   pos.data_ptr() if cap else None, score.data_ptr() if cap else None, stream)))
         except _ffi.BxmiError as err:
             if err.code == _ffi.ERANGE:
                 raise _ffi.BxmiError(err.code, "%s (max_hits = %d; hits per matrix: %s)" % (err, cap, np.diff(mat_hits).tolist())) from None
             raise
     found = int(mat_hits[-1])
     if total:
-        _record(stream, dev, (first, offsets, rows, pos, score))
+        _record(stream, dev, (first, offsets, rows, pos, score) + _copied(strand, strands))
     return mat_hits, rows[:found], pos[:found], score[:found]

@@ -323,45 +323,45 @@ class TwoBitSet:
 
     # position weight matrices over the rows (bxmi.motif, which builds on this module); `pwms`: a motif.MatrixSet, for the host
     # forms also a list of motif.ScoringMatrix
-    def scores(self, chroms, starts, ends, pwms):
+    def scores(self, chroms, starts, ends, pwms, strands=None):
         from . import motif
 
-        return motif.scores(self.tracks.values(), self._track_of(chroms), starts, ends, pwms, self.do_mask)
+        return motif.scores(self.tracks.values(), self._track_of(chroms), starts, ends, pwms, self.do_mask, strands)
 
-    def score_matrix(self, chroms, starts, width, pwms):
+    def score_matrix(self, chroms, starts, width, pwms, strands=None):
         from . import motif
 
-        return motif.score_matrix(self.tracks.values(), self._track_of(chroms), starts, width, pwms, self.do_mask)
+        return motif.score_matrix(self.tracks.values(), self._track_of(chroms), starts, width, pwms, self.do_mask, strands)
 
-    def best(self, chroms, starts, ends, pwms):
+    def best(self, chroms, starts, ends, pwms, strands=None):
         from . import motif
 
-        return motif.best(self.tracks.values(), self._track_of(chroms), starts, ends, pwms, self.do_mask)
+        return motif.best(self.tracks.values(), self._track_of(chroms), starts, ends, pwms, self.do_mask, strands)
 
-    def scores_dev(self, track_of, starts, ends, pwms, stream=None):
+    def scores_dev(self, track_of, starts, ends, pwms, stream=None, strands=None):
         from . import motif
 
-        return motif.scores_dev(self.tracks.values(), track_of, starts, ends, pwms, self.do_mask, stream)
+        return motif.scores_dev(self.tracks.values(), track_of, starts, ends, pwms, self.do_mask, stream, strands)
 
-    def score_matrix_dev(self, track_of, starts, width, pwms, stream=None, out=None):
+    def score_matrix_dev(self, track_of, starts, width, pwms, stream=None, out=None, strands=None):
         from . import motif
 
-        return motif.score_matrix_dev(self.tracks.values(), track_of, starts, width, pwms, self.do_mask, stream, out)
+        return motif.score_matrix_dev(self.tracks.values(), track_of, starts, width, pwms, self.do_mask, stream, out, strands)
 
-    def best_dev(self, track_of, starts, ends, pwms, stream=None):
+    def best_dev(self, track_of, starts, ends, pwms, stream=None, strands=None):
         from . import motif
 
-        return motif.best_dev(self.tracks.values(), track_of, starts, ends, pwms, self.do_mask, stream)
+        return motif.best_dev(self.tracks.values(), track_of, starts, ends, pwms, self.do_mask, stream, strands)
 
-    def hits(self, chroms, starts, ends, pwms, thresholds):
+    def hits(self, chroms, starts, ends, pwms, thresholds, strands=None):
         from . import motif
 
-        return motif.hits(self.tracks.values(), self._track_of(chroms), starts, ends, pwms, thresholds, self.do_mask)
+        return motif.hits(self.tracks.values(), self._track_of(chroms), starts, ends, pwms, thresholds, self.do_mask, strands)
 
-    def hits_dev(self, track_of, starts, ends, pwms, thresholds, max_hits=None, stream=None):
+    def hits_dev(self, track_of, starts, ends, pwms, thresholds, max_hits=None, stream=None, strands=None):
         from . import motif
 
-        return motif.hits_dev(self.tracks.values(), track_of, starts, ends, pwms, thresholds, self.do_mask, max_hits, stream)
+        return motif.hits_dev(self.tracks.values(), track_of, starts, ends, pwms, thresholds, self.do_mask, max_hits, stream, strands)
 
     # the k-mer spectrum of the rows (bxmi.kmers, which builds on this module)
     def kmer_counts(self, chroms, starts, ends, k, alphabet="ACGT", case_sensitive=True, drop_last=False, strands=None):

@@ -15,7 +15,7 @@
 //   pw_scores_kernel   the work is cut on the flat OUTPUT axis as in tb_bases_kernel: workgroup t owns elements [t * PW_TILE,
 //                      (t + 1) * PW_TILE) of every plane, thread k of it the 4 consecutive elements from 4 k.  A tile is walked ROW
 //                      SEGMENT by row segment; everything about a segment is uniform over the workgroup.  Per segment the workgroup
-//                      stages the column (int8, -1: unscoreable) of the segment's positions and of a halo of max width - 1 positions
+//                      stages (pw_stage_columns) the column (int8, -1: unscoreable) of the segment's positions and of a halo of max width - 1 positions
 //                      beyond its end into LDS, 8 positions per thread from at most two packed words and the staged block runs
 //                      (tb_covered), one 8-byte LDS store each; positions past the row's end or outside the sequence are -1, so a
 //                      window that leaves the row meets a -1.  Then, matrix after matrix, every thread walks the W + 3 columns under
@@ -30,6 +30,15 @@
 //                      per (segment, matrix).  A NaN score is never a candidate; every candidate's key is above 0, the value the keys
 //                      start from.  A chain started from +0.0f never gives -0.0f (x + y is -0 only when both are), so equal scores
 //                      have equal bits.  pw_unpack_kernel turns keys into best_score / best_pos: NaN and -1 for a key of 0.
+//   strand             pw_scores_strand_kernel<BEST> (and pw_hits_strand_kernel<FILL> of pwm_hits.hpp) take a strand per row: a minus
+//                      row is scored on its reverse complement (the reference's matrix.score_string(text.translate(DNA_COMP)[::-1]),
+//                      lib/bx/seq/seq.py:108-109), offsets, ties and the order of hits being those of that string.  Strand sits in
+//                      pw_stage_columns<STRAND>, the one staging of both headers, and nowhere else: it decides which column lands
+//                      where in l_col.  Everything behind the staging barrier -- the window walk, the order of every accumulator's
+//                      additions, the 16-byte store rule, the keys, the ranks -- is the same text for both strands, so a minus row's
+//                      chain is ascending in the matrix's rows over the strand's letters, NOT the reverse-complement matrix's chain
+//                      on the plus string read backwards.  Each kernel's text is a body templated on STRAND with two thin wrappers;
+//                      the unstranded kernels are the STRAND == false instantiations.  Rows of both strands share a tile.
 #pragma once
 
 #include "twobit.hpp"
@@ -80,21 +89,112 @@ __device__ __forceinline__ unsigned long long pw_wave_max64(unsigned long long k
 #define PW_ATOMIC_MAX64(at, key) atomicMax(at, key)
 #endif
 
-// track_of, start, row_off, row_base, width, o_first, count: as tb_bases_kernel.  `out` is the address of element o_first of plane
-// 0, plane m lies plane_stride elements after plane m - 1.  BEST: nothing is stored; keys is [n_mats][key_rows], row r of the rows
-// given is entry r (the launch is given the whole batch: row_base == 0).
-template <bool BEST>
-__global__ __launch_bounds__(PW_THREADS) void pw_scores_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
-                                                               const int32_t *__restrict__ start, int64_t n_rows, int64_t row_base, int width,
-                                                               const int64_t *__restrict__ row_off, int64_t o_first, int64_t count, int do_mask,
-                                                               PwSet pw, float *__restrict__ out, int64_t plane_stride,
-                                                               unsigned long long *__restrict__ keys, int64_t key_rows)
+// The int8 columns (-1: unscoreable) of the segment [o, seg1) of a row [r_lo, r_hi) and of a halo of max width - 1 letters behind it, in
+// the order of the row's strand, into l_col; n_stage, the number of columns staged, is returned.  The row names track `t` and starts at
+// `start`.  Staged column k is offset (o - r_lo) + k of the strand's string:
+//   plus    position start + (o - r_lo) + k: the halo lies beyond the segment and ends at the row's end;
+//   minus   position start + (r_hi - r_lo) - 1 - (o - r_lo) - k, in 64 bits, its class complemented (tb_complement: N and the case
+//           are their own complements) BEFORE the `letters` lookup: the halo lies at lower positions and ends at the row's start.
+// Either way the staged positions are one ascending run [p0, p0 + n_stage) of which [c0, c1) are letters of the row inside the
+// sequence, a thread owns 8 consecutive ascending positions from `mine` in at most two packed words, the two searches per block list
+// go over [c0, c1), and the thread makes one 8-byte LDS store: on a minus row its columns byte-reversed, at the mirrored place.
+// The loads, the searches and the chunk walk are the text this kernel always had (on tb_block_bits and tb_codes of twobit.hpp the
+// unstranded kernels measured 1 - 3 % slower); tb_minus, tb_complement, tb_code and tb_covered are twobit.hpp's.
+// Every thread of the workgroup calls this with the same arguments but tid: it holds barriers, the last of them after the stores.
+template <bool STRAND>
+__device__ __forceinline__ int pw_stage_columns(const TbTrack *__restrict__ table, int n_tracks, int t, int start, bool minus, int64_t r_lo, int64_t r_hi,
+                                                int64_t o, int64_t seg1, int do_mask, const PwSet &pw, int tid, int32_t *l_st, int32_t *l_en, int8_t *l_col)
+{
+    const int seg_len = (int)(seg1 - o);
+    const int n_stage = seg_len + pw.max_width - 1;  // the segment and its halo: at most PW_STAGE - 1
+    const bool named = t >= 0 && t < n_tracks;
+    const TbTrack tr = table[named ? t : n_tracks];  // (the spare entry: size 0)
+    const bool mirror = STRAND && minus;
+    // the staged positions that are letters of the row: inside the row, inside the sequence
+    int64_t p0, c0, c1, mine;  // mine: the first of this thread's 8 positions
+    if (mirror) {
+        c1 = (int64_t)start + (r_hi - r_lo) - (o - r_lo);  // one past the position of staged column 0
+        p0 = c1 - n_stage;
+        mine = c1 - 8 - 8 * tid;
+        c0 = p0 > (int64_t)start ? p0 : (int64_t)start;
+        if (c0 < 0) c0 = 0;
+        if (c1 > tr.size) c1 = tr.size;
+    } else {
+        p0 = (int64_t)start + (o - r_lo);  // the position of staged column 0
+        mine = p0 + 8 * tid;
+        c1 = p0 + n_stage;
+        if (c1 > (int64_t)start + (r_hi - r_lo)) c1 = (int64_t)start + (r_hi - r_lo);
+        if (c1 > tr.size) c1 = tr.size;
+        c0 = p0 > 0 ? p0 : 0;
+    }
+    unsigned long long cols = ~0ull;  // this thread's 8 staged columns, -1 each
+    const bool stages = 8 * tid < n_stage;
+    if (c0 < c1) {
+        // this thread's staged positions that are letters: [pf, pf + cnt), places [qa, qa + cnt) of its 8 ascending positions
+        const int64_t lo_p = mine > c0 ? mine : c0, hi_p = mine + 8 < c1 ? mine + 8 : c1;
+        const int cnt = stages && lo_p < hi_p ? (int)(hi_p - lo_p) : 0;
+        const int qa = cnt ? (int)(lo_p - mine) : 0, pf = cnt ? (int)lo_p : 0;
+        uint64_t codes = 0;  // base pf + i at bits 63 - 2 (b + i) .. 62 - 2 (b + i), b = pf & 15
+        if (cnt) {
+            const uint32_t BX_GLOBAL *packed = as_global(tr.packed);
+            const int64_t w = pf >> 4;
+            codes = (uint64_t)tb_word(packed, w) << 32;
+            if (((pf + cnt - 1) >> 4) > w) codes |= tb_word(packed, w + 1);
+        }
+        unsigned is_n = 0, is_m = 0;
+        for (int list = 0; list < (do_mask ? 2 : 1); list++) {
+            const int64_t blocks = list ? tr.m_blocks : tr.n_blocks;
+            if (blocks == 0) continue;
+            const int32_t BX_GLOBAL *b_st = as_global(list ? tr.m_start : tr.n_start), *b_en = as_global(list ? tr.m_end : tr.n_end);
+            const int64_t lo = sm_first_above(b_en, 0, blocks, (int)c0);        // the first block that ends after the staged letters start
+            const int64_t hi = sm_first_above(b_st, lo, blocks, (int)(c1 - 1));  // the first that starts at or after their end
+            unsigned bits = 0;
+            for (int64_t at = lo; at < hi; at += TB_CHUNK) {
+                const int staged = hi - at < TB_CHUNK ? (int)(hi - at) : TB_CHUNK;
+                __syncthreads();  // the previous chunk has been searched
+                for (int k = tid; k < staged; k += PW_THREADS) {
+                    l_st[k] = b_st[at + k];
+                    l_en[k] = b_en[at + k];
+                }
+                __syncthreads();
+                if (cnt) bits |= tb_covered(l_st, l_en, staged, pf, cnt);
+            }
+            if (list) is_m = bits;
+            else is_n = bits;
+        }
+        const int b = pf & 15;
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int i = q - qa;  // the letter's place among this thread's
+            if (i < 0 || i >= cnt) continue;
+            const unsigned code = tb_complement(tb_code(codes, b + i), mirror);
+            const unsigned cls = ((is_n >> i) & 1u ? 4u : code) + ((is_m >> i) & 1u ? 5u : 0u);
+            const unsigned long long col = ((pw.letters >> (5 * cls)) & 31ull) - 1ull;  // (-1: all ones)
+            const int at = mirror ? 7 - q : q;  // the staged column among this thread's 8
+            cols = (cols & ~(0xFFull << (8 * at))) | ((col & 0xFFull) << (8 * at));
+        }
+    }
+    __syncthreads();  // the previous segment's windows have been read (and, the first time, the resident values are staged)
+    if (stages) __builtin_memcpy(l_col + 8 * tid, &cols, 8);
+    __syncthreads();
+    return n_stage;
+}
+
+// The text of pw_scores_kernel (STRAND == false: `strand` is not read) and of pw_scores_strand_kernel (STRAND == true: strand[r] of
+// the rows given).  Strand changes which column lands where in l_col, and nothing after the staging barrier: an element's offset
+// e - r_lo is its offset in the strand's string.
+template <bool STRAND, bool BEST>
+__device__ __forceinline__ void pw_scores_body(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
+                                               const int32_t *__restrict__ start, const int8_t *__restrict__ strand, int64_t n_rows, int64_t row_base,
+                                               int width, const int64_t *__restrict__ row_off, int64_t o_first, int64_t count, int do_mask, PwSet pw,
+                                               float *__restrict__ out, int64_t plane_stride, unsigned long long *__restrict__ keys, int64_t key_rows)
 {
     __shared__ int32_t l_st[TB_CHUNK], l_en[TB_CHUNK];
     __shared__ int8_t l_col[PW_STAGE] __attribute__((aligned(8)));
     __shared__ float l_val[PW_LDS_VALUES];
     const int tid = (int)threadIdx.x;
     const int32_t BX_GLOBAL *g_track = as_global(track_of), *g_start = as_global(start);
+    const int8_t BX_GLOBAL *g_strand = as_global(strand);
     const int64_t BX_GLOBAL *g_off = as_global(row_off);
     const float BX_GLOBAL *g_val = as_global(pw.values);
     const int32_t BX_GLOBAL *g_mat = as_global(pw.mat_off);
@@ -125,67 +225,8 @@ __global__ __launch_bounds__(PW_THREADS) void pw_scores_kernel(const TbTrack *__
             }
             int64_t seg1 = r_hi < t1 ? r_hi : t1;
             if (seg1 <= o) seg1 = o + 1;  // (offsets that are not what they should be: the walk still ends)
-            const int seg_len = (int)(seg1 - o);
-            const int n_stage = seg_len + pw.max_width - 1;  // the segment and its halo: at most PW_STAGE - 1
-            const int t = g_track[r];
-            const bool named = t >= 0 && t < n_tracks;
-            const TbTrack tr = table[named ? t : n_tracks];  // (the spare entry: size 0)
-            const int64_t p0 = (int64_t)g_start[r] + (o - r_lo);  // the position of staged column 0
-            // the staged positions that are letters of the row: inside the row, inside the sequence
-            int64_t c1 = p0 + n_stage;
-            if (c1 > (int64_t)g_start[r] + (r_hi - r_lo)) c1 = (int64_t)g_start[r] + (r_hi - r_lo);
-            if (c1 > tr.size) c1 = tr.size;
-            const int64_t c0 = p0 > 0 ? p0 : 0;
-            unsigned long long cols = ~0ull;  // this thread's 8 staged columns, -1 each
-            const bool stages = 8 * tid < n_stage;
-            if (c0 < c1) {
-                // this thread's staged positions that are letters: [pf, pf + cnt), columns [qa, qa + cnt) of its 8
-                const int64_t mine = p0 + 8 * tid;
-                const int64_t lo_p = mine > c0 ? mine : c0, hi_p = mine + 8 < c1 ? mine + 8 : c1;
-                const int cnt = stages && lo_p < hi_p ? (int)(hi_p - lo_p) : 0;
-                const int qa = cnt ? (int)(lo_p - mine) : 0, pf = cnt ? (int)lo_p : 0;
-                uint64_t codes = 0;  // base pf + i at bits 63 - 2 (b + i) .. 62 - 2 (b + i), b = pf & 15
-                if (cnt) {
-                    const uint32_t BX_GLOBAL *packed = as_global(tr.packed);
-                    const int64_t w = pf >> 4;
-                    codes = (uint64_t)tb_word(packed, w) << 32;
-                    if (((pf + cnt - 1) >> 4) > w) codes |= tb_word(packed, w + 1);
-                }
-                unsigned is_n = 0, is_m = 0;
-                for (int list = 0; list < (do_mask ? 2 : 1); list++) {
-                    const int64_t blocks = list ? tr.m_blocks : tr.n_blocks;
-                    if (blocks == 0) continue;
-                    const int32_t BX_GLOBAL *b_st = as_global(list ? tr.m_start : tr.n_start), *b_en = as_global(list ? tr.m_end : tr.n_end);
-                    const int64_t lo = sm_first_above(b_en, 0, blocks, (int)c0);        // the first block that ends after the staged letters start
-                    const int64_t hi = sm_first_above(b_st, lo, blocks, (int)(c1 - 1));  // the first that starts at or after their end
-                    unsigned bits = 0;
-                    for (int64_t at = lo; at < hi; at += TB_CHUNK) {
-                        const int staged = hi - at < TB_CHUNK ? (int)(hi - at) : TB_CHUNK;
-                        __syncthreads();  // the previous chunk has been searched
-                        for (int k = tid; k < staged; k += PW_THREADS) {
-                            l_st[k] = b_st[at + k];
-                            l_en[k] = b_en[at + k];
-                        }
-                        __syncthreads();
-                        if (cnt) bits |= tb_covered(l_st, l_en, staged, pf, cnt);
-                    }
-                    if (list) is_m = bits;
-                    else is_n = bits;
-                }
-                const int b = pf & 15;
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const int i = q - qa;  // the letter's place among this thread's
-                    if (i < 0 || i >= cnt) continue;
-                    const unsigned code = (unsigned)(codes >> (62 - 2 * (b + i))) & 3u;
-                    const unsigned cls = ((is_n >> i) & 1u ? 4u : code) + ((is_m >> i) & 1u ? 5u : 0u);
-                    const unsigned long long col = ((pw.letters >> (5 * cls)) & 31ull) - 1ull;  // (-1: all ones)
-                    cols = (cols & ~(0xFFull << (8 * q))) | ((col & 0xFFull) << (8 * q));
-                }
-            }
-            __syncthreads();  // the previous segment's windows have been read (and, the first time, the resident values are staged)
-            if (stages) __builtin_memcpy(l_col + 8 * tid, &cols, 8);
-            __syncthreads();
+            const int n_stage = pw_stage_columns<STRAND>(table, n_tracks, g_track[r], g_start[r], tb_minus<STRAND>(g_strand, r), r_lo, r_hi, o, seg1, do_mask,
+                                                         pw, tid, l_st, l_en, l_col);
             // this thread's elements of the segment
             unsigned act = 0;
 #pragma unroll
@@ -246,6 +287,32 @@ __global__ __launch_bounds__(PW_THREADS) void pw_scores_kernel(const TbTrack *__
             o = seg1;
         }
     }
+}
+
+// track_of, start, row_off, row_base, width, o_first, count: as tb_bases_kernel.  `out` is the address of element o_first of plane
+// 0, plane m lies plane_stride elements after plane m - 1.  BEST: nothing is stored; keys is [n_mats][key_rows], row r of the rows
+// given is entry r (the launch is given the whole batch: row_base == 0).
+template <bool BEST>
+__global__ __launch_bounds__(PW_THREADS) void pw_scores_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
+                                                               const int32_t *__restrict__ start, int64_t n_rows, int64_t row_base, int width,
+                                                               const int64_t *__restrict__ row_off, int64_t o_first, int64_t count, int do_mask,
+                                                               PwSet pw, float *__restrict__ out, int64_t plane_stride,
+                                                               unsigned long long *__restrict__ keys, int64_t key_rows)
+{
+    pw_scores_body<false, BEST>(table, n_tracks, track_of, start, nullptr, n_rows, row_base, width, row_off, o_first, count, do_mask, pw, out, plane_stride,
+                                keys, key_rows);
+}
+
+// the same with strand[n_rows] of the rows given: any non-zero entry is a minus row, whose string is the reverse complement
+template <bool BEST>
+__global__ __launch_bounds__(PW_THREADS) void pw_scores_strand_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
+                                                                      const int32_t *__restrict__ start, const int8_t *__restrict__ strand, int64_t n_rows,
+                                                                      int64_t row_base, int width, const int64_t *__restrict__ row_off, int64_t o_first,
+                                                                      int64_t count, int do_mask, PwSet pw, float *__restrict__ out, int64_t plane_stride,
+                                                                      unsigned long long *__restrict__ keys, int64_t key_rows)
+{
+    pw_scores_body<true, BEST>(table, n_tracks, track_of, start, strand, n_rows, row_base, width, row_off, o_first, count, do_mask, pw, out, plane_stride,
+                               keys, key_rows);
 }
 
 // best_score[i], best_pos[i] of keys[i], i in [0, count): NaN and -1 where no element of the row was scored

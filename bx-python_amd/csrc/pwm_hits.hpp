@@ -10,8 +10,8 @@
 //
 //   pw_hits_kernel<FILL>   the cut of pw_scores_kernel: tiles of PW_TILE elements of the flat output axis, four consecutive
 //                          elements per thread, a tile walked row segment by row segment, the columns of the segment and its halo
-//                          staged in LDS, every accumulator in ascending j from +0.0f.  (The staging and the window walk stand
-//                          here a second time: pwm.hpp is as it was.)  A workgroup takes every gridDim.x-th tile of the launch's
+//                          staged in LDS by pw_stage_columns of pwm.hpp, every accumulator in ascending j from +0.0f.  (The
+//                          window walk stands here a second time.)  A workgroup takes every gridDim.x-th tile of the launch's
 //                          [tile_first, tile_first + tile_count).
 //     FILL == false        counts: per (segment, matrix) the workgroup's hits are summed -- a wave prefix over the threads' 0 .. 4
 //                          hits (PH_WAVE_PREFIX), the four waves' totals through LDS -- into a running count per matrix in LDS,
@@ -62,16 +62,14 @@ inline int ph_each_launch(int64_t tiles, int64_t per_launch, int64_t fill, Launc
     return 0;
 }
 
-// track_of, start, row_off, width: the whole batch, as pw_scores_kernel<true> is given it; `total` is exact.  tiles ==
-// ceil(total / PW_TILE) is the stride of counts and bases.  FILL: counts is read; else it is written and bases and the hit arrays
-// are not used.
-template <bool FILL>
-__global__ __launch_bounds__(PW_THREADS) void pw_hits_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
-                                                             const int32_t *__restrict__ start, int64_t n_rows, int width,
-                                                             const int64_t *__restrict__ row_off, int64_t total, int do_mask, PwSet pw, PhThresholds thr,
-                                                             int64_t tile_first, int64_t tile_count, int64_t tiles, int32_t *counts,
-                                                             const int64_t *__restrict__ bases, int32_t *__restrict__ hit_row, int32_t *__restrict__ hit_pos,
-                                                             float *__restrict__ hit_score)
+// The text of pw_hits_kernel (STRAND == false: `strand` is not read) and of pw_hits_strand_kernel (STRAND == true: strand[n_rows],
+// any non-zero entry a minus row).  The staging is pw_stage_columns of pwm.hpp; hit_pos is the offset in the strand's string.
+template <bool STRAND, bool FILL>
+__device__ __forceinline__ void pw_hits_body(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
+                                             const int32_t *__restrict__ start, const int8_t *__restrict__ strand, int64_t n_rows, int width,
+                                             const int64_t *__restrict__ row_off, int64_t total, int do_mask, PwSet pw, PhThresholds thr, int64_t tile_first,
+                                             int64_t tile_count, int64_t tiles, int32_t *counts, const int64_t *__restrict__ bases,
+                                             int32_t *__restrict__ hit_row, int32_t *__restrict__ hit_pos, float *__restrict__ hit_score)
 {
     __shared__ int32_t l_st[TB_CHUNK], l_en[TB_CHUNK];
     __shared__ int8_t l_col[PW_STAGE] __attribute__((aligned(8)));
@@ -80,6 +78,7 @@ __global__ __launch_bounds__(PW_THREADS) void pw_hits_kernel(const TbTrack *__re
     __shared__ int32_t l_wave[2][PW_THREADS / 64];
     const int tid = (int)threadIdx.x;
     const int32_t BX_GLOBAL *g_track = as_global(track_of), *g_start = as_global(start);
+    const int8_t BX_GLOBAL *g_strand = as_global(strand);
     const int64_t BX_GLOBAL *g_off = as_global(row_off);
     const float BX_GLOBAL *g_val = as_global(pw.values);
     const int32_t BX_GLOBAL *g_mat = as_global(pw.mat_off);
@@ -114,67 +113,8 @@ __global__ __launch_bounds__(PW_THREADS) void pw_hits_kernel(const TbTrack *__re
             }
             int64_t seg1 = r_hi < t1 ? r_hi : t1;
             if (seg1 <= o) seg1 = o + 1;  // (offsets that are not what they should be: the walk still ends)
-            const int seg_len = (int)(seg1 - o);
-            const int n_stage = seg_len + pw.max_width - 1;  // the segment and its halo: at most PW_STAGE - 1
-            const int t = g_track[r];
-            const bool named = t >= 0 && t < n_tracks;
-            const TbTrack tr = table[named ? t : n_tracks];  // (the spare entry: size 0)
-            const int64_t p0 = (int64_t)g_start[r] + (o - r_lo);  // the position of staged column 0
-            // the staged positions that are letters of the row: inside the row, inside the sequence
-            int64_t c1 = p0 + n_stage;
-            if (c1 > (int64_t)g_start[r] + (r_hi - r_lo)) c1 = (int64_t)g_start[r] + (r_hi - r_lo);
-            if (c1 > tr.size) c1 = tr.size;
-            const int64_t c0 = p0 > 0 ? p0 : 0;
-            unsigned long long cols = ~0ull;  // this thread's 8 staged columns, -1 each
-            const bool stages = 8 * tid < n_stage;
-            if (c0 < c1) {
-                // this thread's staged positions that are letters: [pf, pf + cnt), columns [qa, qa + cnt) of its 8
-                const int64_t mine = p0 + 8 * tid;
-                const int64_t lo_p = mine > c0 ? mine : c0, hi_p = mine + 8 < c1 ? mine + 8 : c1;
-                const int cnt = stages && lo_p < hi_p ? (int)(hi_p - lo_p) : 0;
-                const int qa = cnt ? (int)(lo_p - mine) : 0, pf = cnt ? (int)lo_p : 0;
-                uint64_t codes = 0;  // base pf + i at bits 63 - 2 (b + i) .. 62 - 2 (b + i), b = pf & 15
-                if (cnt) {
-                    const uint32_t BX_GLOBAL *packed = as_global(tr.packed);
-                    const int64_t w = pf >> 4;
-                    codes = (uint64_t)tb_word(packed, w) << 32;
-                    if (((pf + cnt - 1) >> 4) > w) codes |= tb_word(packed, w + 1);
-                }
-                unsigned is_n = 0, is_m = 0;
-                for (int list = 0; list < (do_mask ? 2 : 1); list++) {
-                    const int64_t blocks = list ? tr.m_blocks : tr.n_blocks;
-                    if (blocks == 0) continue;
-                    const int32_t BX_GLOBAL *b_st = as_global(list ? tr.m_start : tr.n_start), *b_en = as_global(list ? tr.m_end : tr.n_end);
-                    const int64_t lo = sm_first_above(b_en, 0, blocks, (int)c0);        // the first block that ends after the staged letters start
-                    const int64_t hi = sm_first_above(b_st, lo, blocks, (int)(c1 - 1));  // the first that starts at or after their end
-                    unsigned bits = 0;
-                    for (int64_t at = lo; at < hi; at += TB_CHUNK) {
-                        const int staged = hi - at < TB_CHUNK ? (int)(hi - at) : TB_CHUNK;
-                        __syncthreads();  // the previous chunk has been searched
-                        for (int k = tid; k < staged; k += PW_THREADS) {
-                            l_st[k] = b_st[at + k];
-                            l_en[k] = b_en[at + k];
-                        }
-                        __syncthreads();
-                        if (cnt) bits |= tb_covered(l_st, l_en, staged, pf, cnt);
-                    }
-                    if (list) is_m = bits;
-                    else is_n = bits;
-                }
-                const int b = pf & 15;
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const int i = q - qa;  // the letter's place among this thread's
-                    if (i < 0 || i >= cnt) continue;
-                    const unsigned code = (unsigned)(codes >> (62 - 2 * (b + i))) & 3u;
-                    const unsigned cls = ((is_n >> i) & 1u ? 4u : code) + ((is_m >> i) & 1u ? 5u : 0u);
-                    const unsigned long long col = ((pw.letters >> (5 * cls)) & 31ull) - 1ull;  // (-1: all ones)
-                    cols = (cols & ~(0xFFull << (8 * q))) | ((col & 0xFFull) << (8 * q));
-                }
-            }
-            __syncthreads();  // the previous segment's windows have been read (and, the first time, the resident values are staged)
-            if (stages) __builtin_memcpy(l_col + 8 * tid, &cols, 8);
-            __syncthreads();
+            const int n_stage = pw_stage_columns<STRAND>(table, n_tracks, g_track[r], g_start[r], tb_minus<STRAND>(g_strand, r), r_lo, r_hi, o, seg1, do_mask,
+                                                         pw, tid, l_st, l_en, l_col);
             // this thread's elements of the segment
             unsigned act = 0;
 #pragma unroll
@@ -244,6 +184,34 @@ __global__ __launch_bounds__(PW_THREADS) void pw_hits_kernel(const TbTrack *__re
         __syncthreads();  // the last step's running counts are written; the next tile begins them anew
         if (!FILL && tid < pw.n_mats) as_global(counts)[(int64_t)tid * tiles + tile] = l_run[tid];
     }
+}
+
+// track_of, start, row_off, width: the whole batch, as pw_scores_kernel<true> is given it; `total` is exact.  tiles ==
+// ceil(total / PW_TILE) is the stride of counts and bases.  FILL: counts is read; else it is written and bases and the hit arrays
+// are not used.
+template <bool FILL>
+__global__ __launch_bounds__(PW_THREADS) void pw_hits_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
+                                                             const int32_t *__restrict__ start, int64_t n_rows, int width,
+                                                             const int64_t *__restrict__ row_off, int64_t total, int do_mask, PwSet pw, PhThresholds thr,
+                                                             int64_t tile_first, int64_t tile_count, int64_t tiles, int32_t *counts,
+                                                             const int64_t *__restrict__ bases, int32_t *__restrict__ hit_row, int32_t *__restrict__ hit_pos,
+                                                             float *__restrict__ hit_score)
+{
+    pw_hits_body<false, FILL>(table, n_tracks, track_of, start, nullptr, n_rows, width, row_off, total, do_mask, pw, thr, tile_first, tile_count, tiles, counts,
+                              bases, hit_row, hit_pos, hit_score);
+}
+
+// the same with strand[n_rows] of the batch
+template <bool FILL>
+__global__ __launch_bounds__(PW_THREADS) void pw_hits_strand_kernel(const TbTrack *__restrict__ table, int n_tracks, const int32_t *__restrict__ track_of,
+                                                                    const int32_t *__restrict__ start, const int8_t *__restrict__ strand, int64_t n_rows,
+                                                                    int width, const int64_t *__restrict__ row_off, int64_t total, int do_mask, PwSet pw,
+                                                                    PhThresholds thr, int64_t tile_first, int64_t tile_count, int64_t tiles, int32_t *counts,
+                                                                    const int64_t *__restrict__ bases, int32_t *__restrict__ hit_row,
+                                                                    int32_t *__restrict__ hit_pos, float *__restrict__ hit_score)
+{
+    pw_hits_body<true, FILL>(table, n_tracks, track_of, start, strand, n_rows, width, row_off, total, do_mask, pw, thr, tile_first, tile_count, tiles, counts,
+                             bases, hit_row, hit_pos, hit_score);
 }
 
 // heads[m] = bases[m * tiles], m in [0, count): where each matrix's part of the list begins, and (bases[n_mats * tiles]) where it ends

@@ -5,9 +5,11 @@
 // Position weight matrices scored over those rows (bxmi_pwm_*, bxmi_twobit_pwm_*): kernels and semantics in pwm.hpp, those of the
 // thresholded hits (bxmi_twobit_pwm_hits*) in pwm_hits.hpp; they use the same table and scratch and so the same rule.
 // The k-mer spectrum of those rows (bxmi_twobit_kmer_counts*): kernel and semantics in kmer.hpp; the same table, scratch and rule.
-// Strand (bxmi_twobit_bases_strand*, bxmi_twobit_composition_strand*, bxmi_twobit_kmer_counts_strand*): the unstranded entry points
-// are the stranded ones with a NULL strand, which launch the kernels they always launched; a strand array launches the *_strand_kernel
-// of twobit.hpp and kmer.hpp.  The host forms check the entries (0 or 1) and slice the array with the rows of every slab.
+// Strand (bxmi_twobit_bases_strand*, bxmi_twobit_composition_strand*, bxmi_twobit_kmer_counts_strand*, bxmi_twobit_pwm_scores_strand*,
+// bxmi_twobit_pwm_best_strand*, bxmi_twobit_pwm_hits_strand*): the unstranded entry points are the stranded ones with a NULL strand,
+// which launch the kernels they always launched; a strand array launches the *_strand_kernel of twobit.hpp, kmer.hpp, pwm.hpp and
+// pwm_hits.hpp.  The host forms check the entries (0 or 1) and slice the array with the rows of every slab (the best hits and the
+// thresholded hits send the rows, and so the strands, whole).
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -519,51 +521,74 @@ static int pwm_check(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tr
 
 // elements [o_first, o_first + count) of every plane, of rows [row_base, row_base + n_rows); `out` is element o_first's address in
 // plane 0.  keys != nullptr: the best hits instead (the whole batch: row_base == 0), nothing is stored to `out`.
-static int pwm_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n_rows, int64_t row_base, int32_t width,
-                      const int64_t *row_off, int64_t o_first, int64_t count, int do_mask, const bxmi_pwm_t *pwm, float *out, int64_t plane_stride,
+static int pwm_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand, int64_t n_rows,
+                      int64_t row_base, int32_t width, const int64_t *row_off, int64_t o_first, int64_t count, int do_mask, const bxmi_pwm_t *pwm, float *out, int64_t plane_stride,
                       unsigned long long *keys, hipStream_t st)
 {
     if (keys) {  // one launch of at most a device's fill of workgroups, each walking every gridDim.x-th tile: `count` may be a bound
-        hipLaunchKernelGGL(pw_scores_kernel<true>, dim3(fill_grid(div_up(count, PW_TILE))), dim3(PW_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks,
-                           track_of, start, n_rows, row_base, (int)width, row_off, o_first, count, do_mask, pwm->set(), (float *)nullptr, (int64_t)0, keys, n_rows);
+        if (strand)
+            hipLaunchKernelGGL(pw_scores_strand_kernel<true>, dim3(fill_grid(div_up(count, PW_TILE))), dim3(PW_THREADS), 0, st, S.table.as<TbTrack>(),
+                               (int)n_tracks, track_of, start, strand, n_rows, row_base, (int)width, row_off, o_first, count, do_mask, pwm->set(),
+                               (float *)nullptr, (int64_t)0, keys, n_rows);
+        else
+            hipLaunchKernelGGL(pw_scores_kernel<true>, dim3(fill_grid(div_up(count, PW_TILE))), dim3(PW_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks,
+                               track_of, start, n_rows, row_base, (int)width, row_off, o_first, count, do_mask, pwm->set(), (float *)nullptr, (int64_t)0, keys,
+                               n_rows);
         BXMI_LAUNCH_CHECK();
         return BXMI_OK;
     }
     constexpr int64_t PER_LAUNCH = PW_TILES_PER_LAUNCH * PW_TILE;
     for (int64_t done = 0; done < count; done += PER_LAUNCH) {  // a workgroup per tile
         const int64_t m = count - done < PER_LAUNCH ? count - done : PER_LAUNCH;
-        hipLaunchKernelGGL(pw_scores_kernel<false>, dim3((unsigned)div_up(m, PW_TILE)), dim3(PW_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of,
-                           start, n_rows, row_base, (int)width, row_off, o_first + done, m, do_mask, pwm->set(), out + done, plane_stride,
-                           (unsigned long long *)nullptr, (int64_t)0);
+        if (strand)
+            hipLaunchKernelGGL(pw_scores_strand_kernel<false>, dim3((unsigned)div_up(m, PW_TILE)), dim3(PW_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks,
+                               track_of, start, strand, n_rows, row_base, (int)width, row_off, o_first + done, m, do_mask, pwm->set(), out + done, plane_stride,
+                               (unsigned long long *)nullptr, (int64_t)0);
+        else
+            hipLaunchKernelGGL(pw_scores_kernel<false>, dim3((unsigned)div_up(m, PW_TILE)), dim3(PW_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks,
+                               track_of, start, n_rows, row_base, (int)width, row_off, o_first + done, m, do_mask, pwm->set(), out + done, plane_stride,
+                               (unsigned long long *)nullptr, (int64_t)0);
         BXMI_LAUNCH_CHECK();
     }
     return BXMI_OK;
 }
 
-extern "C" int bxmi_twobit_pwm_scores_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
-                                          int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *out,
-                                          void *stream)
+static int pwm_scores_dev(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand,
+                          int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *out, void *stream)
 {
-    const char *who = "bxmi_twobit_pwm_scores_dev";
     BXMI_TRY(pwm_check(who, tracks, n_tracks, track_of, start, n, width, row_off_or_null, total, pwm, true));
     if (n > 0 && total > 0 && !out) return fail(BXMI_EINVAL, "%s: NULL array", who);
     if (n == 0 || total == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_sequence.lock);
     BXMI_TRY(g_sequence.enter());
     BXMI_TRY(sequence_fill_table(g_sequence.bufs, tracks, n_tracks, as_stream(stream)));
-    return pwm_launch(g_sequence.bufs, n_tracks, track_of, start, n, 0, width, row_off_or_null, 0, total, do_mask != 0, pwm, out, total, nullptr,
+    return pwm_launch(g_sequence.bufs, n_tracks, track_of, start, strand, n, 0, width, row_off_or_null, 0, total, do_mask != 0, pwm, out, total, nullptr,
                       as_stream(stream));
 }
 
-extern "C" int bxmi_twobit_pwm_scores(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
-                                      const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *out)
+extern "C" int bxmi_twobit_pwm_scores_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
+                                          int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *out,
+                                          void *stream)
 {
-    const char *who = "bxmi_twobit_pwm_scores";
-    const int64_t *row_off = row_off_or_null;
+    return pwm_scores_dev("bxmi_twobit_pwm_scores_dev", tracks, n_tracks, track_of, start, nullptr, n, width, row_off_or_null, total, do_mask, pwm, out, stream);
+}
+
+extern "C" int bxmi_twobit_pwm_scores_strand_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                                 const int8_t *strand_or_null, int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total,
+                                                 int do_mask, const bxmi_pwm_t *pwm, float *out, void *stream)
+{
+    return pwm_scores_dev("bxmi_twobit_pwm_scores_strand_dev", tracks, n_tracks, track_of, start, strand_or_null, n, width, row_off_or_null, total, do_mask,
+                          pwm, out, stream);
+}
+
+static int pwm_scores_host(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand,
+                           int64_t n, int32_t width, const int64_t *row_off, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *out)
+{
     BXMI_TRY(pwm_check(who, tracks, n_tracks, track_of, start, n, width, row_off, total, pwm, true));
     if (n > 0 && total > 0 && !out) return fail(BXMI_EINVAL, "%s: NULL array", who);
     BXMI_TRY(offsets_check(who, row_off, n, total));
     BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    BXMI_TRY(strand_check(who, strand, n));
     if (n == 0 || total == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_sequence.lock);
     BXMI_TRY(g_sequence.enter(true));
@@ -576,10 +601,12 @@ extern "C" int bxmi_twobit_pwm_scores(bxmi_twobit_t *const *tracks, int32_t n_tr
         const int64_t count = total - o0 < slab ? total - o0 : slab;
         const SaRows rows = sa_rows_of(row_off, n, width, o0, count);  // the slab's rows
         const int64_t *d_off;
+        const int8_t *d_strand;
         BXMI_TRY(stage_rows(S, track_of, start, row_off, rows.r0, rows.m, &d_off, st));
+        BXMI_TRY(stage_strand(S, strand, rows.r0, rows.m, &d_strand, st));
         BXMI_TRY(S.r.reserve((size_t)count * sizeof(float) * (size_t)pwm->n_mats));
-        BXMI_TRY(pwm_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), rows.m, rows.r0, width, d_off, o0, count, do_mask != 0, pwm,
-                            S.r.as<float>(), count, nullptr, st));
+        BXMI_TRY(pwm_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), d_strand, rows.m, rows.r0, width, d_off, o0, count, do_mask != 0,
+                            pwm, S.r.as<float>(), count, nullptr, st));
         for (int32_t k = 0; k < pwm->n_mats; k++)  // each plane's part of the slab
             BXMI_HIP(hipMemcpyAsync(out + (int64_t)k * total + o0, S.r.as<float>() + (int64_t)k * count, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, st));
         BXMI_HIP(hipStreamSynchronize(st));  // the staging is reused by the next slab
@@ -587,45 +614,74 @@ extern "C" int bxmi_twobit_pwm_scores(bxmi_twobit_t *const *tracks, int32_t n_tr
     return BXMI_OK;
 }
 
+extern "C" int bxmi_twobit_pwm_scores(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                                      const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *out)
+{
+    return pwm_scores_host("bxmi_twobit_pwm_scores", tracks, n_tracks, track_of, start, nullptr, n, width, row_off_or_null, total, do_mask, pwm, out);
+}
+
+extern "C" int bxmi_twobit_pwm_scores_strand(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                             const int8_t *strand_or_null, int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total,
+                                             int do_mask, const bxmi_pwm_t *pwm, float *out)
+{
+    return pwm_scores_host("bxmi_twobit_pwm_scores_strand", tracks, n_tracks, track_of, start, strand_or_null, n, width, row_off_or_null, total, do_mask, pwm,
+                           out);
+}
+
 // keys = 0, the walk, the keys unpacked into best_score and best_pos [n_mats][n]
-static int pwm_best_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width, const int64_t *row_off,
-                           int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score, int32_t *best_pos, hipStream_t st)
+static int pwm_best_launch(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand, int64_t n, int32_t width,
+                           const int64_t *row_off, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score, int32_t *best_pos, hipStream_t st)
 {
     const int64_t cells = (int64_t)pwm->n_mats * n;
     BXMI_TRY(S.keys.reserve((size_t)cells * sizeof(unsigned long long)));
     BXMI_HIP(hipMemsetAsync(S.keys.p, 0, (size_t)cells * sizeof(unsigned long long), st));
     if (total > 0)
-        BXMI_TRY(pwm_launch(S, n_tracks, track_of, start, n, 0, width, row_off, 0, total, do_mask, pwm, nullptr, 0, S.keys.as<unsigned long long>(), st));
+        BXMI_TRY(pwm_launch(S, n_tracks, track_of, start, strand, n, 0, width, row_off, 0, total, do_mask, pwm, nullptr, 0, S.keys.as<unsigned long long>(), st));
     hipLaunchKernelGGL(pw_unpack_kernel, dim3((unsigned)div_up(cells, PW_THREADS)), dim3(PW_THREADS), 0, st, S.keys.as<unsigned long long>(), cells, best_score,
                        best_pos);
     BXMI_LAUNCH_CHECK();
     return BXMI_OK;
 }
 
-extern "C" int bxmi_twobit_pwm_best_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
-                                        int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score,
-                                        int32_t *best_pos, void *stream)
+static int pwm_best_dev(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand,
+                        int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score,
+                        int32_t *best_pos, void *stream)
 {
-    const char *who = "bxmi_twobit_pwm_best_dev";
     BXMI_TRY(pwm_check(who, tracks, n_tracks, track_of, start, n, width, row_off_or_null, total, pwm, false));
     if (n > 0 && (!best_score || !best_pos)) return fail(BXMI_EINVAL, "%s: NULL array", who);
     if (n == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_sequence.lock);
     BXMI_TRY(g_sequence.enter());
     BXMI_TRY(sequence_fill_table(g_sequence.bufs, tracks, n_tracks, as_stream(stream)));
-    return pwm_best_launch(g_sequence.bufs, n_tracks, track_of, start, n, width, row_off_or_null, total, do_mask != 0, pwm, best_score, best_pos,
+    return pwm_best_launch(g_sequence.bufs, n_tracks, track_of, start, strand, n, width, row_off_or_null, total, do_mask != 0, pwm, best_score, best_pos,
                            as_stream(stream));
 }
 
-extern "C" int bxmi_twobit_pwm_best(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
-                                    const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score, int32_t *best_pos)
+extern "C" int bxmi_twobit_pwm_best_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
+                                        int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score,
+                                        int32_t *best_pos, void *stream)
 {
-    const char *who = "bxmi_twobit_pwm_best";
-    const int64_t *row_off = row_off_or_null;
+    return pwm_best_dev("bxmi_twobit_pwm_best_dev", tracks, n_tracks, track_of, start, nullptr, n, width, row_off_or_null, total, do_mask, pwm, best_score,
+                        best_pos, stream);
+}
+
+extern "C" int bxmi_twobit_pwm_best_strand_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                               const int8_t *strand_or_null, int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total,
+                                               int do_mask, const bxmi_pwm_t *pwm, float *best_score, int32_t *best_pos, void *stream)
+{
+    return pwm_best_dev("bxmi_twobit_pwm_best_strand_dev", tracks, n_tracks, track_of, start, strand_or_null, n, width, row_off_or_null, total, do_mask, pwm,
+                        best_score, best_pos, stream);
+}
+
+static int pwm_best_host(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand,
+                         int64_t n, int32_t width, const int64_t *row_off, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score,
+                         int32_t *best_pos)
+{
     BXMI_TRY(pwm_check(who, tracks, n_tracks, track_of, start, n, width, row_off, total, pwm, false));
     if (n > 0 && (!best_score || !best_pos)) return fail(BXMI_EINVAL, "%s: NULL array", who);
     BXMI_TRY(offsets_check(who, row_off, n, total));
     BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    BXMI_TRY(strand_check(who, strand, n));
     if (n == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_sequence.lock);
     BXMI_TRY(g_sequence.enter(true));
@@ -637,14 +693,32 @@ extern "C" int bxmi_twobit_pwm_best(bxmi_twobit_t *const *tracks, int32_t n_trac
     const int64_t *d_off;
     BXMI_TRY(S.r.reserve(2 * cell_bytes));
     BXMI_TRY(sequence_fill_table(S, tracks, n_tracks, st));
+    const int8_t *d_strand;
     BXMI_TRY(stage_rows(S, track_of, start, row_off, 0, n, &d_off, st));
+    BXMI_TRY(stage_strand(S, strand, 0, n, &d_strand, st));
     float *d_score = S.r.as<float>();
     int32_t *d_pos = S.r.as<int32_t>() + cells;
-    BXMI_TRY(pwm_best_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), n, width, d_off, total, do_mask != 0, pwm, d_score, d_pos, st));
+    BXMI_TRY(pwm_best_launch(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), d_strand, n, width, d_off, total, do_mask != 0, pwm, d_score, d_pos,
+                             st));
     BXMI_HIP(hipMemcpyAsync(best_score, d_score, cell_bytes, hipMemcpyDeviceToHost, st));
     BXMI_HIP(hipMemcpyAsync(best_pos, d_pos, cell_bytes, hipMemcpyDeviceToHost, st));
     BXMI_HIP(hipStreamSynchronize(st));
     return BXMI_OK;
+}
+
+extern "C" int bxmi_twobit_pwm_best(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                                    const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score, int32_t *best_pos)
+{
+    return pwm_best_host("bxmi_twobit_pwm_best", tracks, n_tracks, track_of, start, nullptr, n, width, row_off_or_null, total, do_mask, pwm, best_score,
+                         best_pos);
+}
+
+extern "C" int bxmi_twobit_pwm_best_strand(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                           const int8_t *strand_or_null, int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask,
+                                           const bxmi_pwm_t *pwm, float *best_score, int32_t *best_pos)
+{
+    return pwm_best_host("bxmi_twobit_pwm_best_strand", tracks, n_tracks, track_of, start, strand_or_null, n, width, row_off_or_null, total, do_mask, pwm,
+                         best_score, best_pos);
 }
 
 // ---- thresholded hits (pwm_hits.hpp) ----
@@ -673,8 +747,8 @@ static int pwm_hits_check(const char *who, bxmi_twobit_t *const *tracks, int32_t
 // their scan into S.hit_bases, and mat_hits[n_mats + 1] (host) from it -- BLOCKS on `st`.  FILL == true: the three hit arrays from
 // S.hit_bases, queued.
 template <bool FILL>
-static int pwm_hits_pass(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width, const int64_t *row_off,
-                         int64_t total, int do_mask, const bxmi_pwm_t *pwm, const float *threshold, int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos,
+static int pwm_hits_pass(SequenceBufs &S, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand, int64_t n, int32_t width,
+                         const int64_t *row_off, int64_t total, int do_mask, const bxmi_pwm_t *pwm, const float *threshold, int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos,
                          float *hit_score, hipStream_t st)
 {
     const int64_t tiles = div_up(total, PW_TILE), cells = tiles * pwm->n_mats;
@@ -685,9 +759,14 @@ static int pwm_hits_pass(SequenceBufs &S, int32_t n_tracks, const int32_t *track
         BXMI_TRY(S.hit_bases.reserve((size_t)(cells + 1 + pwm->n_mats + 1) * sizeof(int64_t)));
     }
     BXMI_TRY(ph_each_launch(tiles, PH_TILES_PER_LAUNCH, PH_TILES_PER_LAUNCH, [&](int64_t first, int64_t count, unsigned grid) {
-        hipLaunchKernelGGL(pw_hits_kernel<FILL>, dim3(grid), dim3(PW_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of, start, n, (int)width, row_off,
-                           total, do_mask, pwm->set(), thr, first, count, tiles, S.hit_counts.as<int32_t>(), S.hit_bases.as<int64_t>(), hit_row, hit_pos,
-                           hit_score);
+        if (strand)
+            hipLaunchKernelGGL(pw_hits_strand_kernel<FILL>, dim3(grid), dim3(PW_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of, start, strand, n,
+                               (int)width, row_off, total, do_mask, pwm->set(), thr, first, count, tiles, S.hit_counts.as<int32_t>(), S.hit_bases.as<int64_t>(),
+                               hit_row, hit_pos, hit_score);
+        else
+            hipLaunchKernelGGL(pw_hits_kernel<FILL>, dim3(grid), dim3(PW_THREADS), 0, st, S.table.as<TbTrack>(), (int)n_tracks, track_of, start, n, (int)width,
+                               row_off, total, do_mask, pwm->set(), thr, first, count, tiles, S.hit_counts.as<int32_t>(), S.hit_bases.as<int64_t>(), hit_row,
+                               hit_pos, hit_score);
         BXMI_LAUNCH_CHECK();
         return (int)BXMI_OK;
     }));
@@ -701,12 +780,10 @@ static int pwm_hits_pass(SequenceBufs &S, int32_t n_tracks, const int32_t *track
     return BXMI_OK;
 }
 
-extern "C" int bxmi_twobit_pwm_hits_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
-                                        int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm,
-                                        const float *threshold, int64_t cap, int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos, float *hit_score,
-                                        void *stream)
+static int pwm_hits_dev(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand,
+                        int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, const float *threshold,
+                        int64_t cap, int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos, float *hit_score, void *stream)
 {
-    const char *who = "bxmi_twobit_pwm_hits_dev";
     BXMI_TRY(pwm_hits_check(who, tracks, n_tracks, track_of, start, n, width, row_off_or_null, total, pwm, threshold, cap, mat_hits, hit_row, hit_pos,
                             hit_score));
     for (int32_t m = 0; m <= pwm->n_mats; m++) mat_hits[m] = 0;
@@ -716,24 +793,41 @@ extern "C" int bxmi_twobit_pwm_hits_dev(bxmi_twobit_t *const *tracks, int32_t n_
     SequenceBufs &S = g_sequence.bufs;
     const hipStream_t st = as_stream(stream);
     BXMI_TRY(sequence_fill_table(S, tracks, n_tracks, st));
-    BXMI_TRY(pwm_hits_pass<false>(S, n_tracks, track_of, start, n, width, row_off_or_null, total, do_mask != 0, pwm, threshold, mat_hits, nullptr, nullptr,
-                                  nullptr, st));
+    BXMI_TRY(pwm_hits_pass<false>(S, n_tracks, track_of, start, strand, n, width, row_off_or_null, total, do_mask != 0, pwm, threshold, mat_hits, nullptr,
+                                  nullptr, nullptr, st));
     const int64_t hits = mat_hits[pwm->n_mats];
     if (hits > cap) return fail(BXMI_ERANGE, "%s: %lld hits need larger arrays than cap=%lld", who, (long long)hits, (long long)cap);
     if (hits == 0) return BXMI_OK;
-    return pwm_hits_pass<true>(S, n_tracks, track_of, start, n, width, row_off_or_null, total, do_mask != 0, pwm, threshold, nullptr, hit_row, hit_pos,
+    return pwm_hits_pass<true>(S, n_tracks, track_of, start, strand, n, width, row_off_or_null, total, do_mask != 0, pwm, threshold, nullptr, hit_row, hit_pos,
                                hit_score, st);
 }
 
-extern "C" int bxmi_twobit_pwm_hits(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
-                                    const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, const float *threshold, int64_t cap,
-                                    int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos, float *hit_score)
+extern "C" int bxmi_twobit_pwm_hits_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n,
+                                        int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm,
+                                        const float *threshold, int64_t cap, int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos, float *hit_score,
+                                        void *stream)
 {
-    const char *who = "bxmi_twobit_pwm_hits";
-    const int64_t *row_off = row_off_or_null;
+    return pwm_hits_dev("bxmi_twobit_pwm_hits_dev", tracks, n_tracks, track_of, start, nullptr, n, width, row_off_or_null, total, do_mask, pwm, threshold, cap,
+                        mat_hits, hit_row, hit_pos, hit_score, stream);
+}
+
+extern "C" int bxmi_twobit_pwm_hits_strand_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                               const int8_t *strand_or_null, int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total,
+                                               int do_mask, const bxmi_pwm_t *pwm, const float *threshold, int64_t cap, int64_t *mat_hits, int32_t *hit_row,
+                                               int32_t *hit_pos, float *hit_score, void *stream)
+{
+    return pwm_hits_dev("bxmi_twobit_pwm_hits_strand_dev", tracks, n_tracks, track_of, start, strand_or_null, n, width, row_off_or_null, total, do_mask, pwm,
+                        threshold, cap, mat_hits, hit_row, hit_pos, hit_score, stream);
+}
+
+static int pwm_hits_host(const char *who, bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, const int8_t *strand,
+                         int64_t n, int32_t width, const int64_t *row_off, int64_t total, int do_mask, const bxmi_pwm_t *pwm, const float *threshold, int64_t cap,
+                         int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos, float *hit_score)
+{
     BXMI_TRY(pwm_hits_check(who, tracks, n_tracks, track_of, start, n, width, row_off, total, pwm, threshold, cap, mat_hits, hit_row, hit_pos, hit_score));
     BXMI_TRY(offsets_check(who, row_off, n, total));
     BXMI_TRY(track_of_check(who, track_of, n, n_tracks));
+    BXMI_TRY(strand_check(who, strand, n));
     for (int32_t m = 0; m <= pwm->n_mats; m++) mat_hits[m] = 0;
     if (n == 0 || total == 0) return BXMI_OK;
     std::lock_guard<std::mutex> hold(g_sequence.lock);
@@ -743,9 +837,11 @@ extern "C" int bxmi_twobit_pwm_hits(bxmi_twobit_t *const *tracks, int32_t n_trac
     // nothing per base comes back: the rows go to the device whole, as for the best hits
     const int64_t *d_off;
     BXMI_TRY(sequence_fill_table(S, tracks, n_tracks, st));
+    const int8_t *d_strand;
     BXMI_TRY(stage_rows(S, track_of, start, row_off, 0, n, &d_off, st));
-    BXMI_TRY(pwm_hits_pass<false>(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), n, width, d_off, total, do_mask != 0, pwm, threshold, mat_hits,
-                                  nullptr, nullptr, nullptr, st));
+    BXMI_TRY(stage_strand(S, strand, 0, n, &d_strand, st));
+    BXMI_TRY(pwm_hits_pass<false>(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), d_strand, n, width, d_off, total, do_mask != 0, pwm, threshold,
+                                  mat_hits, nullptr, nullptr, nullptr, st));
     const int64_t hits = mat_hits[pwm->n_mats];
     if (hits > cap) return fail(BXMI_ERANGE, "%s: %lld hits need larger arrays than cap=%lld", who, (long long)hits, (long long)cap);
     if (hits == 0) return BXMI_OK;
@@ -753,13 +849,30 @@ extern "C" int bxmi_twobit_pwm_hits(bxmi_twobit_t *const *tracks, int32_t n_trac
     BXMI_TRY(S.r.reserve(3 * hit_bytes));
     int32_t *d_row = S.r.as<int32_t>(), *d_pos = d_row + hits;
     float *d_score = S.r.as<float>() + 2 * hits;
-    BXMI_TRY(pwm_hits_pass<true>(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), n, width, d_off, total, do_mask != 0, pwm, threshold, nullptr,
-                                 d_row, d_pos, d_score, st));
+    BXMI_TRY(pwm_hits_pass<true>(S, n_tracks, S.q_track.as<int32_t>(), S.q_start.as<int32_t>(), d_strand, n, width, d_off, total, do_mask != 0, pwm, threshold,
+                                 nullptr, d_row, d_pos, d_score, st));
     BXMI_HIP(hipMemcpyAsync(hit_row, d_row, hit_bytes, hipMemcpyDeviceToHost, st));
     BXMI_HIP(hipMemcpyAsync(hit_pos, d_pos, hit_bytes, hipMemcpyDeviceToHost, st));
     BXMI_HIP(hipMemcpyAsync(hit_score, d_score, hit_bytes, hipMemcpyDeviceToHost, st));
     BXMI_HIP(hipStreamSynchronize(st));
     return BXMI_OK;
+}
+
+extern "C" int bxmi_twobit_pwm_hits(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start, int64_t n, int32_t width,
+                                    const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, const float *threshold, int64_t cap,
+                                    int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos, float *hit_score)
+{
+    return pwm_hits_host("bxmi_twobit_pwm_hits", tracks, n_tracks, track_of, start, nullptr, n, width, row_off_or_null, total, do_mask, pwm, threshold, cap,
+                         mat_hits, hit_row, hit_pos, hit_score);
+}
+
+extern "C" int bxmi_twobit_pwm_hits_strand(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                           const int8_t *strand_or_null, int64_t n, int32_t width, const int64_t *row_off_or_null, int64_t total, int do_mask,
+                                           const bxmi_pwm_t *pwm, const float *threshold, int64_t cap, int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos,
+                                           float *hit_score)
+{
+    return pwm_hits_host("bxmi_twobit_pwm_hits_strand", tracks, n_tracks, track_of, start, strand_or_null, n, width, row_off_or_null, total, do_mask, pwm,
+                         threshold, cap, mat_hits, hit_row, hit_pos, hit_score);
 }
 
 // ---- k-mer counts (kmer.hpp) ----

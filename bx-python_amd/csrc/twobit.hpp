@@ -20,8 +20,9 @@
 //                      last: a 16-bit mask of its positions.  A segment that meets no block of a list runs no chunk loop for it.
 //   the row-segment layer   tb_segment, tb_letters, tb_block_bits, tb_codes: the walk above as this kernel and km_counts_kernel
 //                      (kmer.hpp) share it; the latter's `want` positions per segment hold a halo beyond the segment.  Described
-//                      once, at the helpers.  (pw_scores_kernel and pw_hits_kernel still carry the same walk as their own text:
-//                      on the helpers they measured 1 - 3 % slower at unchanged register counts)
+//                      once, at the helpers.  (pw_scores_kernel and pw_hits_kernel share one staging of their own, pw_stage_columns
+//                      of pwm.hpp, which carries the same walk as its own text: on the helpers they measured 1 - 3 % slower at
+//                      unchanged register counts; it takes tb_minus, tb_complement, tb_code and tb_covered.)
 //   strand             tb_bases_strand_kernel, tb_composition_strand_kernel (and km_counts_strand_kernel of kmer.hpp) take a strand
 //                      per row: a minus row is the reverse complement of the plus row (the reference's SeqFile.reverse_complement,
 //                      lib/bx/seq/seq.py:108-109), the pad mirrored with it and not complemented.  Strand sits in the row-segment layer

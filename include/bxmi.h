@@ -699,7 +699,20 @@ int bxmi_twobit_kmer_force(int way);
  * Every refusal of the sibling applies unchanged.  The host forms also refuse, with BXMI_EINVAL naming the row, before any device
  * call and with the output untouched, a strand entry other than 0 or 1.  The device forms take `strand_or_null` as a device pointer
  * and do not check it, like track_of: ANY NON-ZERO ENTRY IS MINUS.  Track table, scratch, slabs and the one-call-at-a-time rule:
- * as the siblings.  Strand for the pwm calls is not there yet; it will take this same argument. */
+ * as the siblings.
+ *   pwm       (bxmi_twobit_pwm_scores_strand, _best_strand, _hits_strand and their _dev forms; the reference's
+ *             matrix.score_string(reverse_complement(text)), lib/bx/motif/pwm.py:141-149 over _pwm.pyx:23-55.)  The string of a minus
+ *             row is the one the stranded letters call gives with no pad: letter k is the complement (code ^ 2; the case is kept, N
+ *             stays N) of the letter at p = start[i] + (len - 1 - k), p in 64 bits; a p outside [0, size) has no column, and neither
+ *             has any position of a row that names no track.  Everything of the three pwm contracts above holds AS WRITTEN, ON
+ *             THAT STRING: element j of plane m is ((0.0f + v[0][c(j)]) + v[1][c(j + 1)]) + ... + v[W - 1][c(j + W - 1)] in ascending
+ *             matrix row, c the column of the strand string's letter -- letter_col is applied to the COMPLEMENTED letter, and the
+ *             alphabet need not be closed under complement; NaN 0x7FC00000 where a letter has no column or the window passes the
+ *             string's end: the last W - 1 elements of the strand's string, which are the FIRST W - 1 genomic positions of the
+ *             row.  best_pos and hit_pos are offsets in the strand's string -- the genomic start of the site is start + len - W -
+ *             pos; the best hit is the greatest score at its FIRST offset in the strand's string; hits come in ascending (matrix,
+ *             row, offset in the strand's string).  This is NOT the reverse-complement matrix on the plus string mirrored: that
+ *             adds the same terms in descending matrix row, which float32 does not round alike. */
 int bxmi_twobit_bases_strand(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
                              const int8_t *strand_or_null, int64_t n, int32_t width,
                       const int64_t *row_off_or_null, int64_t total, int do_mask, int pad, uint8_t *out);
@@ -719,6 +732,27 @@ int bxmi_twobit_kmer_counts_strand_dev(bxmi_twobit_t *const *tracks, int32_t n_t
                                        const int8_t *strand_or_null, int64_t n, int32_t width,
                                 const int64_t *row_off_or_null, int64_t total, int do_mask, int k, int radix, const int8_t *digits, int32_t *counts,
                                 void *stream);
+int bxmi_twobit_pwm_scores_strand(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                  const int8_t *strand_or_null, int64_t n, int32_t width,
+                           const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *out);
+int bxmi_twobit_pwm_scores_strand_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                      const int8_t *strand_or_null, int64_t n, int32_t width,
+                               const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *out, void *stream);
+int bxmi_twobit_pwm_best_strand(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                const int8_t *strand_or_null, int64_t n, int32_t width,
+                         const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score, int32_t *best_pos);
+int bxmi_twobit_pwm_best_strand_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                    const int8_t *strand_or_null, int64_t n, int32_t width,
+                             const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, float *best_score, int32_t *best_pos,
+                             void *stream);
+int bxmi_twobit_pwm_hits_strand(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                const int8_t *strand_or_null, int64_t n, int32_t width,
+                         const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, const float *threshold, int64_t cap,
+                         int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos, float *hit_score);
+int bxmi_twobit_pwm_hits_strand_dev(bxmi_twobit_t *const *tracks, int32_t n_tracks, const int32_t *track_of, const int32_t *start,
+                                    const int8_t *strand_or_null, int64_t n, int32_t width,
+                             const int64_t *row_off_or_null, int64_t total, int do_mask, const bxmi_pwm_t *pwm, const float *threshold, int64_t cap,
+                             int64_t *mat_hits, int32_t *hit_row, int32_t *hit_pos, float *hit_score, void *stream);
 
 /* ---- BED text -> SoA columns on the host (the step before the hot path) ------
  * Strict single-pass parser for what lib/bx/bitset_builders.py:33-46 and
