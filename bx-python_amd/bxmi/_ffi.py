@@ -100,6 +100,10 @@ _SIGNATURES = {
     "bxmi_beds_summarize": [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp],
     "bxmi_beds_summarize_dev": [vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp],
     "bxmi_twobit_create": [vp, i64, vp, vp, i64, vp, vp, i64, _p(vp)],
+    "bxmi_twobit_create_letters": [vp, i64, i32, _p(vp)],
+    "bxmi_twobit_create_letters_dev": [vp, i64, i32, _p(vp), vp],
+    "bxmi_twobit_create_nib": [vp, i64, i32, _p(vp)],
+    "bxmi_twobit_arrays": [vp, vp, vp, vp, vp, vp],
     "bxmi_twobit_destroy": [vp],
     "bxmi_twobit_info": [vp, _p(i64), _p(i64), _p(i64)],
     "bxmi_twobit_bases": [vp, i32, vp, vp, i64, i32, vp, i64, C.c_int, C.c_int, vp],

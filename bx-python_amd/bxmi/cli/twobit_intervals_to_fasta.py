@@ -7,6 +7,9 @@ interval instead: chrom, start, end and the counts A, C, G, T, N, masked.  With 
 missing column or "." means "+"): an interval on "-" prints its reverse complement, the header line gains the strand as a fourth
 field ("> chrom start end strand") and -c counts the strand's letters (the line gains the strand after end).
 
+In place of the 2bit file a FASTA file (.gz too), a nib file or a directory of nib files may be given (the sequence is then the
+file's stem); a letter outside ACGTN, in either case, is refused.
+
 usage: %prog seq.2bit [-c] [-u] [-s] < bed_file.bed
 """
 # The output format is that of the reference's scripts/nib_intervals_to_fasta.py:25-38, which reads one slice per interval; here the
@@ -30,7 +33,7 @@ def main(argv=None, stdin=None, out=None):
     if len(files) != 1 or any(f not in ("-c", "-u", "-s") for f in flags):
         sys.exit(__doc__.replace("%prog", "twobit_intervals_to_fasta"))
     out = out or sys.stdout
-    genome = sequence.TwoBitSet.from_file(files[0], do_mask="-u" not in flags)
+    genome = sequence.TwoBitSet.open(files[0], do_mask="-u" not in flags)
     try:
         rows, track_of = track_rows(stdin or sys.stdin, genome.tracks)
         starts, ends = [r.start for r in rows], [r.end for r in rows]

@@ -10,6 +10,9 @@ printed.  With -o the int32 [intervals, words] array is saved to out.npy instead
 BED decides the strand (a missing column or "." means "+"): the words of an interval on "-" are those of its reverse complement,
 and every line gains the strand as a fourth field (the header "strand").
 
+In place of the 2bit file a FASTA file (.gz too), a nib file or a directory of nib files may be given (the sequence is then the
+file's stem); a letter outside ACGTN, in either case, is refused.
+
 usage: %prog seq.2bit K [-u] [-i] [-c] [-o out.npy] [-s] < bed_file.bed
 """
 # The counts are those of the reference's bx.intseq.ngramcount.count_ngrams over bx.seqmapping.DNA's digits (ngramcount.pyx:34-85),
@@ -42,7 +45,7 @@ def main(argv=None, stdin=None, out=None):
     k = int(files[1])
     kmers.bins_of(k, 4)
     out = out or sys.stdout
-    genome = sequence.TwoBitSet.from_file(files[0], do_mask="-u" not in flags)
+    genome = sequence.TwoBitSet.open(files[0], do_mask="-u" not in flags)
     try:
         rows, track_of = track_rows(stdin or sys.stdin, genome.tracks)
         strands = [r.strand for r in rows] if "-s" in flags else None

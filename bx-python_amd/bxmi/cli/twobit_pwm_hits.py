@@ -10,6 +10,9 @@ are lower case, and so outside an upper-case alphabet, unless -u is given.  With
 missing column or "." means "+"): an interval on "-" is scanned on its reverse complement, its sites are printed at their genomic
 coordinates, and the strand printed is the interval's for the matrix and the opposite one for its reverse complement.
 
+In place of the 2bit file a FASTA file (.gz too), a nib file or a directory of nib files may be given (the sequence is then the
+file's stem); a letter outside ACGTN, in either case, is refused.
+
 usage: %prog seq.2bit matrix.txt THRESHOLD [-r] [-u] [-s] < bed_file.bed
 """
 # A site is an offset of the reference's bx.motif.pwm.ScoringMatrix.score_string on an interval's sequence whose score is >=
@@ -45,7 +48,7 @@ def main(argv=None, stdin=None, out=None):
         matrices = [motif.read_matrix(f)]
     if "-r" in flags:
         matrices.append(matrices[0].reverse_complement())
-    genome = sequence.TwoBitSet.from_file(files[0], do_mask="-u" not in flags)
+    genome = sequence.TwoBitSet.open(files[0], do_mask="-u" not in flags)
     try:
         rows, track_of = track_rows(stdin or sys.stdin, genome.tracks)
         starts, ends = [r.start for r in rows], [r.end for r in rows]

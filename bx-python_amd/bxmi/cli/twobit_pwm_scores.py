@@ -13,6 +13,9 @@ strand as a fourth field ("> chrom start end strand"; with -b the line gains it 
 strand's string and -b prints the offset in that string.  (-r on a "+" interval is not the same numbers: it adds the same terms in
 the opposite order.)
 
+In place of the 2bit file a FASTA file (.gz too), a nib file or a directory of nib files may be given (the sequence is then the
+file's stem); a letter outside ACGTN, in either case, is refused.
+
 usage: %prog seq.2bit matrix.txt [-r] [-b] [-u] [-s] < bed_file.bed
 """
 # The scores are those of the reference's bx.motif.pwm.ScoringMatrix.score_string on each interval's sequence (pwm.py:141-149); here
@@ -34,7 +37,7 @@ def main(argv=None, stdin=None, out=None):
         matrices = [motif.read_matrix(f)]
     if "-r" in flags:
         matrices.append(matrices[0].reverse_complement())
-    genome = sequence.TwoBitSet.from_file(files[0], do_mask="-u" not in flags)
+    genome = sequence.TwoBitSet.open(files[0], do_mask="-u" not in flags)
     try:
         rows, track_of = track_rows(stdin or sys.stdin, genome.tracks)
         starts, ends = [r.start for r in rows], [r.end for r in rows]

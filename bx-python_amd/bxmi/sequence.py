@@ -16,14 +16,26 @@ complemented with the case kept and N left N, the pad of ``matrix`` mirrored wit
 A and T, C and G exchanged.  The host forms take a sequence of "+" / "-", bools or 0 / 1, the ``_dev`` forms an int8, uint8 or bool
 tensor on the device (any non-zero entry is minus; nothing is read back).
 
+Tracks are also BUILT on the device from letters (csrc/twobit_build.hpp): ``TwoBitTrack.from_letters`` (bytes, str or a uint8 array),
+``from_letters_dev`` (a uint8 tensor in HBM -- the output of ``matrix_dev`` or ``sequences_dev``, edited or not -- with no host copy)
+and ``from_nib`` (nibbles as a nib file holds them); ``TwoBitSet.from_fasta``, ``from_nib`` and ``open`` (which looks at the file) make
+whole sets from what the reference reads through the same ``SeqFile.get`` as 2bit.  The N blocks and the mask blocks of a built track
+are the maximal runs of N / n and of lower case, its packed code under N is 0: the arrays a .2bit file of the same letters holds
+(``TwoBitTrack.arrays`` reads them back).  A letter outside ``TCAGNtcagn`` raises BxmiError naming the lowest such position
+(``other="error"``), or becomes N and, if it is lower case, masked (``other="N"``).  One track per record: a FASTA file of very many
+records loads slowly.
+
 Only files whose blocks are sorted, non-empty, disjoint and inside the sequence are accepted -- every real file; for those the
 reference's walk over the blocks is plain coverage.  Anything else raises BxmiError (EINVAL) naming the condition.
 """
 import ctypes as C
+import glob
+import os
+import struct
 
 import numpy as np
 
-from . import _ffi, twobit
+from . import _ffi, fasta, nib, twobit
 from ._ffi import as_i32, call, ptr
 from .summary import _rows_i32, _Track
 
@@ -53,6 +65,72 @@ class TwoBitTrack(_Track):
     def from_arrays(cls, packed, size, n_starts=(), n_sizes=(), m_starts=(), m_sizes=()):
         u32 = [np.asarray(a, dtype=np.int64) for a in (n_starts, n_sizes, m_starts, m_sizes)]
         return cls(twobit.Sequence(size, *u32, np.asarray(packed, dtype=np.uint8)))
+
+    @classmethod
+    def _built(cls, symbol, *args, stream=()):
+        """a track the library builds from letters: `symbol`(*args, &handle[, stream])"""
+        _ffi.require_gpu()
+        self = cls.__new__(cls)
+        h = C.c_void_p()
+        call(symbol, *args, C.byref(h), *stream)
+        self._h = h
+        self.size, self.n_blocks, self.m_blocks = self._info("bxmi_twobit_info", C.c_int64, C.c_int64, C.c_int64)
+        return self
+
+    @classmethod
+    def from_letters(cls, letters, other="error"):
+        """The track of a sequence given as its letters: bytes, str or a uint8 array.  N blocks and mask blocks are the maximal runs
+        of N / n and of lower case.  A letter outside TCAGNtcagn raises BxmiError (EINVAL) naming the lowest such position and its
+        value under other="error"; under other="N" it becomes N, masked as well if it is a lower-case letter."""
+        if isinstance(letters, str):
+            letters = letters.encode("latin-1")
+        if isinstance(letters, (bytes, bytearray, memoryview)):
+            letters = np.frombuffer(bytes(letters), dtype=np.uint8)
+        letters = np.ascontiguousarray(letters)
+        if letters.dtype != np.uint8 or letters.ndim != 1:
+            raise ValueError("letters must be bytes, str or a 1-d uint8 array")
+        return cls._built("bxmi_twobit_create_letters", ptr(letters), len(letters), _other(other))
+
+    @classmethod
+    def from_letters_dev(cls, letters, other="error", stream=None):
+        """`from_letters` of a contiguous uint8 torch tensor on the GPU, of any shape (its elements in memory order are the
+        sequence): the output of `matrix_dev` / `sequences_dev`, edited or not.  Nothing of the letters is read on the host.  The
+        kernels run on torch's current stream (or `stream`), which is synchronised before this returns: the tensor may then be
+        changed or dropped."""
+        import torch
+
+        if not isinstance(letters, torch.Tensor) or letters.dtype != torch.uint8 or not letters.is_cuda or not letters.is_contiguous():
+            raise ValueError("from_letters_dev takes a contiguous uint8 tensor on the device (host letters: from_letters)")
+        if stream is None:
+            stream = torch.cuda.current_stream(letters.device).cuda_stream
+        return cls._built("bxmi_twobit_create_letters_dev", letters.data_ptr(), letters.numel(), _other(other), stream=(stream,))
+
+    @classmethod
+    def from_nib(cls, nibbles, size, other="error"):
+        """The track of `size` bases held as nibbles, (size + 1) // 2 bytes as a nib file holds them (bxmi.nib.read_file).  The codes
+        5-7, which the reference prints as X, are what `other` is about; the mask bit makes them lower case."""
+        nibbles = np.ascontiguousarray(np.frombuffer(bytes(nibbles), dtype=np.uint8) if isinstance(nibbles, (bytes, bytearray, memoryview)) else nibbles)
+        size = int(size)
+        if nibbles.dtype != np.uint8 or nibbles.ndim != 1 or (size >= 0 and len(nibbles) < (size + 1) // 2):
+            raise ValueError("nibbles must hold (size + 1) // 2 bytes")
+        return cls._built("bxmi_twobit_create_nib", ptr(nibbles), size, _other(other))
+
+    def arrays(self):
+        """The track's arrays as a .2bit file holds them, read back from the device -> bxmi.twobit.Sequence.  For a track made from
+        a file's arrays they are those arrays; for a built one, the arrays the builder derived."""
+        packed = np.zeros((self.size + 3) // 4, dtype=np.uint8)
+        blocks = [np.zeros(k, dtype=np.int32) for k in (self.n_blocks, self.n_blocks, self.m_blocks, self.m_blocks)]
+        call("bxmi_twobit_arrays", self._h, ptr(packed), *[ptr(b) for b in blocks])
+        return twobit.Sequence(self.size, *[b.astype(np.uint32) for b in blocks], packed)
+
+
+_OTHER = {"error": 0, "N": 1}  # BXMI_TB_OTHER_REFUSE, BXMI_TB_OTHER_N
+
+
+def _other(other):
+    if other not in _OTHER:
+        raise ValueError("other must be 'error' or 'N', not %r" % (other,))
+    return _OTHER[other]
 
 
 def _pad_byte(pad):
@@ -283,6 +361,64 @@ class TwoBitSet:
     @classmethod
     def from_file(cls, path=None, do_mask=True, data=None):
         return cls(twobit.read_file(path, data=data), do_mask)
+
+    @classmethod
+    def _of_tracks(cls, tracks, do_mask):
+        self = cls.__new__(cls)
+        self.do_mask = bool(do_mask)
+        self.chroms = list(tracks)
+        self.tracks = dict(tracks)
+        self.sizes = {name: self.tracks[name].size for name in self.chroms}
+        return self
+
+    @classmethod
+    def from_fasta(cls, path=None, do_mask=True, other="error", data=None):
+        """A FASTA file (bxmi.fasta.read_file: .gz accepted) on the device, one track per record, built there from the letters.
+        `other`: as TwoBitTrack.from_letters."""
+        tracks = {}
+        try:
+            for name, letters in fasta.read_file(path, data=data).items():
+                tracks[name] = TwoBitTrack.from_letters(letters, other)
+        except Exception:
+            _ffi.close_all(tracks.values())
+            raise
+        return cls._of_tracks(tracks, do_mask)
+
+    @classmethod
+    def from_nib(cls, paths_or_dir, do_mask=True, other="error"):
+        """nib files on the device, one track each, named by the files' stems: a path, a list of paths, or a directory (its *.nib
+        files in sorted order)."""
+        if isinstance(paths_or_dir, (str, os.PathLike)):
+            paths = sorted(glob.glob(os.path.join(paths_or_dir, "*.nib"))) if os.path.isdir(paths_or_dir) else [paths_or_dir]
+        else:
+            paths = list(paths_or_dir)
+        tracks = {}
+        try:
+            for path in paths:
+                name = os.path.splitext(os.path.basename(path))[0]
+                if name in tracks:
+                    raise ValueError("two nib files named %r" % name)
+                size, nibbles, _ = nib.read_file(path)
+                tracks[name] = TwoBitTrack.from_nib(nibbles, size, other)
+        except Exception:
+            _ffi.close_all(tracks.values())
+            raise
+        return cls._of_tracks(tracks, do_mask)
+
+    @classmethod
+    def open(cls, path, do_mask=True, other="error"):
+        """Whatever sequence file `path` is: a directory (of nib files), or by its first four bytes a .2bit file or a nib file, and
+        otherwise FASTA."""
+        if os.path.isdir(path):
+            return cls.from_nib(path, do_mask, other)
+        with open(path, "rb") as f:
+            head = f.read(4)
+        magic = struct.unpack(">L", head)[0] if len(head) == 4 else None
+        if magic in (twobit.MAGIC, twobit.MAGIC_SWAP):
+            return cls.from_file(path, do_mask)
+        if magic in (nib.MAGIC, nib.MAGIC_SWAP):
+            return cls.from_nib(path, do_mask, other)
+        return cls.from_fasta(path, do_mask, other)
 
     def close(self):
         _ffi.close_all(self.tracks.values())

@@ -10,6 +10,8 @@
 // which launch the kernels they always launched; a strand array launches the *_strand_kernel of twobit.hpp, kmer.hpp, pwm.hpp and
 // pwm_hits.hpp.  The host forms check the entries (0 or 1) and slice the array with the rows of every slab (the best hits and the
 // thresholded hits send the rows, and so the strands, whole).
+// Tracks from letters (bxmi_twobit_create_letters, _create_letters_dev, _create_nib): kernels and semantics in twobit_build.hpp; they
+// fill the buffers bxmi_twobit_create fills from a file's arrays and end with the same twobit_finish.  Their scratch is the call's own.
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -27,6 +29,7 @@
 #undef sm_summary_kernel
 #undef sa_arrays_kernel
 #include "twobit.hpp"
+#include "twobit_build.hpp"
 #include "pwm.hpp"
 #include "pwm_hits.hpp"
 #include "kmer.hpp"
@@ -109,6 +112,39 @@ int running_codes(DevBuf &planes, int64_t items, DevBuf &table, DevBuf &scratch,
 }
 }  // namespace
 
+// What every builder of a track ends with, its nine buffers but ckpt and n_codes filled: the checkpoints, then the counts under the
+// N blocks from them.  Queued on st and waited for.
+static int twobit_finish(bxmi_twobit &t, hipStream_t st)
+{
+    const int64_t size = t.size, n_blocks = t.n_blocks, ckpts = div_up(size, TB_CKPT);
+    DevBuf planes, scratch;
+    const int64_t most = ckpts > n_blocks ? ckpts : n_blocks;
+    BXMI_TRY(planes.reserve((size_t)(most + 1) * 16));
+    BXMI_HIP(hipMemsetAsync(planes.p, 0, (size_t)(ckpts + 1) * 16, st));
+    if (ckpts > 0) {
+        hipLaunchKernelGGL(tb_count_kernel, dim3((unsigned)ckpts), dim3(TB_WAVE), 0, st, t.packed.as<uint32_t>(), size, ckpts + 1, planes.as<int32_t>() + 1);
+        BXMI_LAUNCH_CHECK();
+    }
+    BXMI_TRY(running_codes(planes, ckpts, t.ckpt, scratch, st));
+    BXMI_HIP(hipMemsetAsync(planes.p, 0, (size_t)(n_blocks + 1) * 16, st));
+    for (int64_t first = 0; first < n_blocks; first += TB_ROWS_PER_LAUNCH) {  // (one wave per block: a grid's threads are counted in 32 bits)
+        const int64_t m = n_blocks - first < TB_ROWS_PER_LAUNCH ? n_blocks - first : TB_ROWS_PER_LAUNCH;
+        hipLaunchKernelGGL(tb_under_kernel, dim3((unsigned)m), dim3(TB_WAVE), 0, st, t.packed.as<uint32_t>(), t.ckpt.as<int32_t>(),
+                           t.n_start.as<int32_t>() + first, t.n_end.as<int32_t>() + first, n_blocks + 1, planes.as<int32_t>() + 1 + first);
+        BXMI_LAUNCH_CHECK();
+    }
+    BXMI_TRY(running_codes(planes, n_blocks, t.n_codes, scratch, st));
+    BXMI_HIP(hipStreamSynchronize(st));  // (planes and scratch go away)
+    return BXMI_OK;
+}
+
+// the bytes of `packed` on the device: whole checkpoint blocks, which the kernels read as aligned words
+static size_t packed_room(int64_t size)
+{
+    const int64_t ckpts = div_up(size, TB_CKPT);
+    return (size_t)(ckpts > 0 ? ckpts : 1) * (TB_CKPT / 4);
+}
+
 extern "C" int bxmi_twobit_create(const uint8_t *packed, int64_t size, const int32_t *n_start, const int32_t *n_size, int64_t n_blocks,
                                   const int32_t *m_start, const int32_t *m_size, int64_t m_blocks, bxmi_twobit_t **out)
 {
@@ -127,8 +163,7 @@ extern "C" int bxmi_twobit_create(const uint8_t *packed, int64_t size, const int
     h->n_blocks = n_blocks;
     h->m_blocks = m_blocks;
     // the packed bytes, zero-filled to whole checkpoint blocks: the kernels read aligned words
-    const int64_t ckpts = div_up(size, TB_CKPT);
-    const size_t bytes = (size_t)((size + 3) / 4), room = (size_t)(ckpts > 0 ? ckpts : 1) * (TB_CKPT / 4);
+    const size_t bytes = (size_t)((size + 3) / 4), room = packed_room(size);
     BXMI_TRY(h->packed.reserve(room));
     BXMI_HIP(hipMemset(h->packed.p, 0, room));
     if (bytes) BXMI_HIP(hipMemcpy(h->packed.p, packed, bytes, hipMemcpyHostToDevice));
@@ -138,27 +173,136 @@ extern "C" int bxmi_twobit_create(const uint8_t *packed, int64_t size, const int
     BXMI_TRY(put(h->m_start, m_start, (size_t)m_blocks * 4));
     BXMI_TRY(put(h->m_end, m_end.data(), (size_t)m_blocks * 4));
     BXMI_TRY(put(h->m_cum, m_cum.data(), (size_t)(m_blocks + 1) * 4));
-    // the checkpoints, then the counts under the N blocks from them
-    const hipStream_t st = nullptr;
-    DevBuf planes, scratch;
-    const int64_t most = ckpts > n_blocks ? ckpts : n_blocks;
-    BXMI_TRY(planes.reserve((size_t)(most + 1) * 16));
-    BXMI_HIP(hipMemsetAsync(planes.p, 0, (size_t)(ckpts + 1) * 16, st));
-    if (ckpts > 0) {
-        hipLaunchKernelGGL(tb_count_kernel, dim3((unsigned)ckpts), dim3(TB_WAVE), 0, st, h->packed.as<uint32_t>(), size, ckpts + 1, planes.as<int32_t>() + 1);
-        BXMI_LAUNCH_CHECK();
-    }
-    BXMI_TRY(running_codes(planes, ckpts, h->ckpt, scratch, st));
-    BXMI_HIP(hipMemsetAsync(planes.p, 0, (size_t)(n_blocks + 1) * 16, st));
-    for (int64_t first = 0; first < n_blocks; first += TB_ROWS_PER_LAUNCH) {  // (one wave per block: a grid's threads are counted in 32 bits)
-        const int64_t m = n_blocks - first < TB_ROWS_PER_LAUNCH ? n_blocks - first : TB_ROWS_PER_LAUNCH;
-        hipLaunchKernelGGL(tb_under_kernel, dim3((unsigned)m), dim3(TB_WAVE), 0, st, h->packed.as<uint32_t>(), h->ckpt.as<int32_t>(),
-                           h->n_start.as<int32_t>() + first, h->n_end.as<int32_t>() + first, n_blocks + 1, planes.as<int32_t>() + 1 + first);
-        BXMI_LAUNCH_CHECK();
-    }
-    BXMI_TRY(running_codes(planes, n_blocks, h->n_codes, scratch, st));
-    BXMI_HIP(hipStreamSynchronize(st));  // (planes and scratch go away)
+    BXMI_TRY(twobit_finish(*h, nullptr));
     *out = h.release();
+    return BXMI_OK;
+}
+
+// ---- a track from its letters (bl_build_kernel of twobit_build.hpp) ----
+static int build_check(const char *who, const void *in, int64_t size, int32_t other, bxmi_twobit_t **out)
+{
+    if (!out) return fail(BXMI_EINVAL, "%s: out is NULL", who);
+    *out = nullptr;
+    if (other != BXMI_TB_OTHER_REFUSE && other != BXMI_TB_OTHER_N)
+        return fail(BXMI_EINVAL, "%s: other = %d is neither BXMI_TB_OTHER_REFUSE (0) nor BXMI_TB_OTHER_N (1)", who, (int)other);
+    if (size < 0 || size > TB_SIZE_MAX) return fail(BXMI_EINVAL, "%s: size = %lld outside [0, 2^31-1]", who, (long long)size);
+    if (size > 0 && !in) return fail(BXMI_EINVAL, "%s: NULL input with size = %lld", who, (long long)size);
+    return BXMI_OK;
+}
+
+// running sizes cum[blocks + 1] of the blocks [start[i], end[i])
+static int build_running_sizes(const DevBuf &start, const DevBuf &end, int64_t blocks, DevBuf &cum, DevBuf &scratch, hipStream_t st)
+{
+    BXMI_TRY(cum.reserve((size_t)(blocks + 1) * 4));
+    hipLaunchKernelGGL(bl_sizes_kernel, dim3((unsigned)div_up(blocks + 1, BL_THREADS)), dim3(BL_THREADS), 0, st, start.as<int32_t>(), end.as<int32_t>(), blocks,
+                       cum.as<int32_t>());
+    BXMI_LAUNCH_CHECK();
+    return device_scan<int32_t, int32_t, OpSum, true>(cum.as<int32_t>(), cum.as<int32_t>(), blocks + 1, 0, nullptr, scratch, st);
+}
+
+// d_src: the symbols ON THE DEVICE (size bytes; (size + 1) / 2 of a nib).  Everything is queued on st; one synchronisation reads the
+// two block counts and the lowest other symbol, the last one is twobit_finish's.
+template <int SRC>
+static int build_track(const char *who, const uint8_t *d_src, int64_t size, int32_t other, bxmi_twobit_t **out, hipStream_t st)
+{
+    std::unique_ptr<bxmi_twobit> h(new (std::nothrow) bxmi_twobit());
+    if (!h) return fail(BXMI_ENOMEM, "%s: host allocation failed", who);
+    h->size = size;
+    const size_t room = packed_room(size);
+    BXMI_TRY(h->packed.reserve(room));
+    if (size == 0) BXMI_HIP(hipMemsetAsync(h->packed.p, 0, room, st));  // (else the kernel writes every word)
+    const int64_t tiles = div_up(size, BL_TILE);  // at most 2^19: one launch
+    const int vec = (reinterpret_cast<uintptr_t>(d_src) & (SRC == BL_NIB ? 3 : 15)) == 0;
+    DevBuf counts, bases, scratch, lowest;
+    int64_t head[2] = {0, 0};  // where the mask starts and the N ends begin in the scanned counts
+    if (tiles > 0) {
+        unsigned long long first_other = BL_NO_OTHER;
+        BXMI_TRY(counts.reserve((size_t)tiles * BL_LISTS * 4));
+        BXMI_TRY(bases.reserve((size_t)(tiles * BL_LISTS + 1) * 8));
+        BXMI_TRY(lowest.reserve(8));
+        BXMI_HIP(hipMemsetAsync(lowest.p, 0xFF, 8, st));
+        hipLaunchKernelGGL((bl_build_kernel<SRC, false>), dim3((unsigned)tiles), dim3(BL_THREADS), 0, st, d_src, size, vec, tiles, (int64_t)(room / 4),
+                           h->packed.as<uint32_t>(), counts.as<int32_t>(), (int)(other == BXMI_TB_OTHER_REFUSE), lowest.as<unsigned long long>(),
+                           (const int64_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
+        BXMI_LAUNCH_CHECK();
+        BXMI_TRY((device_scan<int32_t, int64_t, OpSum, false>(counts.as<int32_t>(), bases.as<int64_t>(), tiles * BL_LISTS, (int64_t)0,
+                                                              bases.as<int64_t>() + tiles * BL_LISTS, scratch, st)));
+        BXMI_HIP(hipMemcpyAsync(&first_other, lowest.p, 8, hipMemcpyDeviceToHost, st));
+        BXMI_HIP(hipMemcpyAsync(&head[0], bases.as<int64_t>() + tiles, 8, hipMemcpyDeviceToHost, st));
+        BXMI_HIP(hipMemcpyAsync(&head[1], bases.as<int64_t>() + 2 * tiles, 8, hipMemcpyDeviceToHost, st));
+        BXMI_HIP(hipStreamSynchronize(st));
+        if (other == BXMI_TB_OTHER_REFUSE && first_other != BL_NO_OTHER) {
+            const long long at = (long long)(first_other >> 8);
+            const unsigned v = (unsigned)(first_other & 0xFFu);
+            if (SRC == BL_NIB) return fail(BXMI_EINVAL, "%s: position %lld holds nibble 0x%X (code %u), none of the codes 0 - 4 (T C A G N)", who, at, v, v & 7u);
+            return fail(BXMI_EINVAL, "%s: position %lld holds byte 0x%02X, none of TCAGNtcagn", who, at, v);
+        }
+    }
+    h->n_blocks = head[0];
+    h->m_blocks = head[1] - head[0];
+    BXMI_TRY(h->n_start.reserve((size_t)(h->n_blocks ? h->n_blocks * 4 : 8)));
+    BXMI_TRY(h->n_end.reserve((size_t)(h->n_blocks ? h->n_blocks * 4 : 8)));
+    BXMI_TRY(h->m_start.reserve((size_t)(h->m_blocks ? h->m_blocks * 4 : 8)));
+    BXMI_TRY(h->m_end.reserve((size_t)(h->m_blocks ? h->m_blocks * 4 : 8)));
+    if (h->n_blocks + h->m_blocks > 0) {
+        hipLaunchKernelGGL((bl_build_kernel<SRC, true>), dim3((unsigned)tiles), dim3(BL_THREADS), 0, st, d_src, size, vec, tiles, (int64_t)(room / 4),
+                           (uint32_t *)nullptr, counts.as<int32_t>(), 0, (unsigned long long *)nullptr, (const int64_t *)bases.as<int64_t>(),
+                           h->n_start.as<int32_t>(), h->n_end.as<int32_t>(), h->m_start.as<int32_t>(), h->m_end.as<int32_t>());
+        BXMI_LAUNCH_CHECK();
+    }
+    BXMI_TRY(build_running_sizes(h->n_start, h->n_end, h->n_blocks, h->n_cum, scratch, st));
+    BXMI_TRY(build_running_sizes(h->m_start, h->m_end, h->m_blocks, h->m_cum, scratch, st));
+    BXMI_TRY(twobit_finish(*h, st));  // (waits: counts, bases and scratch go away)
+    *out = h.release();
+    return BXMI_OK;
+}
+
+// the host forms: the whole input into a temporary on the device
+template <int SRC>
+static int build_from_host(const char *who, const uint8_t *in, int64_t size, int32_t other, bxmi_twobit_t **out)
+{
+    BXMI_TRY(build_check(who, in, size, other, out));
+    const size_t bytes = (size_t)(SRC == BL_NIB ? (size + 1) / 2 : size);
+    DevBuf tmp;
+    BXMI_TRY(tmp.reserve(bytes ? bytes : 8));
+    if (bytes) BXMI_HIP(hipMemcpy(tmp.p, in, bytes, hipMemcpyHostToDevice));
+    return build_track<SRC>(who, tmp.as<uint8_t>(), size, other, out, nullptr);
+}
+
+extern "C" int bxmi_twobit_create_letters(const uint8_t *letters, int64_t size, int32_t other, bxmi_twobit_t **out)
+{
+    return build_from_host<BL_ASCII>("bxmi_twobit_create_letters", letters, size, other, out);
+}
+
+extern "C" int bxmi_twobit_create_nib(const uint8_t *nibbles, int64_t size, int32_t other, bxmi_twobit_t **out)
+{
+    return build_from_host<BL_NIB>("bxmi_twobit_create_nib", nibbles, size, other, out);
+}
+
+extern "C" int bxmi_twobit_create_letters_dev(const uint8_t *letters, int64_t size, int32_t other, bxmi_twobit_t **out, void *stream)
+{
+    const char *who = "bxmi_twobit_create_letters_dev";
+    BXMI_TRY(build_check(who, letters, size, other, out));
+    return build_track<BL_ASCII>(who, letters, size, other, out, as_stream(stream));
+}
+
+extern "C" int bxmi_twobit_arrays(const bxmi_twobit_t *h, uint8_t *packed, int32_t *n_start, int32_t *n_size, int32_t *m_start, int32_t *m_size)
+{
+    if (!h) return fail(BXMI_EINVAL, "bxmi_twobit_arrays: NULL handle");
+    const size_t bytes = (size_t)((h->size + 3) / 4);
+    if (packed && bytes) BXMI_HIP(hipMemcpy(packed, h->packed.p, bytes, hipMemcpyDeviceToHost));
+    for (int list = 0; list < 2; list++) {
+        const size_t blocks = (size_t)(list ? h->m_blocks : h->n_blocks);
+        int32_t *start = list ? m_start : n_start, *size = list ? m_size : n_size;
+        if (blocks == 0 || (!start && !size)) continue;
+        std::vector<int32_t> s(blocks), e(blocks);
+        BXMI_HIP(hipMemcpy(s.data(), (list ? h->m_start : h->n_start).p, blocks * 4, hipMemcpyDeviceToHost));
+        if (size) BXMI_HIP(hipMemcpy(e.data(), (list ? h->m_end : h->n_end).p, blocks * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < blocks; i++) {
+            if (start) start[i] = s[i];
+            if (size) size[i] = e[i] - s[i];
+        }
+    }
     return BXMI_OK;
 }
 

@@ -554,6 +554,29 @@ int bxmi_beds_summarize_dev(bxmi_beds_t *const *tracks, int32_t n_tracks, const 
 typedef struct bxmi_twobit bxmi_twobit_t;
 int bxmi_twobit_create(const uint8_t *packed, int64_t size, const int32_t *n_start, const int32_t *n_size, int64_t n_blocks,
                        const int32_t *m_start, const int32_t *m_size, int64_t m_blocks, bxmi_twobit_t **out);
+/* A track from its LETTERS, built on the device (csrc/twobit_build.hpp): what the reference reads through the same SeqFile.get as
+ * 2bit -- FASTA (lib/bx/seq/fasta.py) and nib (nib.py, _nib.pyx) -- and letters that are already in HBM.  `size` symbols: ASCII
+ * bytes (_letters), or nib nibbles, (size + 1) / 2 bytes, the first symbol of a byte in its high half, codes 0-3 = T C A G, 4 = N,
+ * 5-7 = the reference's 'X', bit 3 = lower case (_nib).  The track holds what a .2bit file of the same sequence holds: the N blocks
+ * are the MAXIMAL runs of N / n, the mask blocks the maximal runs of lower case (an n lies in both), the packed code is 0 under N
+ * and the bits after the last base are 0; the results are the same on every run.  A symbol that is none of TCAGNtcagn (nib codes
+ * 5-7) is "other": with other == BXMI_TB_OTHER_REFUSE the call returns BXMI_EINVAL, the message naming the LOWEST such position
+ * and its value, *out stays NULL and nothing is kept; with BXMI_TB_OTHER_N it becomes N, masked too if it is lower case (ASCII
+ * a-z, the nib's bit 3).  Refused with BXMI_EINVAL before the first device call: out == NULL, `other` neither of the two, size
+ * outside [0, 2^31-1], a NULL input with size > 0.  size == 0 makes a valid empty track.
+ * The host forms upload the WHOLE input into a temporary device buffer of its size (freed on return) and block.  The _dev form
+ * takes `letters` on the device (any alignment; 16-byte aligned it is read by 16-byte loads), reads none of it on the host, queues
+ * its kernels on `stream`, synchronises that stream once in the middle to read the two block counts (and the refused position), and
+ * RETURNS AFTER SYNCHRONISING IT: the track is complete and `letters` may be changed or freed. */
+#define BXMI_TB_OTHER_REFUSE 0
+#define BXMI_TB_OTHER_N 1
+int bxmi_twobit_create_letters(const uint8_t *letters, int64_t size, int32_t other, bxmi_twobit_t **out);
+int bxmi_twobit_create_letters_dev(const uint8_t *letters, int64_t size, int32_t other, bxmi_twobit_t **out, void *stream);
+int bxmi_twobit_create_nib(const uint8_t *nibbles, int64_t size, int32_t other, bxmi_twobit_t **out);
+/* The file-order arrays of a track, copied back: packed[(size + 3) / 4], the N blocks and the mask blocks as starts and sizes (the
+ * counts from bxmi_twobit_info).  Any pointer may be NULL.  For a track from bxmi_twobit_create they are its inputs, for a built one
+ * the derived arrays.  Blocks. */
+int bxmi_twobit_arrays(const bxmi_twobit_t *h, uint8_t *packed, int32_t *n_start, int32_t *n_size, int32_t *m_start, int32_t *m_size);
 int bxmi_twobit_destroy(bxmi_twobit_t *h);
 int bxmi_twobit_info(const bxmi_twobit_t *h, int64_t *size, int64_t *n_blocks, int64_t *m_blocks);
 /* _twobit.read for a batch of n rows, the contract of bxmi_spans_arrays with bytes for floats: element j of row i is position p =
